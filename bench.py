@@ -1,7 +1,15 @@
 """bench.py -- the reference's headline workload on MI355X: LaDDer training iterations, CelebA 128x128.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]            (N > 1 without a launcher: spawns the N ranks itself)
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]   (N > 1 without a launcher: spawns the N ranks itself)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
+
+A plain run measures the headline only: set-up, W warm-up steps, ONE timed region of exactly K steps, the outputs of the last timed step
+(`--dump-outputs`), the JSON line.  `--full` adds everything else described below (5 timed regions, the roofline and per-collective
+regions, the sustained leg, the AE-only / forward-only / single-stream extras, the f16x3 leg, the CPU baseline with its parity check).
+`--dump-outputs DIR` writes what the timed path computed in its last timed step as DIR/<name>.npy: the fetched scalars of RUN#1 /
+RUN#2 / RUN#3 (`run1_<name>`, `run2_<name>`, `run3_<name>`, float64) and the parameters after that step (`param__<scope>__<name>`,
+float32; a variable of more than 65 536 elements as a fixed seeded sample of 65 536 of them).  Inputs, initial parameters and noise
+are seeded, so the same arguments give the same inputs in every run.
 
 A "step" = one pass of the hot path over one minibatch = the reference's four sess.run's (codes/base.py:583-641) in
 the post-pretraining regime (fitted-GM feed, prior + inner-sigma training on), through the trainer's own step functions.
@@ -15,14 +23,14 @@ Precision: the headline (`value`, `ms_per_step`, `dtype`, `roofline`, `sustained
 v_mfma_f32_16x16x4_f32, bit-exact fp32 FMA chains.  The 16-bit split format f16x3 (fp32 operands as 2 scaled fp16 planes = 22 bits:
 narrower than fp32) is an explicit opt-in (`"matmul_precision": "f16x3"`) and appears here only as the labelled extra `fast_f16x3`.
 
-Timing: W warm-up steps, then `--repeats` (5) timed regions of EXACTLY K steps each, every region bracketed by
+Timing: W warm-up steps, then `--repeats` timed regions (1; 5 with --full) of EXACTLY K steps each, every region bracketed by
 barrier + torch.cuda.synchronize() on both sides and reduced with MAX over ranks, NO profiler events inside them; `value` is the MEDIAN
-region (all regions are listed in `repeats_images_per_sec`).  The roofline's per-kernel durations come from ONE further region of K steps
+region (all regions are listed in `repeats_images_per_sec`).  --full: the roofline's per-kernel durations come from ONE further region of K steps
 with HIP events around every contraction launch; a `sustained` leg of >= 30 s of back-to-back steps follows (clock / power settle there).
 `roofline.achieved` / `frac` count the FLOPs the kernel ISSUES (`effective`: the reference's operation count of the same launches).
-`parity` (N = 1): the HIP engine evaluated on the FIRST iteration of the `cpu_baseline` leg -- the same 4 images, seeded parameters, noise draws and mixture -- and
+`parity` (N = 1, --full): the HIP engine evaluated on the FIRST iteration of the `cpu_baseline` leg -- the same 4 images, seeded parameters, noise draws and mixture -- and
 the relative deviation of its `elbo` / `elbo_prior` from the fp32 CPU oracle's (north_star: identical inputs, same run; tolerance 1e-3).  `comm.measured_small_allreduce_us`
-(N > 1): back-to-back 8 B / 352 B / 2 KB all-reduces of the job's backend, measured before the timed regions; the ring model's latency term is that 8-byte number.
+(N > 1, --full): back-to-back 8 B / 352 B / 2 KB all-reduces of the job's backend, measured before the timed regions; the ring model's latency term is that 8-byte number.
 Prints ONE JSON line on rank 0.  Exits non-zero when the number of ranks actually running differs from --gpus.
 """
 import argparse
@@ -192,13 +200,48 @@ def roofline_of(prof, precision, step_seconds, traffic_for=None):
                               for r in prof.values() if r is not dom and r.get("bound", "mfma") == "mfma"]}
 
 
+DUMP_SAMPLE = 65536      # --dump-outputs: elements kept of a larger variable (fixed seeded sample)
+DUMP_MAX_BYTES = 64 << 20
+
+
+def last_step_outputs(trainer):
+    """What the timed path computed in its last step, as {name: float32 / float64 array}: the scalars the trainer fetched from RUN#1, RUN#2
+    and RUN#3 and the parameters after the step (variables larger than DUMP_SAMPLE elements as the same seeded sample in every run)."""
+    import numpy as np
+    out = {}
+    for tag, f in (("run1", trainer.last_fetch_ae), ("run2", trainer.last_fetch_sigma), ("run3", trainer.last_fetch_prior)):
+        for k, v in sorted((f or {}).items()):
+            out["%s_%s" % (tag, k)] = np.asarray(v, dtype=np.float64)
+    rng = np.random.default_rng(0)
+    for name, v in trainer.engine.ps.to_dict().items():
+        v = np.asarray(v, dtype=np.float32).reshape(-1)
+        if v.size > DUMP_SAMPLE:
+            v = v[np.sort(rng.choice(v.size, DUMP_SAMPLE, replace=False))]
+        out["param__" + name.replace("/", "__")] = v
+    return out
+
+
+def dump_outputs(arrays, directory):
+    import numpy as np
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_MAX_BYTES, "--dump-outputs: %d bytes" % total
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--repeats", type=int, default=5, help="timed regions of --steps steps each; `value` is their median")
-    ap.add_argument("--sustained-seconds", type=float, default=30.0, help="length of the sustained-throughput leg (0: skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: 5 timed regions, roofline / per-collective regions, sustained leg, AE-only / "
+                         "forward-only / single-stream extras, f16x3 leg, CPU baseline + parity (a plain run times one region only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write the outputs of the last timed step (fetched scalars, parameters) as DIR/<name>.npy")
+    ap.add_argument("--repeats", type=int, default=None, help="timed regions of --steps steps each; `value` is their median (default 1; 5 with --full)")
+    ap.add_argument("--sustained-seconds", type=float, default=None, help="length of the sustained-throughput leg (0: skip; default 0; 30 with --full)")
     ap.add_argument("--config", default=os.path.join(ROOT, "codes", "celeba_config.json"))
     ap.add_argument("--batch", type=int, default=0, help="per-GPU batch override (default: config batch_size)")
     ap.add_argument("--precision", default="", help="matmul_precision override: f32 | f16x3 | bf16x6 | bf16x3 (default: the config's; the shipped configs and the engine default are f32)")
@@ -212,6 +255,10 @@ def main():
                          "configs, whose ~350 short launches per iteration are host-bound in eager mode: 2.87 -> 2.49 ms on digit); "
                          "the per-kernel profile then comes from a second, eager pass after the timed region")
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
+    if args.sustained_seconds is None:
+        args.sustained_seconds = 30.0 if args.full else 0.0
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         spawn_ranks(args)                                       # never returns
@@ -250,7 +297,7 @@ def main():
     # measured small-message all-reduce latency of THIS job's backend, before anything is timed (the ring model below used an
     # ASSUMED 5 us per hop): 8 B = the pure latency of a collective launch, 2 KB = a C2 batch-norm statistics record, 352 B ~ the C3 partials
     small_allreduce_us = None
-    if world > 1:
+    if world > 1 and args.full:
         small_allreduce_us = {}
         for nbytes in (8, 352, 2048):
             t = torch.zeros(nbytes // 4, device="cuda")
@@ -323,10 +370,10 @@ def main():
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
         return float(t.item())
 
-    def measure(trainer, steps, warmup, repeats, sustained_seconds, profile):
-        """One precision leg under the full protocol: W warm-up steps, `repeats` timed regions of EXACTLY `steps` steps (NO profiler
-        events inside them), then -- `profile` -- one more region of the same length with HIP events around the contraction launches
-        (the roofline's per-kernel durations: live, same process, same state, same command), then the sustained leg."""
+    def measure(trainer, steps, warmup, repeats, sustained_seconds, profile, dump=False):
+        """One precision leg: W warm-up steps, `repeats` timed regions of EXACTLY `steps` steps (NO profiler events inside them), the
+        outputs of the last timed step (`dump`), then -- `profile` -- one more region of the same length with HIP events around the
+        contraction launches (the roofline's per-kernel durations: live, same process, same state, same command), then the sustained leg."""
         graphs = trainer.engine.use_graphs and world == 1
         step = lambda: (trainer.train_step_ae(cur_lr=lr, batch_data=x), trainer.train_step_prior(batch_data=x))
         if graphs:                                              # set-up, not warm-up: capture the four run graphs first
@@ -336,6 +383,7 @@ def main():
         for _ in range(warmup):
             step()
         dts = [timed(step, steps) for _ in range(max(1, repeats))]
+        outputs = last_step_outputs(trainer) if dump else None
         prof, prof_seconds = None, None
         comm = trainer.engine.ctx.comm
         if profile:
@@ -353,7 +401,7 @@ def main():
             if graphs:
                 trainer.engine.use_graphs = True
         dt = sorted(dts)[len(dts) // 2]                         # the median region
-        res = dict(value=B * world * steps / dt, ms_per_step=1e3 * dt / steps, dts=dts, prof=prof, prof_seconds=prof_seconds, graphs=graphs,
+        res = dict(value=B * world * steps / dt, ms_per_step=1e3 * dt / steps, dts=dts, prof=prof, prof_seconds=prof_seconds, graphs=graphs, outputs=outputs,
                    comm=comm_table if profile else None,
                    profiled_region_images_per_sec=(B * world * steps / prof_seconds) if prof_seconds else None)
         if sustained_seconds > 0:
@@ -380,7 +428,10 @@ def main():
                      "reference's count (1 of 16 behind the factor-4 resize), the tap-folded form 25 of 36" % ", ".join("%s %.4g/36" % (k, 36 * (1 - skipped.get(k, 11.0 / 36.0))) for k in sorted(used)))
         return dict(fl, note=note)
 
-    head = measure(trainer, args.steps, args.warmup, args.repeats, args.sustained_seconds, not args.no_profile)
+    head = measure(trainer, args.steps, args.warmup, args.repeats, args.sustained_seconds, args.full and not args.no_profile,
+                   dump=bool(args.dump_outputs) and rank == 0)
+    if head["outputs"] is not None:
+        dump_outputs(head["outputs"], args.dump_outputs)
     value, dts, prof = head["value"], head["dts"], head["prof"]
     graphs = head["graphs"]
     f = trainer.last_fetch_ae
@@ -397,8 +448,8 @@ def main():
                                    workload_index(cfg, world), cfg["exp_name"], cfg["dim_input_x"], cfg["dim_input_y"], cfg["dim_input_channel"],
                                    cfg["num_hidden_units"], cfg["code_size"], R, K, cfg["n_MC_samples"], B),
                    "global_batch": B * world, "parallelism": "dp%d" % world},
-        "timing": "median of %d timed regions of exactly %d steps (each: barrier + synchronize on both sides, MAX over ranks; no profiler "
-                  "events inside them)" % (len(dts), args.steps),
+        "timing": "%s of exactly %d steps (each: barrier + synchronize on both sides, MAX over ranks; no profiler events inside them)" % (
+                  "median of %d timed regions" % len(dts) if len(dts) > 1 else "one timed region", args.steps),
         "repeats_images_per_sec": [round(B * world * args.steps / t, 2) for t in dts],
         "launch": "hipGraph replay (4 graphs/iteration)" if graphs else "eager", "matmul_precision": precision,
         "elbo": f["elbo"], "elbo_prior": trainer.last_fetch_prior["elbo_prior"],
@@ -446,57 +497,58 @@ def main():
                                             "beyond that pass (~1.4 ms at batch 128)"}
     if "sustained" in head:
         out["sustained"] = head["sustained"]
-    # also the AE-step-only (RUN#1) and forward-only (val_step, VAE fetches) rates; untimed extras after the metric
-    n_x = max(3, args.steps // 2)
-    use_sg, use_mask = trainer.compute_feeddict(x, "VAE")
-    ae_only = lambda: (trainer.engine.run_ae(x, lr, None, use_sg, use_mask), trainer.engine.fetch())
-    ae_only()
-    out["ae_step_only_images_per_sec"] = round(B * world * n_x / timed(ae_only, n_x), 2)
-    fwd_only = lambda: trainer.val_step("VAE", x)
-    fwd_only()
-    out["forward_only_images_per_sec"] = round(B * world * n_x / timed(fwd_only, n_x), 2)
-    if world == 1 and trainer.engine._aux_on and not graphs:
-        # what a data-parallel rank gives up (engine.enable_prior_overlap is off under DP: collectives stay on one stream)
-        trainer.flush()
-        trainer.engine.enable_prior_overlap(False)
-        one = lambda: (trainer.train_step_ae(cur_lr=lr, batch_data=x), trainer.train_step_prior(batch_data=x))
-        one()
-        t1 = timed(one, n_x)
-        trainer.engine.enable_prior_overlap(True)
-        out["single_stream_cost"] = {"ms_per_step_without_prior_overlap": round(1e3 * t1 / n_x, 3), "ms_per_step": out["ms_per_step"],
-                                     "note": "the schedule every rank of a data-parallel job runs (RUN#3 / RUN#4 behind RUN#2 on one stream)"}
-    fl = FLOP_PER_IMG.get(cfg["exp_name"])
-    full_size = bool(fl and int(cfg["num_hidden_units"]) == 512 and int(cfg["code_size"]) == 64)
-    if full_size:
-        fle = executed_flops(trainer.engine, fl)
-        out["flop_per_image"] = fle
-        out["whole_step_tflops_per_gpu"] = round(fle["executed"] * value / world / 1e12, 2)
-        if precision == "f32":
-            out["whole_step_frac_of_fp32_peak"] = round(out["whole_step_tflops_per_gpu"] / FP32_PEAK_TFLOPS, 4)
-    if precision == "f32" and cfg["exp_name"] == "celeba" and not args.no_compare:
-        # labelled EXTRA, never the headline: the same iteration with the contractions on the 16-bit matrix cores in the f16x3 split format
-        # (fp32 operands cut to 2 scaled fp16 planes = 22 significand bits, 3 fp16 MFMAs per product: NARROWER than the reference's fp32;
-        # opt-in through `"matmul_precision": "f16x3"`) -- thinner protocol (3 warm-up, 2 regions of steps/2)
-        cfgx = dict(cfg, matmul_precision="f16x3")
-        with contextlib.redirect_stdout(io.StringIO()):
-            modelx = Model(cfgx, device="cuda:%d" % local, seed=1)
-        trx = BaseTrain_joint(None, modelx, None, cfgx)
-        trx.cur_epoch, trx.gm_params = trainer.cur_epoch, trainer.gm_params
-        hx = measure(trx, n_x, 3, 2, 0, not args.no_profile)
-        ex = {"images_per_sec": round(hx["value"], 2), "ms_per_step": round(hx["ms_per_step"], 3), "steps": n_x, "regions": 2,
-              "matmul_precision": "f16x3", "dtype": "fp32 operands as 2 scaled fp16 planes (22 significand bits), 3 fp16 MFMAs per product, fp32 accumulate",
-              "note": "opt-in fast path; narrower arithmetic than the reference's fp32 -- NOT the headline", "elbo": trx.last_fetch_ae["elbo"]}
-        rlx = roofline_of(hx["prof"], "f16x3", hx["prof_seconds"], traffic_for=(B == 128)) if hx["prof"] else None
-        if rlx is not None:
-            ex["roofline"] = rlx
+    if args.full:
+        # also the AE-step-only (RUN#1) and forward-only (val_step, VAE fetches) rates; untimed extras after the metric
+        n_x = max(3, args.steps // 2)
+        use_sg, use_mask = trainer.compute_feeddict(x, "VAE")
+        ae_only = lambda: (trainer.engine.run_ae(x, lr, None, use_sg, use_mask), trainer.engine.fetch())
+        ae_only()
+        out["ae_step_only_images_per_sec"] = round(B * world * n_x / timed(ae_only, n_x), 2)
+        fwd_only = lambda: trainer.val_step("VAE", x)
+        fwd_only()
+        out["forward_only_images_per_sec"] = round(B * world * n_x / timed(fwd_only, n_x), 2)
+        if world == 1 and trainer.engine._aux_on and not graphs:
+            # what a data-parallel rank gives up (engine.enable_prior_overlap is off under DP: collectives stay on one stream)
+            trainer.flush()
+            trainer.engine.enable_prior_overlap(False)
+            one = lambda: (trainer.train_step_ae(cur_lr=lr, batch_data=x), trainer.train_step_prior(batch_data=x))
+            one()
+            t1 = timed(one, n_x)
+            trainer.engine.enable_prior_overlap(True)
+            out["single_stream_cost"] = {"ms_per_step_without_prior_overlap": round(1e3 * t1 / n_x, 3), "ms_per_step": out["ms_per_step"],
+                                         "note": "the schedule every rank of a data-parallel job runs (RUN#3 / RUN#4 behind RUN#2 on one stream)"}
+        fl = FLOP_PER_IMG.get(cfg["exp_name"])
+        full_size = bool(fl and int(cfg["num_hidden_units"]) == 512 and int(cfg["code_size"]) == 64)
         if full_size:
-            ex["whole_step_tflops_per_gpu"] = round(executed_flops(trx.engine, fl)["executed"] * hx["value"] / world / 1e12, 2)
-        out["fast_f16x3"] = ex
-        del trx, modelx
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
-        out["cpu_baseline"], sample = cpu_baseline(cfg, gm)
-        if cfg["prior"] == "ours":
-            out["parity"] = parity_on_cpu_sample(cfg, gm, sample, "cuda:%d" % local)
+            fle = executed_flops(trainer.engine, fl)
+            out["flop_per_image"] = fle
+            out["whole_step_tflops_per_gpu"] = round(fle["executed"] * value / world / 1e12, 2)
+            if precision == "f32":
+                out["whole_step_frac_of_fp32_peak"] = round(out["whole_step_tflops_per_gpu"] / FP32_PEAK_TFLOPS, 4)
+        if precision == "f32" and cfg["exp_name"] == "celeba" and not args.no_compare:
+            # labelled EXTRA, never the headline: the same iteration with the contractions on the 16-bit matrix cores in the f16x3 split format
+            # (fp32 operands cut to 2 scaled fp16 planes = 22 significand bits, 3 fp16 MFMAs per product: NARROWER than the reference's fp32;
+            # opt-in through `"matmul_precision": "f16x3"`) -- thinner protocol (3 warm-up, 2 regions of steps/2)
+            cfgx = dict(cfg, matmul_precision="f16x3")
+            with contextlib.redirect_stdout(io.StringIO()):
+                modelx = Model(cfgx, device="cuda:%d" % local, seed=1)
+            trx = BaseTrain_joint(None, modelx, None, cfgx)
+            trx.cur_epoch, trx.gm_params = trainer.cur_epoch, trainer.gm_params
+            hx = measure(trx, n_x, 3, 2, 0, not args.no_profile)
+            ex = {"images_per_sec": round(hx["value"], 2), "ms_per_step": round(hx["ms_per_step"], 3), "steps": n_x, "regions": 2,
+                  "matmul_precision": "f16x3", "dtype": "fp32 operands as 2 scaled fp16 planes (22 significand bits), 3 fp16 MFMAs per product, fp32 accumulate",
+                  "note": "opt-in fast path; narrower arithmetic than the reference's fp32 -- NOT the headline", "elbo": trx.last_fetch_ae["elbo"]}
+            rlx = roofline_of(hx["prof"], "f16x3", hx["prof_seconds"], traffic_for=(B == 128)) if hx["prof"] else None
+            if rlx is not None:
+                ex["roofline"] = rlx
+            if full_size:
+                ex["whole_step_tflops_per_gpu"] = round(executed_flops(trx.engine, fl)["executed"] * hx["value"] / world / 1e12, 2)
+            out["fast_f16x3"] = ex
+            del trx, modelx
+        if rank == 0 and world == 1 and not args.no_cpu_baseline:
+            out["cpu_baseline"], sample = cpu_baseline(cfg, gm)
+            if cfg["prior"] == "ours":
+                out["parity"] = parity_on_cpu_sample(cfg, gm, sample, "cuda:%d" % local)
     if rank == 0:
         print(json.dumps(out), flush=True)
     if world > 1:

@@ -652,7 +652,7 @@ def test_bench_script_two_ranks_one_gpu(tmp_path):
     env = dict(os.environ, LADDER_BENCH_SINGLE_DEVICE="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     # round 3: `python bench.py --gpus 2` WITHOUT a launcher spawns its two ranks itself (through the same torch.distributed.run)
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--repeats", "2",
-           "--sustained-seconds", "0", "--config", os.path.join(root, "codes", "mnist_fashion_config.json")]
+           "--sustained-seconds", "0", "--full", "--config", os.path.join(root, "codes", "mnist_fashion_config.json")]
     out = subprocess.run(cmd, env={k: v for k, v in env.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}, capture_output=True,
                          text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-3000:]
@@ -681,6 +681,40 @@ def test_bench_script_two_ranks_one_gpu(tmp_path):
                          LOCAL_RANK="0"), capture_output=True, text=True, timeout=300)
     assert bad.returncode == 2 and "refusing" in bad.stderr
     assert j["config"]["parallelism"] == "dp2" and j["value"] > 0 and np.isfinite(j["elbo"]) and "cpu_baseline" not in j
+
+
+def test_bench_plain_run_and_dumped_outputs(tmp_path):
+    """A plain `bench.py --gpus 1` run (no --full) times ONE region of exactly --steps steps and prints the headline only; --dump-outputs
+    writes the outputs of the last timed step (fetched scalars, parameters; float32 / float64, at most 64 MB), and a second run with the
+    same arguments writes the same arrays."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "LADDER_BENCH_SINGLE_DEVICE")}
+    runs = []
+    for i in range(2):
+        d = str(tmp_path / ("out%d" % i))
+        cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2", "--dump-outputs", d,
+               "--config", os.path.join(root, "codes", "mnist_fashion_config.json")]
+        out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-3000:]
+        lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, out.stdout[-2000:]
+        j = json.loads(lines[0])
+        assert j["steps"] == 3 and len(j["repeats_images_per_sec"]) == 1 and j["ms_per_step"] > 0 and j["unit"] == "images/sec"
+        assert j["higher_is_better"] is True and j["dtype"] == "f32" and abs(j["value"] * j["ms_per_step"] / 1e3 / j["config"]["global_batch"] - 1) < 1e-2
+        for k in ("roofline", "sustained", "cpu_baseline", "parity", "fast_f16x3", "ae_step_only_images_per_sec", "single_stream_cost"):
+            assert k not in j, k
+        arrays = {f[:-4]: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d))}
+        assert all(f.endswith(".npy") for f in os.listdir(d))
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+        assert float(arrays["run1_elbo"]) == j["elbo"] and float(arrays["run3_elbo_prior"]) == j["elbo_prior"]
+        assert "run2_sigma" in arrays and any(k.startswith("param__decoder__") for k in arrays)
+        runs.append(arrays)
+    assert sorted(runs[0]) == sorted(runs[1])
+    for k, a in runs[0].items():
+        np.testing.assert_array_equal(a, runs[1][k], err_msg=k)
 
 
 @pytest.mark.parametrize("exp,Z", [("mnist_digit", 8), ("mnist_fashion", 16), ("celeba", 16)])

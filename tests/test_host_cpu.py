@@ -351,6 +351,26 @@ def test_bench_refuses_a_gpu_count_it_cannot_honour():
     assert p.returncode == 2 and "refusing" in p.stderr and not [l for l in p.stdout.splitlines() if l.startswith("{")]
 
 
+def test_bench_dump_outputs_names_dtypes_and_fixed_sample(tmp_path):
+    """`bench.py --dump-outputs`: fetched scalars as float64 run<k>_<name>, parameters as float32 param__<scope>__<name>; a variable larger
+    than DUMP_SAMPLE elements is cut to the same seeded sample in every call (two builds compare element for element)."""
+    import types
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    import bench
+    big = np.arange(3 * bench.DUMP_SAMPLE, dtype=np.float32).reshape(3, -1)
+    params = {"decoder/dense/kernel": big, "sigma/Variable": np.float32(0.25)}
+    tr = types.SimpleNamespace(last_fetch_ae={"elbo": -1.5, "loss_ae": 1.5}, last_fetch_sigma={"sigma": 0.1}, last_fetch_prior={"elbo_prior": 2.0},
+                               engine=types.SimpleNamespace(ps=types.SimpleNamespace(to_dict=lambda: params)))
+    a, b = bench.last_step_outputs(tr), bench.last_step_outputs(tr)
+    assert sorted(a) == ["param__decoder__dense__kernel", "param__sigma__Variable", "run1_elbo", "run1_loss_ae", "run2_sigma", "run3_elbo_prior"]
+    assert a["run1_elbo"].dtype == np.float64 and float(a["run1_elbo"]) == -1.5 and a["param__sigma__Variable"].dtype == np.float32
+    k = a["param__decoder__dense__kernel"]
+    assert k.size == bench.DUMP_SAMPLE and np.array_equal(k, b["param__decoder__dense__kernel"]) and np.all(np.diff(k) > 0)
+    bench.dump_outputs(a, str(tmp_path / "d"))
+    assert sorted(os.listdir(tmp_path / "d")) == sorted(n + ".npy" for n in a)
+    assert np.array_equal(np.load(tmp_path / "d" / "param__decoder__dense__kernel.npy"), k)
+
+
 def test_bench_workload_labels_and_default_graph_registry():
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     import bench
