@@ -13,7 +13,7 @@ from . import arch
 from . import layers as _layers
 from .comm import Comm, VirtualComm, VirtualGroup, run_virtual_ranks, _NoComm, _DoneWork, _TracedWork  # noqa: F401  (re-exported: tests, bench.py)
 from .layers import (ADAM_B1, ADAM_B2, ADAM_EPS, BN_EPS, DEFAULT_PRECISION, IN_EPS, PRECISION_NOTES, PRECISIONS, BatchNormAct, Conv2D, Ctx, Dense,  # noqa: F401
-                     DepthToSpace, InstanceNormStyleAct, ParamStore, PlanesOnly, Resize, _igemm, _p, _timed, add_, pad_symmetric)
+                     DepthToSpace, InstanceNormStyleAct, ParamStore, PlanesOnly, Resize, _igemm, _p, _timed, add_, pad_symmetric, plan_decoder)
 from .profiler import KernelProfiler  # noqa: F401
 
 
@@ -125,6 +125,7 @@ class CelebADecoder:
                 si += 1
             self.blocks.append((conv, sty, norm, Resize(ctx, rs, rs) if rs else None))
         self.conv_out = Conv2D(ctx, ps, "decoder/conv2d_8", 1, nh // 4, int(cfg["dim_input_channel"]), 1, "same", None)
+        self._plans, self.plan = {}, None       # plan_decoder's cache; the plan of the last training forward
 
     def forward(self, z):
         B = z.shape[0]
@@ -133,140 +134,60 @@ class CelebADecoder:
         for lyr in self.mapping:
             d = lyr.forward(d)
         dlatent = d
+        keep = self.ctx.keep_activations
         h = self.conv0.forward(encoded.view(B, 1, 1, self.nh))
-        lowres = 0                # != 0: h is the LOW-resolution input of a resize by this factor that the next conv applies itself (forward-only runs)
-        lowres_copy = None        # training forward: the low-resolution tensor behind h = its upsample (kept for the backward pass) ...
-        lo_f = 2                  # ... by this factor
-
-        def _fac(rs_, t):         # integer factor (2 or 4) of resize `rs_` applied to t's map, 0 when it is neither
-            for f_ in (2, 4):
-                if (rs_.oh, rs_.ow) == (f_ * t.shape[1], f_ * t.shape[2]):
-                    return f_
-            return 0
-        # the 1x1 -> 2x2 resize in front of conv2d_1 folds into it like every other one (projected form: all three passes from the 1x1 map)
-        f0 = _fac(self.up0, h)
-        self.up0_folded = bool(f0 and self.blocks[0][0].upf_ok(B, h.shape[1], h.shape[2], f0)
-                               and (not self.ctx.keep_activations or self.blocks[0][0].virtual_upf_ok(B, h.shape[1], h.shape[2], f0)))
-        if self.up0_folded and self.ctx.keep_activations:
-            self.up0.in_shape = tuple(h.shape)
-            lowres_copy, lo_f, h = h, f0, None
-        elif self.up0_folded:
-            lowres = f0
-        else:
-            h = self.up0.forward(h)
-        for bi, (conv, sty, norm, rs) in enumerate(self.blocks):
-            x_lo, lowres_copy = lowres_copy, None
-            conv_done = False
-            if lowres:
-                f_in, lowres = lowres, 0
-                last = (bi == len(self.blocks) - 1 and norm is None and f_in == 2
-                        and (rs is None or (rs.oh, rs.ow) == (2 * h.shape[1], 2 * h.shape[2])))
-                if last:
-                    return conv.forward_up2(h, self.conv_out)
-                h = conv.forward_up2(h, factor=f_in)
-                conv_done = True
-            elif bi == len(self.blocks) - 1 and norm is None and (rs is None or h is None or (rs.oh, rs.ow) == tuple(h.shape[1:3])):
-                if x_lo is not None and lo_f == 2:
-                    # training forward: h = the resized tensor (kept for the backward pass) -- or None when every consumer of it runs from the
-                    # low-resolution tensor (virtual upsample); the convolution reads the low-resolution one
-                    if rs is not None:
-                        rs.in_shape = (x_lo.shape[0], 2 * x_lo.shape[1], 2 * x_lo.shape[2], conv.cout)
-                    return conv.forward_up2(x_lo, self.conv_out, keep_y=True, x_for_backward=h)
-                # the last 3x3 conv feeds the 1x1 output conv directly (its resize is the identity): one fused launch
-                out = conv.forward_fused_proj(h, self.conv_out, keep_y=self.ctx.keep_activations)
-                if out is not None:
-                    if rs is not None:
-                        rs.in_shape = tuple(h.shape[:3]) + (conv.cout,)
-                    return out
-            if not conv_done and x_lo is not None:
-                # training forward of an inner layer (conv2d_6): h = the resized tensor, kept for this layer's filter gradient / backward-data;
-                # the convolution itself reads the low-resolution tensor (25 of 36 tap products)
-                h = conv.forward_up2(x_lo, keep_y=True, x_for_backward=h, factor=lo_f)
-                conv_done = True
-            if not conv_done:
+        plan = plan_decoder(self._plans, self.ctx, self.up0, self.blocks, self.conv_out, tuple(h.shape[:3]))
+        if keep:
+            self.plan = plan          # (the backward pass follows the plan of the training forward, not those of the forward-only runs in between)
+        # h: the tensor at the next conv's resolution (None where the plan never materialises it); lo: the low-resolution tensor behind it where
+        # the conv reads that one.  The 1x1 -> 2x2 resize in front of conv2d_1 folds into it like every other one
+        h, lo = (None, h) if plan[0].resize in ("virtual", "fold_forward_only") else (self.up0.forward(h), None)
+        for e, (conv, sty, norm, rs) in zip(plan, self.blocks):
+            proj = self.conv_out if e.proj else None
+            if e.form != "plain":
+                h = conv.forward_up2(lo, e, proj, keep_y=keep, upsampled=h)
+            elif proj is not None:        # the last 3x3 conv feeds the 1x1 output conv directly (its resize is the identity): one fused launch
+                h = conv.forward_fused_proj(h, proj, keep_y=keep)
+            else:
                 h = conv.forward(h)
-            # the resize behind this block folds into the NEXT conv when that one can take the low-resolution tensor (forward-only runs)
-            nxt = self.blocks[bi + 1][0] if bi + 1 < len(self.blocks) else None
-            f_rs = _fac(rs, h) if (rs is not None and nxt is not None) else 0
-            fold = bool(f_rs and not self.ctx.keep_activations and nxt.upf_ok(h.shape[0], h.shape[1], h.shape[2], f_rs))
+            if proj is not None:
+                return h
+            lo = None
             if norm is not None:
                 style = sty.forward(dlatent)
-                # (training forward: the NEXT conv reads the low-resolution tensor, written beside the resized one it keeps for backward)
-                want_lo = bool(self.ctx.up2 >= 2 and f_rs and not fold and self.ctx.keep_activations
-                               and nxt.upf_ok(h.shape[0], h.shape[1], h.shape[2], f_rs))
-                if want_lo and nxt.virtual_upf_ok(h.shape[0], h.shape[1], h.shape[2], f_rs):
-                    # the resized tensor has no reader left (the next layer's forward, backward-data and filter gradient all take the
-                    # low-resolution tensor): plain instance norm, no resize, 1/4 of the bytes
-                    rs.in_shape = tuple(h.shape)
-                    lowres_copy, lo_f = norm.forward(h, style), f_rs
-                    h = None
-                    continue
-                up = norm.forward_resized(h, style, rs, keep_lowres=want_lo and f_rs == 2) if (rs is not None and not fold) else None
-                if up is not None:
-                    h = up
-                    lowres_copy, lo_f = (norm.y_lo if want_lo else None), 2
-                    continue
-                h = norm.forward(h, style)
-            if fold:
-                lowres = f_rs
-                continue
-            if rs is not None:
-                # (training forward, un-normalised layer in front of a factor-2 resize -- conv2d_5: its output IS the low-resolution tensor)
-                keep_lo = bool(norm is None and self.ctx.up2 >= 2 and self.ctx.keep_activations and f_rs
-                               and nxt.upf_ok(h.shape[0], h.shape[1], h.shape[2], f_rs)
-                               and (f_rs == 2 or nxt.virtual_upf_ok(h.shape[0], h.shape[1], h.shape[2], f_rs)))
-                lo = h
-                if keep_lo and nxt.virtual_upf_ok(h.shape[0], h.shape[1], h.shape[2], f_rs):
-                    rs.in_shape = tuple(h.shape)                 # (virtual upsample: see above)
-                    h = None
-                else:
-                    h = rs.forward(h)
-                lowres_copy, lo_f = (lo if keep_lo else None), (f_rs or 2)
+                h, lo = (norm.forward(h, style), None) if e.norm_out == "lowres" else norm.forward_resized(h, style, rs, e.norm_out == "both")
+            if e.behind in ("virtual", "fold_forward_only"):
+                h, lo = None, h
+            elif e.behind is not None and e.norm_out in (None, "lowres"):
+                # (keep_both behind an un-normalised layer -- conv2d_5: its output IS the low-resolution tensor)
+                h, lo = rs.forward(h), (h if e.behind == "keep_both" else None)
         return self.conv_out.forward(h)
 
     def backward(self, dxhat, need_dz=True):
-        ctx = self.ctx
-        # the last 3x3 conv feeds conv_out directly (its resize is the identity at full resolution): its leaky-ReLU
-        # backward is fused into conv_out's backward-data epilogue (saves a read+write pass over the largest map)
-        last_conv, _, last_norm, last_rs = self.blocks[-1]
-        fuse_last = (last_norm is None and last_conv.act is not None
-                     and (last_rs is None or tuple(last_rs.in_shape[1:3]) == (last_rs.oh, last_rs.ow)))
-        # ... and where that conv ran in the projected form, its backward combination is formed straight from dxhat: neither the 1x1 conv's backward-data
-        # result nor the read of it exist, and conv_out's filter / bias gradient comes out of the same launch (Conv2D.bwd_proj_ok)
-        proj_grad = (dxhat, self.conv_out) if (fuse_last and last_conv.bwd_proj_ok(self.conv_out)) else None
-        dh = None if proj_grad is not None else self.conv_out.backward(dxhat, gate_prev=last_conv.act if fuse_last else None)
+        ctx, plan = self.ctx, self.plan
+        # the last 3x3 conv feeds conv_out directly (its resize is the identity at full resolution): its leaky-ReLU backward is fused into conv_out's
+        # backward-data epilogue (saves a read+write pass over the largest map) -- and where that conv ran in the projected form, its backward combination
+        # is formed straight from dxhat: neither the 1x1 conv's backward-data result nor the read of it exist, and conv_out's filter / bias gradient comes
+        # out of the same launch
+        last = plan[-1]
+        dh = None if last.proj_grad else self.conv_out.backward(dxhat, gate_prev=self.blocks[-1][0].act if last.fuse_last else None)
         ddlat = None
-        lowres = False            # dh is already the gradient of the LOW-resolution tensor behind the next resize (fused into the conv's backward-data)
-        pre_gated = False         # ... and already carries this block's activation derivative (gated low-resolution backward-data of the block above)
-        for bi, (conv, sty, norm, rs) in enumerate(reversed(self.blocks)):
-            gated = False
-            if lowres:
-                lowres = False                                   # (this block's resize transpose is done)
-            elif rs is not None and not (bi == 0 and proj_grad is not None):     # (fuse_last: the last block's resize is the identity)
-                if norm is None and conv.act is not None and not (bi == 0 and fuse_last):
-                    dh, gated = rs.backward(dh, gate=(conv.y, conv.act))   # leaky conv -> resize: its activation backward rides on the transpose
-                else:
-                    dh = rs.backward(dh)
+        for i in range(len(self.blocks) - 1, -1, -1):
+            e, (conv, sty, norm, rs) = plan[i], self.blocks[i]
+            if e.gated:               # leaky conv -> resize: its activation backward rides on the transpose
+                dh, _ = rs.backward(dh, gate=(conv.kept.y, conv.act))
+            elif e.rs_bwd:
+                dh = rs.backward(dh)
             if norm is not None:
                 dh, dstyle = norm.backward(dh)
                 g = sty.backward(dstyle)
                 ddlat = g if ddlat is None else add_(ctx, ddlat, g)
-            # the block below ends in a factor-2 resize: this conv's backward-data can return the gradient of the resize's INPUT (conv2d_7, conv2d_6)
-            below = self.blocks[len(self.blocks) - 2 - bi] if bi + 1 < len(self.blocks) else None
-            lowres = bool(conv.x_is_lo or (
-                below is not None and below[3] is not None and conv.x is not None and (bi == 0 or self.ctx.up2 >= 3)
-                and (below[3].oh, below[3].ow) == tuple(conv.x.shape[1:3]) and conv.x.shape[1] % 2 == 0
-                and tuple(getattr(below[3], "in_shape", (0, 0, 0))[1:3]) == (conv.x.shape[1] // 2, conv.x.shape[2] // 2)
-                and conv.up2t_ok(conv.x.shape[0], conv.x.shape[1] // 2, conv.x.shape[2] // 2)))
-            # ... and that block's own activation backward rides on it when it is an un-normalised leaky conv (conv2d_5 under conv2d_6)
-            lgate = None
-            if (lowres and below is not None and below[2] is None and below[0].act is not None and below[0].y is not None and conv.x is not None
-                    and conv.lowres_gate_ok(conv.x.shape[0], below[0].y.shape[1], below[0].y.shape[2])):
-                lgate = (below[0].y, below[0].act)
-            dh = conv.backward(dh, act_done=(bi == 0 and fuse_last) or gated or pre_gated, lowres_dx=lowres, lowres_gate=lgate,
-                               proj_grad=proj_grad if bi == 0 else None)
-            pre_gated = lgate is not None                      # (the NEXT block's activation backward is done)
-        dh = self.conv0.backward(dh if lowres else self.up0.backward(dh))     # (lowres: conv2d_1 returned the gradient of the 1x1 map itself)
+            # (lowres_dx: the block below ends in a resize and this conv's backward-data returns the gradient of the resize's INPUT; lgate: that block's own
+            # activation backward rides on it when it is an un-normalised leaky conv -- conv2d_5 under conv2d_6)
+            below = self.blocks[i - 1][0]
+            dh = conv.backward(dh, act_done=e.fuse_last or e.gated or e.pre_gated, lowres_dx=e.lowres_dx,
+                               lowres_gate=(below.kept.y, below.act) if e.lgate else None, proj_grad=(dxhat, self.conv_out) if e.proj_grad else None)
+        dh = self.conv0.backward(dh if plan[0].lowres_dx else self.up0.backward(dh))     # (lowres_dx: conv2d_1 returned the gradient of the 1x1 map itself)
         denc = dh.reshape(dh.shape[0], self.nh)
         # mapping MLP: each layer's backward-data epilogue applies the previous layer's leaky-ReLU derivative
         for i in range(len(self.mapping) - 1, -1, -1):

@@ -1,6 +1,7 @@
 """Device context, parameter store and the layers with explicit backward passes of the HIP LaDDer path.  PyTorch supplies device memory, streams and
 torch.distributed only; every arithmetic op below is a call into libladder_hip.so (see _lib.py) -- there is no CPU path."""
 import os
+from collections import namedtuple
 
 import numpy as np
 import torch
@@ -342,9 +343,36 @@ class ParamStore:
 
 
 # ------------------------------------------------------------------------------------------ layers
-UP2T_MIN_PIXELS = int(os.environ.get("LADDER_UP2T_MIN_PIXELS", "256"))      # smallest low-resolution map whose backward-data runs upsample-fused
-PROJ_MAX_BYTES = int(os.environ.get("LADDER_PROJ_MAX_BYTES", str(32 << 30)))  # largest Z / D temporary of a projected pair (conv2d_7 at batch 128: 2.4 GB)
-UP2W_MIN_PIXELS = int(os.environ.get("LADDER_UP2W_MIN_PIXELS", "256"))      # ... and whose filter gradient does (8x8: 758 us fused against 612 direct)
+# environment switches of this module: name -> (default, meaning).  The first two are read at every use (tests flip them between engines of one
+# process), the others once, at import.
+SWITCHES = {
+    "LADDER_DISABLE_HALO": ("0", "1: strict fp32 runs on the round-1 generic gather kernels everywhere, no halo kernels and no projected pairs (test switch)"),
+    "LADDER_ENABLE_LOWRES_GATE": ("0", "1: the low-resolution backward-data of a resize -> conv pair also applies the activation backward of the layer below"),
+    "LADDER_PROJ_MAX_BYTES": (str(32 << 30), "largest Z / D temporary of a projected pair (conv2d_7 at batch 128: 2.4 GB)"),
+    "LADDER_UP2T_MIN_PIXELS": ("256", "smallest low-resolution map whose backward-data runs upsample-fused"),
+    "LADDER_UP2W_MIN_PIXELS": ("256", "... and whose filter gradient does (8x8: 758 us fused against 612 direct)")}
+
+
+def switch(name):
+    """Value of an environment switch of SWITCHES (the only place of this module that reads the environment)."""
+    return os.environ.get(name, SWITCHES[name][0])
+
+
+def halo_disabled():
+    return switch("LADDER_DISABLE_HALO") == "1"
+
+
+UP2T_MIN_PIXELS = int(switch("LADDER_UP2T_MIN_PIXELS"))
+PROJ_MAX_BYTES = int(switch("LADDER_PROJ_MAX_BYTES"))
+UP2W_MIN_PIXELS = int(switch("LADDER_UP2W_MIN_PIXELS"))
+
+# what a Conv2D forward kept for its backward pass:
+#   form    "plain" (the convolution over x) | "tapfold" (resize -> conv as four parity classes with effective taps, 25 of 36 products) |
+#           "projected" (nine 1x1 convolutions on the low-resolution tensor + combination, 9 of 36)
+#   x       the kept input operand; x_kind says what it is: "input" (the layer's input itself) | "upsampled" (the materialised resize of the tensor
+#           the forward read) | "lowres" (the low-resolution tensor: its upsample by `factor` was never materialised)
+#   y       the activated output;  x_amax  the absolute-maximum record of x (f16x3) or None;  pt, pl  top / left padding
+Kept = namedtuple("Kept", "form x x_kind factor y x_amax pt pl")
 
 
 class Conv2D:
@@ -359,15 +387,16 @@ class Conv2D:
         self._packed = {}      # (transpose_flip, ns) -> [weight version, packed bf16 planes]
         self.group = arch.group_of(name + "/kernel")           # optimiser group whose version stamps the packed images
         self.want_bn_sums, self.bn_sums = False, None          # batch-norm statistics of the output from the conv epilogue (RGB conv)
-        self.x_is_up2 = False                                   # set by forward_up2(keep_y): self.x is a factor-2 legacy-bilinear upsample
-        self.x_is_lo = False                                    # ... or self.x is the LOW-resolution tensor itself (the upsample was never materialised)
-        self.lo_factor = 2                                      # ... by this resize factor
-        self.x = self.y = None                                  # operands kept by a training forward for the backward pass
+        self.kept = None                                        # Kept record of the last forward (None: a forward-only run kept nothing, or backward consumed it)
+
+    def _keep(self, form, x, y, x_kind="input", factor=1, x_amax=None, pt=0, pl=0, keep=True):
+        """The one place a forward variant records what the backward pass gets (backward() clears it)."""
+        self.kept = Kept(form, x, x_kind, factor, y, x_amax, pt, pl) if keep else None
 
     def _halo_ok(self, N, H, W, cin, cout):
         """The layer runs on the fused 3x3 halo kernels of the configured precision (strict fp32: csrc/convf32.hip; split formats:
         csrc/convsplit.hip) -- same tiling, same eligibility."""
-        if self.ctx.ns == 0 and os.environ.get("LADDER_DISABLE_HALO") == "1":      # (test switch: the round-1 generic fp32 gather kernels everywhere)
+        if self.ctx.ns == 0 and halo_disabled():      # (test switch: the round-1 generic fp32 gather kernels everywhere)
             return False
         # (strict fp32 also takes the 16- / 8-pixel-wide maps: csrc/convf32s.hip)
         return bool(self.k == 3 and self.stride == 1 and self.padding == "same"
@@ -396,15 +425,15 @@ class Conv2D:
         can re-scale at sample boundaries (a sample's output pixels = whole 32-pixel chunks)."""
         return (Ho * Wo) % 32 == 0
 
-    def _rgb(self, N, H, W):
+    def _rgb(self, N, H, W, pt, pl):
         # (the kernels are f16x3 inside -- the filter gradient takes tensor-wide absmax records -- so they belong to that precision mode)
         return bool(self.ctx.ns == 4 and self.cin == 3 and L.query("ladder_conv_rgb_s2_eligible", N, H, W, self.cin, self.cout, self.k, self.k,
-                                                               self.stride, self.pt, self.pl))
+                                                               self.stride, pt, pl))
 
-    def _rgb_fwd32(self, N, H, W):
+    def _rgb_fwd32(self, N, H, W, pt, pl):
         # strict fp32: the forward of the same layer on the fp32 instantiation of the kernel (its filter gradient stays on the generic kernel)
-        return bool(self.ctx.ns == 0 and self.cin == 3 and os.environ.get("LADDER_DISABLE_HALO") != "1" and
-                    L.query("ladder_conv_rgb_s2_eligible", N, H, W, self.cin, self.cout, self.k, self.k, self.stride, self.pt, self.pl))
+        return bool(self.ctx.ns == 0 and self.cin == 3 and not halo_disabled() and
+                    L.query("ladder_conv_rgb_s2_eligible", N, H, W, self.cin, self.cout, self.k, self.k, self.stride, pt, pl))
 
     def planes_demand(self, in_shape):
         """(wants_planes, needs_fp32) for an input of `in_shape`: whether this layer's forward reads the fp16 plane images of its input
@@ -455,149 +484,219 @@ class Conv2D:
 
     def forward_fused_proj(self, x, proj, keep_y):
         """This 3x3 conv + activation followed by the 1x1 conv `proj` (<= 4 output channels, no activation) in ONE launch of the split
-        halo kernel (ladder_conv3x3_split_proj); returns proj's output or None when the pair is not eligible.  `keep_y` = the
+        halo kernel (ladder_conv3x3_split_proj); returns proj's output (plan_decoder decides eligibility).  `keep_y` = the
         activation is needed later (training forward: both layers' backward read it); a forward-only run never writes it."""
         N, H, W, _ = x.shape
-        if not (self._halo_ok(N, H, W, self.cin, self.cout) and self.cout <= 128 and proj.k == 1 and proj.stride == 1
-                and proj.cout <= 4 and proj.act is None and proj.cin == self.cout):
-            return None
-        self.pt, _ = arch.conv_out(H, self.k, self.stride, self.padding)
-        self.pl, _ = arch.conv_out(W, self.k, self.stride, self.padding)
-        proj.pt = proj.pl = 0
+        pt, _ = arch.conv_out(H, self.k, self.stride, self.padding)
+        pl, _ = arch.conv_out(W, self.k, self.stride, self.padding)
         y = self.ctx.empty(N, H, W, self.cout) if keep_y else None
         out = self.ctx.empty(N, H, W, proj.cout)
-        self.x_amax = self.ctx.absmax(x)
-        args = (_p(x), _p(self.x_amax), _p(self._packed_filter(0)), _p(self.ps.w[self.name + "/bias"]), _p(y),
+        x_amax = self.ctx.absmax(x)
+        args = (_p(x), _p(x_amax), _p(self._packed_filter(0)), _p(self.ps.w[self.name + "/bias"]), _p(y),
                 _p(self.ps.w[proj.name + "/kernel"]), _p(self.ps.w[proj.name + "/bias"]), _p(out), proj.cout, N, H, W, self.cin, self.cout,
                 L.ACT[self.act], self.ctx.ns, self.ctx.stream)
         _timed(256120 + self.ctx.ns, 2.0 * N * H * W * 9 * self.cin * self.cout, "ladder_conv3x3_split_proj", args)
-        self.x, self.y = x, y
-        self.x_is_up2 = self.x_is_lo = False
-        proj.x, proj.y = y, out
+        self._keep("plain", x, y, x_amax=x_amax, pt=pt, pl=pl)
+        proj._keep("plain", y, out)
         return out
 
-    def _proj_rides(self, proj):
-        """The 1x1 conv `proj` behind this layer can ride on the epilogue of its upsample-fused / projected launch."""
-        return bool(self.cout == 128 and proj.k == 1 and proj.stride == 1 and proj.cout <= 4 and proj.act is None and proj.cin == self.cout)
+    def _is_projection(self, proj):
+        """`proj` is a 1x1 conv to <= 4 channels without activation on this layer's output (the RGB conv behind the last 3x3 conv)."""
+        return bool(proj.k == 1 and proj.stride == 1 and proj.cout <= 4 and proj.act is None and proj.cin == self.cout)
 
-    def up2_ok(self, N, H, W):
-        """This layer can take the LOW-resolution tensor [N, H, W, cin] that a factor-2 legacy-bilinear resize would have blown up for it
-        (ladder_conv3x3_up2_split: four output-parity classes with effective taps, 25 instead of 36 low-resolution tap products and no
-        upsampled tensor).  Forward-only runs use it; a training forward keeps the resized tensor for its backward pass."""
-        if self.ctx.ns == 0 and os.environ.get("LADDER_DISABLE_HALO") == "1":
-            return False
-        if self.proj_ok(N, H, W):
-            return True
-        return bool(self.ctx.up2 and self.ctx.ns in (0, 2, 4) and self.k == 3 and self.stride == 1 and self.padding == "same"
-                    and L.query("ladder_conv3x3_up2_split_eligible", N, H, W, self.cin, self.cout, self.ctx.ns))
-
-    def upf_ok(self, N, H, W, f):
-        """up2_ok for a resize factor f: 2 (every form) or 4 (projected form only -- decoder conv2d_3 behind the 2x2 -> 8x8 resize)."""
-        return self.up2_ok(N, H, W) if f == 2 else self.proj_ok(N, H, W, f)
-
-    def virtual_upf_ok(self, N, H, W, f):
-        return self.virtual_up2_ok(N, H, W) if f == 2 else self.proj_ok(N, H, W, f)
-
-    def proj_ok(self, N, H, W, f=2):
-        """'Project, then upsample' (csrc/upproj.hip; strict fp32, config `upsample_fused_convs` >= 4): resize x2 -> this conv over a LOW-resolution
-        [N, H, W, cin] tensor as nine 1x1 convolutions on it (9 of the direct form's 36 products per 2x2 output block, against 25 for the tap-folded
-        form above) + an exact elementwise combination.  Forward, backward-data and the filter gradient all run from the low-resolution tensor.
-        `f` = the resize factor, 2 or 4 (1 of 16 products at 4)."""
-        # (the nine planes Z / D are a transient [N H W, 9 cout] fp32 tensor: beyond PROJ_MAX_BYTES the layer takes the forms that allocate none)
-        return bool(self.ctx.ns == 0 and self.ctx.up2 >= 4 and self.k == 3 and self.stride == 1 and self.padding == "same"
-                    and os.environ.get("LADDER_DISABLE_HALO") != "1" and 36 * N * H * W * self.cout <= PROJ_MAX_BYTES
-                    and L.query("ladder_upfproj_eligible", f, N, H, W, self.cin, self.cout))
-
-    def virtual_up2_ok(self, N, H, W):
-        """A training forward may skip materialising the factor-2 upsample of its [N, H, W, cin] input altogether: strict fp32, and forward,
-        backward-data AND filter gradient of this layer all run from the low-resolution tensor (csrc/convf32.hip)."""
-        if self.proj_ok(N, H, W):
-            return True
-        return bool(self.ctx.ns == 0 and self.ctx.up2 >= 3 and self.up2_ok(N, H, W) and self.up2t_ok(N, H, W) and H * W >= UP2W_MIN_PIXELS
-                    and L.query("ladder_conv3x3_up2_wgrad_eligible", N, H, W, self.cin, self.cout))
-
-    def _forward_proj(self, x, proj, keep_y, upsampled, f=2):
-        """forward_up2 in the project-then-upsample form: Z [M, 9 cout] = x [M, cin] . wcat (dense kernel), then the elementwise combination with
-        bias, activation and -- for the last layer -- the 1x1 output conv on the activated value."""
+    def _forward_proj(self, x, proj, keep_y, f, one_launch):
+        """forward_up2 in the project-then-upsample form (csrc/upproj.hip; strict fp32, config `upsample_fused_convs` >= 4): resize by f -> this conv over
+        the LOW-resolution x as nine 1x1 convolutions on it (9 of the direct form's 36 products per 2x2 output block at f = 2, 1 of 16 at f = 4)
+        + an exact elementwise combination with bias, activation and -- for the last layer -- the 1x1 output conv on the activated value:
+        Z [M, 9 cout] = x [M, cin] . wcat (dense kernel), then the combination; `one_launch`: both in ONE launch.  Returns (y, out)."""
         ctx, st = self.ctx, self.ctx.stream
         N, H, W = x.shape[0], x.shape[1], x.shape[2]
         M, n9 = N * H * W, 9 * self.cout
-        self.pt = self.pl = 1
         flops = 2.0 * N * f * f * H * W * 9 * self.cin * self.cout      # the reference's operation count (algorithmic) ...
         executed = 2.0 * M * self.cin * n9                               # ... of which 9 / 36 are issued (factor 2; 1 / 16 at factor 4)
         ukey = self.name + (":train" if keep_y else "")
         ctx.up2_used[ukey] = ctx.up2_used.get(ukey, 0) + 1
         ctx.up2_skipped[ukey] = 1.0 - 1.0 / (f * f)
         bias = self.ps.w[self.name + "/bias"]
-        if f == 2 and ctx.fuse_fwd and L.query("ladder_up2proj_fused_eligible" if ctx.fuse_fwd >= 2 else "ladder_up2proj_fused_preferred", N, H, W, self.cin, self.cout):
+        y = ctx.empty(N, f * H, f * W, self.cout) if (keep_y or proj is None) else None
+        out, pw, pb, pco = y, None, None, 0
+        if proj is not None:
+            out, pco = ctx.empty(N, 2 * H, 2 * W, proj.cout), proj.cout
+            pw, pb = self.ps.w[proj.name + "/kernel"], self.ps.w[proj.name + "/bias"]
+        if one_launch:
             # round 6: GEMM + combination in ONE launch, the nine planes in an LDS ring (csrc/upproj.hip: up2proj_fused_fwd_kernel) -- Z never reaches HBM
-            y = ctx.empty(N, 2 * H, 2 * W, self.cout) if (keep_y or proj is None) else None
-            out, pw, pb, pco = y, None, None, 0
-            if proj is not None:
-                proj.pt = proj.pl = 0
-                out, pco = ctx.empty(N, 2 * H, 2 * W, proj.cout), proj.cout
-                pw, pb = self.ps.w[proj.name + "/kernel"], self.ps.w[proj.name + "/bias"]
-                proj.x, proj.y = (y, out) if keep_y else (None, None)
             nb = L.query("ladder_up2proj_fused_workspace_bytes", N, H, W, self.cout, pco)
             wsp, wsn = ctx.ws(nb) if nb else (None, 0)
             _timed(128136, flops, "ladder_up2proj_fused_fwd",
                    (_p(x), _p(self._packed_filter(7)), _p(bias), _p(y), _p(pw), _p(pb), _p(out) if proj is not None else None, pco, N, H, W, self.cin, self.cout,
                     L.ACT[self.act], wsp, wsn, st), executed)
-            self.x_amax = None
-            self.lo_factor = f
-            self.x, self.y = ((upsampled if upsampled is not None else x), y) if keep_y else (None, None)
-            self.x_is_up2 = bool(keep_y and upsampled is not None)
-            self.x_is_lo = bool(keep_y and upsampled is None)
-            return out
+            return y, out
+        # (the nine planes Z are a transient [N H W, 9 cout] fp32 tensor: beyond PROJ_MAX_BYTES the layer takes the forms that allocate none)
         z = ctx.empty(M, n9)
         wsp, wsn = ctx.ws(L.query("ladder_igemm_fwd_workspace_bytes", M, self.cin, n9))
         _timed(128132 if L.query("ladder_dense_fwd_is_persistent", M, self.cin, n9) else abs(L.query("ladder_igemm_fwd_tile", M, self.cin, n9)), flops, "ladder_dense_fwd",
                (_p(x), _p(self._packed_filter(6)), None, _p(z), M, self.cin, n9, 0, wsp, wsn, st), executed)
         if proj is not None:
-            proj.pt = proj.pl = 0
+            L.call("ladder_up2proj_fwd_combine", _p(z), _p(bias), _p(y), _p(pw), _p(pb), _p(out), proj.cout, N, H, W, self.cout, L.ACT[self.act], st)
+        else:
+            L.call("ladder_upfproj_fwd_combine", _p(z), _p(bias), _p(y), f, N, H, W, self.cout, L.ACT[self.act], st)
+        return y, out
+
+    def _forward_tapfold(self, x, proj, keep_y):
+        """forward_up2 in the tap-folded form (ladder_conv3x3_up2_split: four output-parity classes with effective taps, 25 instead of 36
+        low-resolution tap products and no upsampled tensor) + its exact border lines.  Returns (y, out, absmax record of x)."""
+        ctx = self.ctx
+        N, H, W = x.shape[0], x.shape[1], x.shape[2]
+        strided = 0
+        bias, wk = self.ps.w[self.name + "/bias"], self.ps.w[self.name + "/kernel"]
+        x_amax = ctx.absmax(x)                                           # (max |upsampled| = max |x|: the resize is a convex combination)
+        flops = 2.0 * N * 4 * H * W * 9 * self.cin * self.cout          # the reference's operation count (algorithmic) ...
+        executed = flops * 25.0 / 36.0                                   # ... of which 25 / 36 are issued
+        ukey = self.name + (":train" if keep_y else "")                   # (bench.py's executed-FLOP model: forward-only / training forward)
+        ctx.up2_used[ukey] = ctx.up2_used.get(ukey, 0) + 1
+        ctx.up2_skipped[ukey] = 11.0 / 36.0
+        wsp, wsn = ctx.ws(L.query("ladder_conv3x3_up2_edges_workspace_bytes", N, H, W, self.cin, self.cout))
+        if proj is not None:
             y = ctx.empty(N, 2 * H, 2 * W, self.cout) if keep_y else None
             out = ctx.empty(N, 2 * H, 2 * W, proj.cout)
-            L.call("ladder_up2proj_fwd_combine", _p(z), _p(bias), _p(y), _p(self.ps.w[proj.name + "/kernel"]), _p(self.ps.w[proj.name + "/bias"]), _p(out),
-                   proj.cout, N, H, W, self.cout, L.ACT[self.act], st)
-            proj.x, proj.y = (y, out) if keep_y else (None, None)
+            pw, pb = self.ps.w[proj.name + "/kernel"], self.ps.w[proj.name + "/bias"]
+            _timed(self._halo_kid(N, H, W, self.cin, 4 * self.cout, self.cout), flops, "ladder_conv3x3_up2_split_proj",
+                   (_p(x), _p(x_amax), _p(self._packed_filter(3)), _p(bias), _p(y), _p(pw), _p(pb), _p(out), proj.cout, N, H, W, self.cin, self.cout,
+                    L.ACT[self.act], ctx.ns, strided, ctx.stream), executed)
+            L.call("ladder_conv3x3_up2_edges", _p(x), _p(wk), _p(bias), _p(y), None, _p(pw), _p(pb), _p(out), proj.cout, N, H, W, self.cin, self.cout,
+                   L.ACT[self.act], strided, wsp, wsn, ctx.stream)
+            return y, out, x_amax
+        y = ctx.empty(N, 2 * H, 2 * W, self.cout)
+        y_amax = ctx.new_amax() if ctx.ns == 4 else None
+        _timed(self._halo_kid(N, H, W, self.cin, 4 * self.cout, self.cout), flops, "ladder_conv3x3_up2_split",
+               (_p(x), _p(x_amax), _p(self._packed_filter(3)), _p(bias), _p(y), _p(y_amax), N, H, W, self.cin, self.cout, L.ACT[self.act], ctx.ns,
+                strided, ctx.stream), executed)
+        L.call("ladder_conv3x3_up2_edges", _p(x), _p(wk), _p(bias), _p(y), _p(y_amax), None, None, None, 0, N, H, W, self.cin, self.cout,
+               L.ACT[self.act], strided, wsp, wsn, ctx.stream)
+        ctx.set_amax(y, y_amax)
+        return y, y, x_amax
+
+    def forward_up2(self, x, pair, proj=None, keep_y=False, upsampled=None):
+        """conv(resize(x)) from the low-resolution x itself, in the form the PairPlan `pair` names; with `proj` the 1x1 output conv rides on the
+        epilogue as in forward_fused_proj, or follows as a launch of its own.  Forward-only runs keep nothing.  A training forward (`keep_y`)
+        keeps `upsampled` = the resized tensor where the plan materialised it (filter gradient and backward-data are then those of the plain
+        convolution on it), else x itself (all three passes run from the low-resolution tensor)."""
+        if proj is not None and pair.proj == "follows":
+            # the fused 1x1 epilogues hold one pixel's 128 channels in a half-wave and project to <= 4 columns (csrc/upproj.hip, convf32.hip):
+            # any other last-layer width (num_hidden_units != 512) runs the pair unfused -- this conv from the low-resolution tensor, then `proj`
+            out = proj.forward(self.forward_up2(x, pair, None, keep_y, upsampled))
+            if not keep_y:
+                proj.kept = None
+            return out
+        x_amax = None
+        if pair.form == "projected":
+            y, out = self._forward_proj(x, proj, keep_y, pair.factor, pair.one_launch)
         else:
-            out = y = ctx.empty(N, f * H, f * W, self.cout)
-            L.call("ladder_upfproj_fwd_combine", _p(z), _p(bias), _p(y), f, N, H, W, self.cout, L.ACT[self.act], st)
-        self.x_amax = None
-        self.lo_factor = f
-        self.x, self.y = ((upsampled if upsampled is not None else x), y) if keep_y else (None, None)
-        self.x_is_up2 = bool(keep_y and upsampled is not None)
-        self.x_is_lo = bool(keep_y and upsampled is None)
+            y, out, x_amax = self._forward_tapfold(x, proj, keep_y)
+        if upsampled is not None:          # x = the factor-2 upsample of a tensor: the filter gradient reads its even sub-grid
+            self._keep(pair.form, upsampled, y, "upsampled", pair.factor, x_amax, 1, 1, keep=keep_y)
+        else:
+            self._keep(pair.form, x, y, "lowres", pair.factor, x_amax, 1, 1, keep=keep_y)
+        if proj is not None:
+            proj._keep("plain", y, out, keep=keep_y)
         return out
 
-    def bwd_proj_ok(self, proj):
-        """The backward combination of this (last) pair can be formed straight from the gradient of the 1x1 conv `proj` behind it -- dy of this layer is
-        never materialised and proj's filter / bias gradient comes out of the same launch (ladder_up2proj_bwd_combine_proj)."""
-        if not (self.ctx.fuse_bwd_proj and self.x_is_lo and self.lo_factor == 2 and self.x is not None and self.y is not None
-                and self.act in (None, "leaky_relu", "relu") and proj.k == 1 and proj.stride == 1 and proj.act is None and proj.cin == self.cout):
-            return False
-        N, H, W, _ = self.x.shape
-        return bool(self.proj_ok(N, H, W, 2) and L.query("ladder_up2proj_bwd_combine_proj_eligible", N, H, W, self.cout, proj.cout))
+    def forward(self, x):
+        N, H, W, _ = x.shape
+        pt, Ho = arch.conv_out(H, self.k, self.stride, self.padding)
+        pl, Wo = arch.conv_out(W, self.k, self.stride, self.padding)
+        y = self.ctx.empty(N, Ho, Wo, self.cout)
+        self._keep("plain", x, y, x_amax=self._forward_plain(x, y, N, H, W, Ho, Wo, pt, pl), pt=pt, pl=pl)
+        return y
+
+    def _forward_plain(self, x, y, N, H, W, Ho, Wo, pt, pl):
+        """The launch(es) of forward(); returns the absolute-maximum record of x where the kernel took one (the filter gradient re-uses it)."""
+        x_amax = None
+        if self._halo_ok(N, H, W, self.cin, self.cout):
+            x_amax = self.ctx.absmax(x)
+            y_amax = self.ctx.new_amax() if self.ctx.ns == 4 else None
+            args = (_p(x), _p(x_amax), _p(self._packed_filter(0)), _p(self.ps.w[self.name + "/bias"]), _p(y), _p(y_amax), N, H, W,
+                    self.cin, self.cout, L.ACT[self.act], self.ctx.ns, self.ctx.stream)
+            self.ctx.set_amax(y, y_amax)
+            _timed(self._halo_kid(N, H, W, self.cin, self.cout), 2.0 * N * H * W * 9 * self.cin * self.cout, "ladder_conv3x3_split", args)
+            return x_amax
+        if self._as_dense(N * H * W):                   # 1x1 conv over a tiny map (decoder conv0 on the 1x1 map) = a batch-sized dense layer
+            L.call("ladder_dense_fwd_small" + self.ctx.sfx, _p(x), _p(self.ps.w[self.name + "/kernel"]), _p(self.ps.w[self.name + "/bias"]), _p(y), N * H * W,
+                   self.cin, self.cout, L.ACT[self.act], self.ctx.stream)
+            return x_amax
+        geo = (N, H, W, self.cin, Ho, Wo, self.cout, self.k, self.k, self.stride, pt, pl)
+        if self._rgb(N, H, W, pt, pl) or self._rgb_fwd32(N, H, W, pt, pl):   # the image-side encoder conv (3 -> Cout channels, stride 2): csrc/convrgb.hip
+            sfx = "" if self.ctx.ns else "_f32"
+            if self.want_bn_sums and self.act is None:
+                wsp, wsn = self.ctx.ws(L.query("ladder_conv_rgb_s2_fwd_bnstats_workspace_bytes", N, H, W, self.cout))
+                self.bn_sums = self.ctx.empty(6 * self.cout)       # sum | sum of squares | min | max per channel
+                L.call("ladder_conv_rgb_s2_fwd_bnstats" + sfx, _p(x), _p(self.ps.w[self.name + "/kernel"]), _p(self.ps.w[self.name + "/bias"]), _p(y),
+                       N, H, W, self.cout, 0, _p(self.bn_sums), wsp, wsn, self.ctx.stream)
+            else:
+                L.call("ladder_conv_rgb_s2_fwd" + sfx, _p(x), _p(self.ps.w[self.name + "/kernel"]), _p(self.ps.w[self.name + "/bias"]), _p(y), N, H,
+                       W, self.cout, L.ACT[self.act], self.ctx.stream)
+            return x_amax
+        if self.ctx.ns and L.query("ladder_conv2d_fwd_split_eligible", *geo):
+            x_amax = self.ctx.absmax(x)
+            nb = L.query("ladder_conv2d_fwd_split_workspace_bytes", *geo)
+            wsp, wsn = self.ctx.ws(nb)
+            if self.want_bn_sums and self.act is None and not nb:
+                snb = L.query("ladder_conv2d_fwd_split_bnstats_workspace_bytes", *geo)
+                if snb:                                  # the epilogue also emits the batch-norm statistics of y (no second pass over it)
+                    swp, swn = self.ctx.ws(snb)
+                    self.bn_sums = self.ctx.empty(6 * self.cout)
+                    L.call("ladder_conv2d_fwd_split_bnstats", _p(self.ctx.planes(x, self._ps(Ho, Wo))), _p(x_amax), _p(self._packed_filter(0)),
+                           _p(self.ps.w[self.name + "/bias"]), _p(y), *geo, 0, self.ctx.ns, _p(self.bn_sums), swp, swn, self.ctx.stream)
+                    return x_amax
+            args = (_p(self.ctx.planes(x, self._ps(Ho, Wo))), _p(x_amax), _p(self._packed_filter(0)), _p(self.ps.w[self.name + "/bias"]), _p(y)) + geo + (
+                L.ACT[self.act], self.ctx.ns, wsp, wsn, self.ctx.stream)
+            if nb:                                       # split-K launch: two kernels, not attributed by the profiler
+                L.call("ladder_conv2d_fwd_split", *args)
+            else:
+                _timed(128120 + self.ctx.ns, 2.0 * N * Ho * Wo * self.k * self.k * self.cin * self.cout, "ladder_conv2d_fwd_split", args)
+            return x_amax
+        if self.ctx.ns == 0 and self.want_bn_sums and self.act is None:
+            snb = L.query("ladder_conv2d_fwd_bnstats_workspace_bytes", *geo)
+            if snb:                                      # strict fp32: the epilogue also emits the batch-norm statistics of y (no second pass over it)
+                swp, swn = self.ctx.ws(snb)
+                self.bn_sums = self.ctx.empty(6 * self.cout)
+                L.call("ladder_conv2d_fwd_bnstats", _p(x), _p(self.ps.w[self.name + "/kernel"]), _p(self.ps.w[self.name + "/bias"]), _p(y), *geo, 0,
+                       _p(self.bn_sums), swp, swn, self.ctx.stream)
+                return x_amax
+        if (self.ctx.ns == 0 and self.k == 3 and self.stride == 2 and pt == 0 and pl == 0 and not halo_disabled()
+                and L.query("ladder_conv3x3_s2_fwd_f32_eligible", N, H, W, self.cin, Ho, Wo, self.cout)):
+            # strict fp32, 3x3 / stride 2 over an even map (encoder conv2d_2 / conv2d_3): a stride-1 correlation over the four pixel-parity classes
+            # of x on the halo kernels (x staged once per slab for all taps; csrc/convf32s.hip): 185 / 115 us against 202 / 127 on the gather kernel.
+            # (Behind the statistics-epilogue branch above: conv2d_1 measures 344 us + a statistics pass here against 356 us with them.)
+            args = (_p(x), _p(self._packed_filter(5)), _p(self.ps.w[self.name + "/bias"]), _p(y), N, H, W, self.cin, Ho, Wo, self.cout,
+                    L.ACT[self.act], self.ctx.stream)
+            _timed(self._halo_kid(N, Ho, Wo, 4 * self.cin, self.cout), 2.0 * N * Ho * Wo * 9 * self.cin * self.cout, "ladder_conv3x3_s2_fwd_f32", args)
+            return x_amax
+        _igemm(self.ctx, "ladder_conv2d_fwd", N * Ho * Wo, self.cin, self.cout, self.k * self.k * self.cin,
+               _p(x), _p(self.ps.w[self.name + "/kernel"]), _p(self.ps.w[self.name + "/bias"]), _p(y),
+               N, H, W, self.cin, Ho, Wo, self.cout, self.k, self.k, self.stride, pt, pl, L.ACT[self.act],
+               conv=(N, H, W, self.cin, Ho, Wo, self.cout, self.k, self.k, self.stride, 1, pt, pl))
+        return x_amax
 
     def _backward_proj(self, dy, need_dx, wgrad, gate, proj_grad=None):
         """Backward of the project-then-upsample form from the low-resolution x: D [M, 9 cout] = (shift o up)^T dy once (elementwise), then
         dWcat = x^T D (+ the bias gradient as the centre plane's column sums) and dx_lo = D . wcatT -- two dense calls, exact on every pixel.
         `proj_grad` = (dyp, proj): dy is not given -- D comes from this layer's activated output and the gradient dyp of the 1x1 conv `proj`
-        behind it, together with proj's own filter / bias gradient (bwd_proj_ok)."""
+        behind it, together with proj's own filter / bias gradient (plan_decoder: proj_grad)."""
         ctx, st = self.ctx, self.ctx.stream
-        x = self.x
+        x, f = self.kept.x, self.kept.factor
         N, H, W, _ = x.shape
-        M, n9, f = N * H * W, 9 * self.cout, self.lo_factor
+        M, n9 = N * H * W, 9 * self.cout
         flops = 2.0 * N * f * f * H * W * 9 * self.cin * self.cout
         executed = 2.0 * M * self.cin * n9
         d = ctx.empty(M, n9)
         if proj_grad is not None:
             dyp, proj = proj_grad
             wsp, wsn = ctx.ws(L.query("ladder_up2proj_bwd_combine_proj_workspace_bytes", N, H, W, self.cout, proj.cout))
-            L.call("ladder_up2proj_bwd_combine_proj", _p(self.y), _p(dyp), _p(proj.ps.w[proj.name + "/kernel"]), _p(d), _p(proj.ps.g[proj.name + "/kernel"]),
+            L.call("ladder_up2proj_bwd_combine_proj", _p(self.kept.y), _p(dyp), _p(proj.ps.w[proj.name + "/kernel"]), _p(d), _p(proj.ps.g[proj.name + "/kernel"]),
                    _p(proj.ps.g[proj.name + "/bias"]) if proj.bias_grad else None, proj.cout, N, H, W, self.cout, L.ACT[self.act] if self.act else 0,
                    wsp, wsn, st)
-            proj.x = proj.y = None
+            proj.kept = None
         else:
             L.call("ladder_upfproj_bwd_combine", _p(dy), _p(d), f, N, H, W, self.cout, st)
         if wgrad:
@@ -625,182 +724,7 @@ class Conv2D:
             else:
                 _timed(abs(L.query("ladder_igemm_fwd_tile", M, n9, self.cin)), flops, "ladder_dense_bwd_data",
                        (_p(d), _p(self._packed_filter(7)), _p(dx), M, self.cin, n9, _p(gy), L.ACT[gact] if gact else 0, wsp, wsn, st), executed)
-        self.x = self.y = None
         return dx
-
-    def forward_up2(self, x, proj=None, keep_y=False, x_for_backward=None, factor=2):
-        """conv(resize2x(x)) from the low-resolution x itself; with `proj` the 1x1 output conv rides on the epilogue as in forward_fused_proj.
-        Forward-only runs keep nothing.  A training forward (`keep_y`) passes `x_for_backward` = the resized tensor, which it has to keep for
-        the backward pass anyway (filter gradient and backward-data are those of the plain convolution on it): x / y are then kept exactly
-        as forward_fused_proj keeps them."""
-        ctx = self.ctx
-        src = x
-        N, H, W = x.shape[0], x.shape[1], x.shape[2]
-        if proj is not None and not self._proj_rides(proj):
-            # the fused 1x1 epilogues hold one pixel's 128 channels in a half-wave and project to <= 4 columns (csrc/upproj.hip, convf32.hip):
-            # any other last-layer width (num_hidden_units != 512) runs the pair unfused -- this conv from the low-resolution tensor, then `proj`
-            y = self.forward_up2(x, None, keep_y, x_for_backward, factor)
-            out = proj.forward(y)
-            if not keep_y:
-                proj.x = proj.y = None
-            return out
-        if self.proj_ok(N, H, W, factor):
-            return self._forward_proj(x, proj, keep_y, x_for_backward, factor)
-        if factor != 2:
-            raise RuntimeError("%s: a factor-%d resize folds into the convolution in the projected form only" % (self.name, factor))
-        self.lo_factor = 2
-        strided = 0
-        upsampled = x_for_backward
-        self.pt = self.pl = 1
-        bias, wk = self.ps.w[self.name + "/bias"], self.ps.w[self.name + "/kernel"]
-        x_amax = ctx.absmax(src)                                         # (max |upsampled| = max |x|: the resize is a convex combination)
-        flops = 2.0 * N * 4 * H * W * 9 * self.cin * self.cout          # the reference's operation count (algorithmic) ...
-        executed = flops * 25.0 / 36.0                                   # ... of which 25 / 36 are issued
-        ukey = self.name + (":train" if keep_y else "")                   # (bench.py's executed-FLOP model: forward-only / training forward)
-        ctx.up2_used[ukey] = ctx.up2_used.get(ukey, 0) + 1
-        ctx.up2_skipped[ukey] = 11.0 / 36.0
-        wsp, wsn = ctx.ws(L.query("ladder_conv3x3_up2_edges_workspace_bytes", N, H, W, self.cin, self.cout))
-        if proj is not None:
-            proj.pt = proj.pl = 0
-            y = ctx.empty(N, 2 * H, 2 * W, self.cout) if keep_y else None
-            out = ctx.empty(N, 2 * H, 2 * W, proj.cout)
-            pw, pb = self.ps.w[proj.name + "/kernel"], self.ps.w[proj.name + "/bias"]
-            _timed(self._halo_kid(N, H, W, self.cin, 4 * self.cout, self.cout), flops, "ladder_conv3x3_up2_split_proj",
-                   (_p(src), _p(x_amax), _p(self._packed_filter(3)), _p(bias), _p(y), _p(pw), _p(pb), _p(out), proj.cout, N, H, W, self.cin, self.cout,
-                    L.ACT[self.act], ctx.ns, strided, ctx.stream), executed)
-            L.call("ladder_conv3x3_up2_edges", _p(src), _p(wk), _p(bias), _p(y), None, _p(pw), _p(pb), _p(out), proj.cout, N, H, W, self.cin, self.cout,
-                   L.ACT[self.act], strided, wsp, wsn, ctx.stream)
-            self.x_amax = x_amax if keep_y else None
-            # (keep_y without a resized tensor: the LOW-resolution tensor is what the backward pass gets -- virtual_up2_ok)
-            self.x, self.y = ((upsampled if upsampled is not None else src), y) if keep_y else (None, None)
-            self.x_is_up2 = bool(keep_y and upsampled is not None)       # x = the factor-2 upsample of a tensor: the filter gradient reads its even sub-grid
-            self.x_is_lo = bool(keep_y and upsampled is None)
-            proj.x, proj.y = (y, out) if keep_y else (None, None)
-            return out
-        y = ctx.empty(N, 2 * H, 2 * W, self.cout)
-        y_amax = ctx.new_amax() if ctx.ns == 4 else None
-        _timed(self._halo_kid(N, H, W, self.cin, 4 * self.cout, self.cout), flops, "ladder_conv3x3_up2_split",
-               (_p(src), _p(x_amax), _p(self._packed_filter(3)), _p(bias), _p(y), _p(y_amax), N, H, W, self.cin, self.cout, L.ACT[self.act], ctx.ns,
-                strided, ctx.stream), executed)
-        L.call("ladder_conv3x3_up2_edges", _p(src), _p(wk), _p(bias), _p(y), _p(y_amax), None, None, None, 0, N, H, W, self.cin, self.cout,
-               L.ACT[self.act], strided, wsp, wsn, ctx.stream)
-        ctx.set_amax(y, y_amax)
-        self.x_amax = x_amax if keep_y else None
-        self.x, self.y = ((upsampled if upsampled is not None else src), y) if keep_y else (None, None)
-        self.x_is_up2 = bool(keep_y and upsampled is not None)
-        self.x_is_lo = bool(keep_y and upsampled is None)
-        return y
-
-    def forward(self, x):
-        N, H, W, _ = x.shape
-        self.pt, Ho = arch.conv_out(H, self.k, self.stride, self.padding)
-        self.pl, Wo = arch.conv_out(W, self.k, self.stride, self.padding)
-        y = self.ctx.empty(N, Ho, Wo, self.cout)
-        self.x_amax = None
-        self.x_is_up2 = self.x_is_lo = False
-        if self._halo_ok(N, H, W, self.cin, self.cout):
-            self.x_amax = self.ctx.absmax(x)
-            y_amax = self.ctx.new_amax() if self.ctx.ns == 4 else None
-            args = (_p(x), _p(self.x_amax), _p(self._packed_filter(0)), _p(self.ps.w[self.name + "/bias"]), _p(y), _p(y_amax), N, H, W,
-                    self.cin, self.cout, L.ACT[self.act], self.ctx.ns, self.ctx.stream)
-            self.ctx.set_amax(y, y_amax)
-            _timed(self._halo_kid(N, H, W, self.cin, self.cout), 2.0 * N * H * W * 9 * self.cin * self.cout, "ladder_conv3x3_split", args)
-            self.x, self.y = x, y
-            return y
-        if self._as_dense(N * H * W):                   # 1x1 conv over a tiny map (decoder conv0 on the 1x1 map) = a batch-sized dense layer
-            L.call("ladder_dense_fwd_small" + self.ctx.sfx, _p(x), _p(self.ps.w[self.name + "/kernel"]), _p(self.ps.w[self.name + "/bias"]), _p(y), N * H * W,
-                   self.cin, self.cout, L.ACT[self.act], self.ctx.stream)
-            self.x, self.y = x, y
-            return y
-        geo = (N, H, W, self.cin, Ho, Wo, self.cout, self.k, self.k, self.stride, self.pt, self.pl)
-        if self._rgb(N, H, W) or self._rgb_fwd32(N, H, W):   # the image-side encoder conv (3 -> Cout channels, stride 2): csrc/convrgb.hip
-            sfx = "" if self.ctx.ns else "_f32"
-            if self.want_bn_sums and self.act is None:
-                wsp, wsn = self.ctx.ws(L.query("ladder_conv_rgb_s2_fwd_bnstats_workspace_bytes", N, H, W, self.cout))
-                self.bn_sums = self.ctx.empty(6 * self.cout)       # sum | sum of squares | min | max per channel
-                L.call("ladder_conv_rgb_s2_fwd_bnstats" + sfx, _p(x), _p(self.ps.w[self.name + "/kernel"]), _p(self.ps.w[self.name + "/bias"]), _p(y),
-                       N, H, W, self.cout, 0, _p(self.bn_sums), wsp, wsn, self.ctx.stream)
-            else:
-                L.call("ladder_conv_rgb_s2_fwd" + sfx, _p(x), _p(self.ps.w[self.name + "/kernel"]), _p(self.ps.w[self.name + "/bias"]), _p(y), N, H,
-                       W, self.cout, L.ACT[self.act], self.ctx.stream)
-            self.x, self.y = x, y
-            return y
-        if self.ctx.ns and L.query("ladder_conv2d_fwd_split_eligible", *geo):
-            self.x_amax = self.ctx.absmax(x)
-            nb = L.query("ladder_conv2d_fwd_split_workspace_bytes", *geo)
-            wsp, wsn = self.ctx.ws(nb)
-            if self.want_bn_sums and self.act is None and not nb:
-                snb = L.query("ladder_conv2d_fwd_split_bnstats_workspace_bytes", *geo)
-                if snb:                                  # the epilogue also emits the batch-norm statistics of y (no second pass over it)
-                    swp, swn = self.ctx.ws(snb)
-                    self.bn_sums = self.ctx.empty(6 * self.cout)
-                    L.call("ladder_conv2d_fwd_split_bnstats", _p(self.ctx.planes(x, self._ps(Ho, Wo))), _p(self.x_amax), _p(self._packed_filter(0)),
-                           _p(self.ps.w[self.name + "/bias"]), _p(y), *geo, 0, self.ctx.ns, _p(self.bn_sums), swp, swn, self.ctx.stream)
-                    self.x, self.y = x, y
-                    return y
-            args = (_p(self.ctx.planes(x, self._ps(Ho, Wo))), _p(self.x_amax), _p(self._packed_filter(0)), _p(self.ps.w[self.name + "/bias"]), _p(y)) + geo + (
-                L.ACT[self.act], self.ctx.ns, wsp, wsn, self.ctx.stream)
-            if nb:                                       # split-K launch: two kernels, not attributed by the profiler
-                L.call("ladder_conv2d_fwd_split", *args)
-            else:
-                _timed(128120 + self.ctx.ns, 2.0 * N * Ho * Wo * self.k * self.k * self.cin * self.cout, "ladder_conv2d_fwd_split", args)
-            self.x, self.y = x, y
-            return y
-        if self.ctx.ns == 0 and self.want_bn_sums and self.act is None:
-            snb = L.query("ladder_conv2d_fwd_bnstats_workspace_bytes", *geo)
-            if snb:                                      # strict fp32: the epilogue also emits the batch-norm statistics of y (no second pass over it)
-                swp, swn = self.ctx.ws(snb)
-                self.bn_sums = self.ctx.empty(6 * self.cout)
-                L.call("ladder_conv2d_fwd_bnstats", _p(x), _p(self.ps.w[self.name + "/kernel"]), _p(self.ps.w[self.name + "/bias"]), _p(y), *geo, 0,
-                       _p(self.bn_sums), swp, swn, self.ctx.stream)
-                self.x, self.y = x, y
-                return y
-        if (self.ctx.ns == 0 and self.k == 3 and self.stride == 2 and self.pt == 0 and self.pl == 0 and os.environ.get("LADDER_DISABLE_HALO") != "1"
-                and L.query("ladder_conv3x3_s2_fwd_f32_eligible", N, H, W, self.cin, Ho, Wo, self.cout)):
-            # strict fp32, 3x3 / stride 2 over an even map (encoder conv2d_2 / conv2d_3): a stride-1 correlation over the four pixel-parity classes
-            # of x on the halo kernels (x staged once per slab for all taps; csrc/convf32s.hip): 185 / 115 us against 202 / 127 on the gather kernel.
-            # (Behind the statistics-epilogue branch above: conv2d_1 measures 344 us + a statistics pass here against 356 us with them.)
-            args = (_p(x), _p(self._packed_filter(5)), _p(self.ps.w[self.name + "/bias"]), _p(y), N, H, W, self.cin, Ho, Wo, self.cout,
-                    L.ACT[self.act], self.ctx.stream)
-            _timed(self._halo_kid(N, Ho, Wo, 4 * self.cin, self.cout), 2.0 * N * Ho * Wo * 9 * self.cin * self.cout, "ladder_conv3x3_s2_fwd_f32", args)
-            self.x, self.y = x, y
-            return y
-        _igemm(self.ctx, "ladder_conv2d_fwd", N * Ho * Wo, self.cin, self.cout, self.k * self.k * self.cin,
-               _p(x), _p(self.ps.w[self.name + "/kernel"]), _p(self.ps.w[self.name + "/bias"]), _p(y),
-               N, H, W, self.cin, Ho, Wo, self.cout, self.k, self.k, self.stride, self.pt, self.pl, L.ACT[self.act],
-               conv=(N, H, W, self.cin, Ho, Wo, self.cout, self.k, self.k, self.stride, 1, self.pt, self.pl))
-        self.x, self.y = x, y
-        return y
-
-    def up2t_ok(self, N, H, W):
-        """The gradient with respect to the LOW-resolution tensor [N, H, W, cin] behind a factor-2 resize in front of this layer can come from
-        ONE launch (ladder_conv3x3_up2_bwd_data_split) + border strips, instead of backward-data on the upsampled map + the resize transpose."""
-        if self.ctx.ns == 0 and os.environ.get("LADDER_DISABLE_HALO") == "1":
-            return False
-        if self.proj_ok(N, H, W) and (self.x is None or self.x_is_lo):
-            # (asked before the forward: the geometry decides; asked in backward: only when the forward really kept the LOW-resolution tensor --
-            # a materialised upsample goes through the tap-folded eligibility below, ADVICE r5)
-            return True
-        if self.ctx.ns == 0 and H * W < UP2T_MIN_PIXELS:
-            # policy (measured, profiles/r05_small_maps.txt): on an 8x8 low-resolution map the four exact border lines cost more than the
-            # 11 / 36 of the products the fused launch saves (conv2d_4: 461 + 221 us against 595 + 26 for the direct pair)
-            return False
-        return bool(self.ctx.up2 >= 2 and self.ctx.ns in (0, 2, 4) and self.k == 3 and self.stride == 1 and self.padding == "same"
-                    and L.query("ladder_conv3x3_up2_bwd_data_split_eligible", N, H, W, self.cout, self.cin, self.ctx.ns)
-                    and (self.ctx.ns == 0 or all(L.query("ladder_conv2d_bwd_data_split_eligible", *g, 0) for g in (
-                        (N, 2, 2 * W, self.cin, 3, 2 * W, self.cout, 3, 3, 1, 1, 1), (N, 3, 2 * W, self.cin, 4, 2 * W, self.cout, 3, 3, 1, 2, 1),
-                        (N, 2 * H, 2, self.cin, 2 * H, 3, self.cout, 3, 3, 1, 1, 1), (N, 2 * H, 3, self.cin, 2 * H, 4, self.cout, 3, 3, 1, 1, 2)))))
-
-    def lowres_gate_ok(self, N, H, W):
-        """_dx_lowres can apply the activation backward of the layer below (its `gate`) in the same launches (strict fp32, 8x32-pixel tiling).
-        OFF by default (LADDER_ENABLE_LOWRES_GATE=1 turns it on): measured in round 5, the 64 gate loads per lane in the epilogue of conv2d_6's fused
-        backward-data cost 72 us (1 631 -> 1 703 us) -- the 67 us ladder_act_bwd pass they replace (profiles/r05_f32_percall.md was taken with it on)."""
-        if self.x_is_lo and self.proj_ok(N, H, W, self.lo_factor):
-            # (projected form: the gate would ride on the dense kernel's epilogue -- measured 772 against 655 us on conv2d_6's backward-data GEMM, more than
-            # the ~85 us activation pass it replaces: opt-in like the tap-folded form's)
-            return os.environ.get("LADDER_ENABLE_LOWRES_GATE") == "1"
-        return bool(self.ctx.ns == 0 and os.environ.get("LADDER_ENABLE_LOWRES_GATE") == "1"
-                    and L.query("ladder_conv3x3_up2_bwd_data_gated_f32_eligible", N, H, W, self.cout, self.cin))
 
     def _dx_lowres(self, dy, dy_amax, gate=None):
         """d loss / d x_lo for y = conv(resize2x(x_lo)): the composite transpose is a zero-padded 5x5 / stride-2 correlation over dy (one launch of
@@ -864,25 +788,30 @@ class Conv2D:
 
     def backward(self, dy, need_dx=True, wgrad=True, act_done=False, gate_prev=None, lowres_dx=False, lowres_gate=None, proj_grad=None):
         """`act_done`: dy already carries this layer's activation derivative (fused into the consumer's epilogue).
-        `proj_grad` = (dyp, proj) instead of dy: see _backward_proj / bwd_proj_ok.
+        `proj_grad` = (dyp, proj) instead of dy: see _backward_proj.
         `gate_prev`: activation name of the layer that produced this conv's input x: its derivative act'(x) is fused into
         the backward-data epilogue, so that layer must then be called with act_done=True.
         `lowres_dx`: x is the factor-2 upsample of a tensor the caller wants the gradient of: return d / d (that tensor) (see _dx_lowres)."""
-        x, y = self.x, self.y
+        try:
+            return self._backward(self.kept, dy, need_dx, wgrad, act_done, gate_prev, lowres_dx, lowres_gate, proj_grad)
+        finally:
+            self.kept = None          # the one place the record of the forward is dropped
+
+    def _backward(self, k, dy, need_dx, wgrad, act_done, gate_prev, lowres_dx, lowres_gate, proj_grad):
+        x, y, x_amax, pt, pl = k.x, k.y, k.x_amax, k.pt, k.pl
         N, H, W, _ = x.shape
-        if self.x_is_lo:                                  # x is the low-resolution tensor: the layer's input is its (never materialised) upsample
-            H, W = self.lo_factor * H, self.lo_factor * W
-            if not lowres_dx and need_dx:
-                raise RuntimeError("%s: only the low-resolution gradient exists for a virtual upsample" % self.name)
+        lo = k.x_kind == "lowres"                         # x is the low-resolution tensor: the layer's input is its (never materialised) upsample
+        if lo:
+            H, W = k.factor * H, k.factor * W
         if proj_grad is not None:
-            if not (wgrad and self.bwd_proj_ok(proj_grad[1])):
+            if not (wgrad and lo and k.form == "projected" and k.factor == 2):
                 raise RuntimeError("%s: the projection-gradient form of the backward combination does not apply" % self.name)
             return self._backward_proj(None, need_dx, wgrad, lowres_gate, proj_grad)
         _, Ho, Wo, _ = y.shape
         st = self.ctx.stream
         if self.act is not None and not act_done:
             L.call("ladder_act_bwd", _p(dy), _p(y), _p(dy), dy.numel(), L.ACT[self.act], st)
-        if self.x_is_lo and self.proj_ok(N, H // self.lo_factor, W // self.lo_factor, self.lo_factor):
+        if lo and k.form == "projected":
             return self._backward_proj(dy, need_dx, wgrad, lowres_gate)
         if (wgrad and self.k == 1 and self.stride == 1 and L.query("ladder_conv1x1_smallcout_eligible", N * H * W, self.cin, self.cout)):
             # 1x1 to <= 4 channels over a wide map (the CelebA output conv): dx, dW and db from ONE pass over x
@@ -895,7 +824,6 @@ class Conv2D:
                    self.cout, L.ACT[gate_prev] if gate_prev else 0, wsp, wsn, _p(dx_amax), H * W, st)
             if dx is not None:
                 self.ctx.set_amax(dx, dx_amax)
-            self.x = self.y = None
             return dx
         if self._as_dense(N * H * W):
             M = N * H * W
@@ -907,16 +835,15 @@ class Conv2D:
                 dx = self.ctx.empty(N, H, W, self.cin)
                 L.call("ladder_dense_bwd_data_small" + self.ctx.sfx, _p(dy), _p(self.ps.w[self.name + "/kernel"]), _p(dx), M, self.cin, self.cout,
                        _p(x) if gate_prev else None, L.ACT[gate_prev] if gate_prev else 0, st)
-            self.x = self.y = None
             return dx
-        if wgrad and self._rgb(N, H, W):
+        if wgrad and self._rgb(N, H, W, pt, pl):
             xa, da = self.ctx.absmax(x), self.ctx.absmax(dy)
             with self.ctx.side_or_main(x, dy, xa, da):
                 wsp, wsn = self.ctx.ws(L.query("ladder_conv_rgb_s2_bwd_filter_workspace_bytes", N, H, W, self.cout))
                 L.call("ladder_conv_rgb_s2_bwd_filter", _p(x), _p(xa), _p(dy), _p(da), _p(self.ps.g[self.name + "/kernel"]),
                        _p(self.ps.g[self.name + "/bias"]) if self.bias_grad else None, N, H, W, self.cout, wsp, wsn, self.ctx.stream)
             wgrad = False
-        if wgrad and self._rgb_fwd32(N, H, W):            # strict fp32: the fp32 filter-gradient kernel of the same layer
+        if wgrad and self._rgb_fwd32(N, H, W, pt, pl):            # strict fp32: the fp32 filter-gradient kernel of the same layer
             with self.ctx.side_or_main(x, dy):
                 wsp, wsn = self.ctx.ws(L.query("ladder_conv_rgb_s2_bwd_filter_workspace_bytes", N, H, W, self.cout))
                 L.call("ladder_conv_rgb_s2_bwd_filter_f32", _p(x), _p(dy), _p(self.ps.g[self.name + "/kernel"]),
@@ -925,35 +852,35 @@ class Conv2D:
         dy_amax = None
         split_w = bool(wgrad and self._split_ok(N, H, W, self.cin, self.cout)
                        and L.query("ladder_conv3x3_wgrad_split_eligible", N, H, W, self.cin, self.cout, self.ctx.ns))
-        if split_w and self.ctx.ns == 4 and getattr(self, "x_amax", None) is None:
-            self.x_amax = self.ctx.absmax(x)
+        if split_w and self.ctx.ns == 4 and x_amax is None:
+            x_amax = self.ctx.absmax(x)
         split_d = bool(need_dx and not gate_prev and self._halo_ok(N, Ho, Wo, self.cout, self.cin))
         if split_w or split_d:
             dy_amax = self.ctx.absmax(dy)               # one pass serves the filter gradient and the backward-data call
         if split_w:
             # (on the side stream: the filter gradient is MFMA-bound and only the optimiser step needs it; the backward-data call below
             # and the HBM-bound resize / norm backward kernels of the layers underneath run beside it)
-            with self.ctx.side_or_main(x, dy, self.x_amax, dy_amax):
+            with self.ctx.side_or_main(x, dy, x_amax, dy_amax):
                 wsp, wsn = self.ctx.ws(L.query("ladder_conv3x3_wgrad_split_workspace_bytes", N, H, W, self.cin, self.cout))
-                args = (_p(x), _p(self.x_amax), _p(dy), _p(dy_amax), _p(self.ps.g[self.name + "/kernel"]),
+                args = (_p(x), _p(x_amax), _p(dy), _p(dy_amax), _p(self.ps.g[self.name + "/kernel"]),
                         _p(self.ps.g[self.name + "/bias"]) if self.bias_grad else None, N, H, W, self.cin, self.cout, self.ctx.ns, wsp, wsn,
                         self.ctx.stream)
                 _timed(9120 + self.ctx.ns, 2.0 * N * H * W * 9 * self.cin * self.cout, "ladder_conv3x3_wgrad_split", args)
         elif wgrad and self.ctx.ns and L.query("ladder_conv2d_bwd_filter_split_eligible", N, H, W, self.cin, Ho, Wo, self.cout, self.k,
-                                               self.k, self.stride, self.pt, self.pl):
+                                               self.k, self.stride, pt, pl):
             if self.ctx.ns == 4:
-                if getattr(self, "x_amax", None) is None:
-                    self.x_amax = self.ctx.absmax(x)
+                if x_amax is None:
+                    x_amax = self.ctx.absmax(x)
                 dy_amax = self.ctx.absmax(dy)
             ps_ = self._ps(Ho, Wo)
             xpl, dpl = self.ctx.planes(x, ps_), self.ctx.planes(dy, ps_)          # (split on the main stream: backward-data reads dy's planes too)
-            with self.ctx.side_or_main(x, dy, xpl, dpl, self.x_amax, dy_amax):
+            with self.ctx.side_or_main(x, dy, xpl, dpl, x_amax, dy_amax):
                 wsp, wsn = self.ctx.ws(L.query("ladder_conv2d_bwd_filter_split_workspace_bytes", N, H, W, self.cin, Ho, Wo, self.cout, self.k,
                                                self.k))
-                L.call("ladder_conv2d_bwd_filter_split", _p(xpl), _p(self.x_amax), _p(dpl), _p(dy_amax), _p(self.ps.g[self.name + "/kernel"]),
+                L.call("ladder_conv2d_bwd_filter_split", _p(xpl), _p(x_amax), _p(dpl), _p(dy_amax), _p(self.ps.g[self.name + "/kernel"]),
                        _p(self.ps.g[self.name + "/bias"]) if self.bias_grad else None, N, H, W, self.cin, Ho, Wo, self.cout, self.k, self.k,
-                       self.stride, self.pt, self.pl, self.ctx.ns, wsp, wsn, self.ctx.stream)
-        elif (wgrad and self.ctx.ns == 0 and (self.x_is_up2 or self.x_is_lo) and self.ctx.up2 >= 2 and (H // 2) * (W // 2) >= UP2W_MIN_PIXELS
+                       self.stride, pt, pl, self.ctx.ns, wsp, wsn, self.ctx.stream)
+        elif (wgrad and self.ctx.ns == 0 and k.x_kind != "input" and self.ctx.up2 >= 2 and (H // 2) * (W // 2) >= UP2W_MIN_PIXELS
               and L.query("ladder_conv3x3_up2_wgrad_eligible", N, H // 2, W // 2, self.cin, self.cout)):
             # strict fp32, x = resize2x(x_lo): 25 instead of 36 tap tiles, read from the even sub-grid of the kept upsample (csrc/convf32.hip)
             wsp, wsn = self.ctx.ws(L.query("ladder_conv3x3_up2_wgrad_workspace_bytes", N, H // 2, W // 2, self.cin, self.cout))
@@ -961,17 +888,18 @@ class Conv2D:
             self.ctx.up2_used[self.name + ":wgrad"] = self.ctx.up2_used.get(self.name + ":wgrad", 0) + 1
             self.ctx.up2_skipped[self.name + ":wgrad"] = 11.0 / 36.0
             _timed(9120, fl, "ladder_conv3x3_up2_wgrad",
-                   (_p(x), 0 if self.x_is_lo else 1, _p(dy), _p(self.ps.g[self.name + "/kernel"]), _p(self.ps.g[self.name + "/bias"]) if self.bias_grad else None, N, H // 2, W // 2,
+                   (_p(x), 0 if lo else 1, _p(dy), _p(self.ps.g[self.name + "/kernel"]), _p(self.ps.g[self.name + "/bias"]) if self.bias_grad else None, N, H // 2, W // 2,
                     self.cin, self.cout, wsp, wsn, st), fl * 25.0 / 36.0)
         elif wgrad:
-            if self.x_is_lo:        # (x is [N, H/2, W/2, cin]: the generic kernel would read 4x past it -- the forward's decision must hold here)
-                raise RuntimeError("%s: virtual upsample without the low-resolution filter gradient" % self.name)
+            # (a low-resolution x is [N, H/2, W/2, cin]: the generic kernel would read 4x past it.  plan_decoder plans a virtual upsample only where
+            # the branch above takes the filter gradient)
+            assert not lo, "%s: virtual upsample without the low-resolution filter gradient" % self.name
             nb = L.query("ladder_conv2d_bwd_filter_workspace_bytes", N, H, W, self.cin, Ho, Wo, self.cout, self.k, self.k)
             wsp, wsn = self.ctx.ws(nb)
             wargs = (_p(x), _p(dy), _p(self.ps.g[self.name + "/kernel"]), _p(self.ps.g[self.name + "/bias"]) if self.bias_grad else None,
-                     N, H, W, self.cin, Ho, Wo, self.cout, self.k, self.k, self.stride, self.pt, self.pl, wsp, wsn, st)
+                     N, H, W, self.cin, Ho, Wo, self.cout, self.k, self.k, self.stride, pt, pl, wsp, wsn, st)
             if PROF is not None and L.query("ladder_conv2d_bwd_filter_kernel_id", N, H, W, self.cin, Ho, Wo, self.cout, self.k, self.k,
-                                            self.stride, self.pt, self.pl) == 9128:
+                                            self.stride, pt, pl) == 9128:
                 s_, e_ = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 s_.record()
                 L.call("ladder_conv2d_bwd_filter", *wargs)         # (+ its fixed-order split reduction: counted with the kernel)
@@ -991,9 +919,9 @@ class Conv2D:
                     self.ctx.ns, st)
             self.ctx.set_amax(dx, dx_amax)
             _timed(self._halo_kid(N, H, W, self.cout, self.cin), 2.0 * N * H * W * 9 * self.cin * self.cout, "ladder_conv3x3_split", args)
-        elif (need_dx and self.ctx.ns in (0, 4) and not gate_prev and self.stride == 2 and not (self.ctx.ns == 0 and os.environ.get("LADDER_DISABLE_HALO") == "1")
+        elif (need_dx and self.ctx.ns in (0, 4) and not gate_prev and self.stride == 2 and not (self.ctx.ns == 0 and halo_disabled())
               and (L.query("ladder_conv3x3_s2_bwd_data_split_eligible", N, H, W, self.cin, Ho, Wo, self.cout, self.k, self.k, self.stride,
-                           self.pt, self.pl) or (self.ctx.ns == 0 and self.k == 3 and self.pt == 0 and self.pl == 0 and
+                           pt, pl) or (self.ctx.ns == 0 and self.k == 3 and pt == 0 and pl == 0 and
                                                  L.query("ladder_conv3x3_s2_bwd_data_f32_eligible", N, H, W, self.cin, Ho, Wo, self.cout)))):
             # 3x3 / stride 2 over a map whose gradient is halo-kernel sized (enc.conv1): the four output-parity classes in ONE launch
             if dy_amax is None:
@@ -1004,8 +932,8 @@ class Conv2D:
             self.ctx.set_amax(dx, dx_amax)
             _timed(self._halo_kid(N, Ho, Wo, self.cout, 4 * self.cin, self.cin), 2.0 * N * Ho * Wo * 9 * self.cin * self.cout, "ladder_conv3x3_s2_bwd_data_split", args)
         elif need_dx and self.ctx.ns and L.query("ladder_conv2d_bwd_data_split_eligible", N, H, W, self.cin, Ho, Wo, self.cout, self.k,
-                                                 self.k, self.stride, self.pt, self.pl, 1 if gate_prev else 0):
-            geo = (N, H, W, self.cin, Ho, Wo, self.cout, self.k, self.k, self.stride, self.pt, self.pl)
+                                                 self.k, self.stride, pt, pl, 1 if gate_prev else 0):
+            geo = (N, H, W, self.cin, Ho, Wo, self.cout, self.k, self.k, self.stride, pt, pl)
             if dy_amax is None:
                 dy_amax = self.ctx.absmax(dy)
             wsp, wsn = self.ctx.ws(L.query("ladder_conv2d_bwd_data_split_workspace_bytes", *geo))
@@ -1022,12 +950,141 @@ class Conv2D:
             dx = self.ctx.empty(N, H, W, self.cin)
             _igemm(self.ctx, "ladder_conv2d_bwd_data", N * H * W, self.cout, self.cin, self.k * self.k * self.cout,
                    _p(dy), _p(wT), _p(dx), N, H, W, self.cin, Ho, Wo, self.cout, self.k, self.k,
-                   self.stride, self.pt, self.pl, _p(x) if gate_prev else None, L.ACT[gate_prev] if gate_prev else 0,
+                   self.stride, pt, pl, _p(x) if gate_prev else None, L.ACT[gate_prev] if gate_prev else 0,
                    # a strided backward-data call is several parity-class launches: not attributed by the profiler
-                   conv=(N, Ho, Wo, self.cout, H, W, self.cin, self.k, self.k, 1, 1, self.k - 1 - self.pt, self.k - 1 - self.pl)
+                   conv=(N, Ho, Wo, self.cout, H, W, self.cin, self.k, self.k, 1, 1, self.k - 1 - pt, self.k - 1 - pl)
                    if self.stride == 1 else "skip")
-        self.x = self.y = None
         return dx
+
+
+# How one block of the CelebA decoder (resize in front -> 3x3 conv -> [instance norm] -> resize behind) runs, forward and backward:
+#   resize      the resize in FRONT of the conv: None (none, or the identity) | "materialise" (a resize pass writes the resized tensor, the conv reads it) |
+#               "keep_both" (training: the conv reads the low-resolution tensor, the resized one is written beside it for the backward pass) |
+#               "virtual" (training: forward, backward-data and filter gradient all run from the low-resolution tensor, the resized one never exists) |
+#               "fold_forward_only" (forward-only run: the conv reads the low-resolution tensor, nothing is kept);  factor: 2 or 4 (0: neither)
+#   form        of the conv (Kept.form);  one_launch: projected form as GEMM + combination in one launch
+#   proj        the 1x1 RGB conv behind the last 3x3 conv: None (a layer call of its own after the loop) | "rides" (on this conv's epilogue) |
+#               "follows" (an upsample-fused conv whose epilogue cannot take it: the conv, then the 1x1 conv)
+#   norm_out    what this block's instance norm writes: None (no norm) | "lowres" (its plain output) | "resized" (only the resize of it, by the resize
+#               behind the block) | "both";  behind: `resize` of the next block (last block: None, or "materialise")
+#   lowres_dx   backward: the conv's backward-data returns the gradient of the low-resolution tensor (the transpose of the resize in front is in it) ...
+#   lgate       ... and applies the activation derivative of the conv below;  pre_gated: dy arrives with this conv's derivative applied that way
+#   rs_bwd      the transpose of the resize behind runs as a launch of its own;  gated: ... and applies this conv's activation derivative
+#   fuse_last   last block: the 1x1 conv's backward-data applies this conv's activation derivative;  proj_grad: ... or rather the backward combination of
+#               the projected form is formed straight from the 1x1 conv's gradient (ladder_up2proj_bwd_combine_proj: dy of this layer never exists)
+PairPlan = namedtuple("PairPlan", "resize factor form one_launch proj norm_out behind lowres_dx lgate pre_gated gated rs_bwd fuse_last proj_grad")
+
+
+def plan_decoder(cache, ctx, up0, blocks, conv_out, shape):
+    """One PairPlan per block of `blocks` [(conv, style dense, norm, resize behind)] for an input map `shape` = (N, H, W) in front of the resize `up0`,
+    under ctx.keep_activations.  Every eligibility query, config level and switch that routes a resize -> conv pair is consulted here and only here;
+    CelebADecoder.forward and .backward follow the list.  Plans are cached in `cache` by everything that enters them."""
+    keep, ns, up2 = ctx.keep_activations, ctx.ns, ctx.up2
+    halo_sw, gate_sw = halo_disabled(), switch("LADDER_ENABLE_LOWRES_GATE") == "1"
+    key = (tuple(shape), keep, ns, up2, ctx.fuse_fwd, ctx.fuse_bwd_proj, halo_sw, gate_sw)
+    if key in cache:
+        return cache[key]
+    N = shape[0]
+    halo_off = ns == 0 and halo_sw          # (test switch: the round-1 generic fp32 gather kernels everywhere)
+
+    def c3(c):
+        return c.k == 3 and c.stride == 1 and c.padding == "same"
+
+    def factor(rs, H, W):                   # integer factor (2 or 4) of resize `rs` applied to an H x W map, 0 when it is neither
+        return next((f for f in (2, 4) if rs is not None and (rs.oh, rs.ow) == (f * H, f * W)), 0)
+
+    def proj_ok(c, H, W, f):
+        # projected form (strict fp32, config `upsample_fused_convs` >= 4; factor 2 or 4).  The nine planes Z / D are a transient [N H W, 9 cout] fp32
+        # tensor: beyond PROJ_MAX_BYTES the pair takes the forms that allocate none
+        return bool(ns == 0 and up2 >= 4 and c3(c) and not halo_sw and 36 * N * H * W * c.cout <= PROJ_MAX_BYTES
+                    and L.query("ladder_upfproj_eligible", f, N, H, W, c.cin, c.cout))
+
+    def fold_ok(c, H, W, f):
+        # the conv can take the LOW-resolution tensor [N, H, W, cin] in its forward: projected (factor 2 or 4), else tap-folded (factor 2)
+        if proj_ok(c, H, W, f):
+            return True
+        return bool(f == 2 and not halo_off and up2 and ns in (0, 2, 4) and c3(c) and L.query("ladder_conv3x3_up2_split_eligible", N, H, W, c.cin, c.cout, ns))
+
+    def tap_bwd_ok(c, H, W):
+        # the gradient of the low-resolution tensor behind a MATERIALISED factor-2 resize from ONE launch (ladder_conv3x3_up2_bwd_data_split) + border strips
+        if halo_off:
+            return False
+        if ns == 0 and H * W < UP2T_MIN_PIXELS:
+            # policy (measured, profiles/r05_small_maps.txt): on an 8x8 low-resolution map the four exact border lines cost more than the
+            # 11 / 36 of the products the fused launch saves (conv2d_4: 461 + 221 us against 595 + 26 for the direct pair)
+            return False
+        return bool(up2 >= 2 and ns in (0, 2, 4) and c3(c) and L.query("ladder_conv3x3_up2_bwd_data_split_eligible", N, H, W, c.cout, c.cin, ns)
+                    and (ns == 0 or all(L.query("ladder_conv2d_bwd_data_split_eligible", *g, 0) for g in (
+                        (N, 2, 2 * W, c.cin, 3, 2 * W, c.cout, 3, 3, 1, 1, 1), (N, 3, 2 * W, c.cin, 4, 2 * W, c.cout, 3, 3, 1, 2, 1),
+                        (N, 2 * H, 2, c.cin, 2 * H, 3, c.cout, 3, 3, 1, 1, 1), (N, 2 * H, 3, c.cin, 2 * H, 4, c.cout, 3, 3, 1, 1, 2)))))
+
+    def virtual_ok(c, H, W, f):
+        # a training forward may skip materialising the resize altogether: strict fp32, and forward, backward-data AND filter gradient of the conv all
+        # run from the low-resolution tensor (projected form; or, factor 2, the tap-folded kernels of csrc/convf32.hip)
+        if proj_ok(c, H, W, f):
+            return True
+        return bool(f == 2 and ns == 0 and up2 >= 3 and fold_ok(c, H, W, 2) and tap_bwd_ok(c, H, W) and H * W >= UP2W_MIN_PIXELS
+                    and L.query("ladder_conv3x3_up2_wgrad_eligible", N, H, W, c.cin, c.cout))
+
+    # forward: the resize in front of each block and the form of its conv
+    n, fwd, front, (h, w) = len(blocks), [], up0, shape[1:3]
+    for i, (conv, _, norm, rs) in enumerate(blocks):
+        f, resize = factor(front, h, w), None
+        if front is not None and (front.oh, front.ow) != (h, w):
+            if not (f and fold_ok(conv, h, w, f)):
+                resize = "materialise"
+            elif not keep:
+                resize = "fold_forward_only"
+            elif virtual_ok(conv, h, w, f):
+                resize = "virtual"
+            elif i and up2 >= 2 and f == 2 and (blocks[i - 1][2] is None or blocks[i - 1][0].cout % 4 == 0):
+                resize = "keep_both"        # (behind a norm: written by ladder_in_style_fwd_resize2x_keep; the 1x1 -> 2x2 resize in front of conv2d_1 never)
+            else:
+                resize = "materialise"
+        lo_hw, (h, w) = (h, w), ((front.oh, front.ow) if front is not None else (h, w))
+        # the last 3x3 conv feeds the 1x1 output conv directly (its resize is the identity)
+        last = i == n - 1 and norm is None and (rs is None or (rs.oh, rs.ow) == (h, w))
+        if resize in (None, "materialise"):
+            form, one_launch = "plain", False
+            proj = "rides" if (last and conv.cout <= 128 and conv._is_projection(conv_out) and conv._halo_ok(N, h, w, conv.cin, conv.cout)) else None
+        else:
+            form = "projected" if proj_ok(conv, lo_hw[0], lo_hw[1], f) else "tapfold"
+            one_launch = bool(form == "projected" and f == 2 and ctx.fuse_fwd and L.query(
+                "ladder_up2proj_fused_eligible" if ctx.fuse_fwd >= 2 else "ladder_up2proj_fused_preferred", N, lo_hw[0], lo_hw[1], conv.cin, conv.cout))
+            # (the fused 1x1 epilogues hold one pixel's 128 channels in a half-wave, ADVICE r5)
+            proj = None if not (last and f == 2) else "rides" if (conv.cout == 128 and conv._is_projection(conv_out)) else "follows"
+        fwd.append((resize, f, form, one_launch, proj, lo_hw, (h, w), last))
+        front = rs
+    # the tail of each block (norm, resize behind) and the backward pass, from the last block down
+    plan, above_lowres, above_lgate = [None] * n, False, False
+    for i in range(n - 1, -1, -1):
+        conv, _, norm, rs = blocks[i]
+        resize, f, form, one_launch, proj, (lh, lw), (ho, wo), last = fwd[i]        # (lh x lw: the map in front of the resize; ho x wo: the conv's)
+        if i + 1 < n:
+            behind, fb = fwd[i + 1][0], fwd[i + 1][1]
+        else:
+            behind, fb = ("materialise" if rs is not None and (rs.oh, rs.ow) != (ho, wo) else None), factor(rs, ho, wo)
+        norm_out = None if norm is None else "both" if behind == "keep_both" else \
+            "resized" if (behind == "materialise" and fb == 2 and conv.cout % 4 == 0) else "lowres"
+        # a kept upsample: the low-resolution backward-data only for the last block or at `upsample_fused_convs` >= 3
+        lowres_dx = bool(keep and (resize == "virtual" or (
+            resize in ("materialise", "keep_both") and i and f == 2 and (i == n - 1 or up2 >= 3) and tap_bwd_ok(conv, lh, lw))))
+        below = blocks[i - 1] if i else None
+        # OFF by default (LADDER_ENABLE_LOWRES_GATE=1): measured in round 5, the gate loads in the epilogue of conv2d_6's fused backward-data cost 72 us
+        # (1 631 -> 1 703 us), on the projected form's dense kernel 772 against 655 us -- more than the 67 / ~85 us ladder_act_bwd pass they replace
+        lgate = bool(lowres_dx and below is not None and below[2] is None and below[0].act is not None and gate_sw and (
+            (resize == "virtual" and form == "projected")
+            or (ns == 0 and L.query("ladder_conv3x3_up2_bwd_data_gated_f32_eligible", N, lh, lw, conv.cout, conv.cin))))
+        fuse_last = bool(last and conv.act is not None)
+        proj_grad = bool(keep and fuse_last and ctx.fuse_bwd_proj and resize == "virtual" and form == "projected" and f == 2
+                         and conv.act in ("leaky_relu", "relu") and conv_out.k == 1 and conv_out.stride == 1 and conv_out.act is None
+                         and conv_out.cin == conv.cout and L.query("ladder_up2proj_bwd_combine_proj_eligible", N, lh, lw, conv.cout, conv_out.cout))
+        rs_bwd = bool(behind in ("materialise", "keep_both") and not above_lowres)
+        gated = bool(rs_bwd and norm is None and conv.act is not None and not fuse_last and fb == 2)
+        plan[i] = PairPlan(resize, f, form, one_launch, proj, norm_out, behind, lowres_dx, lgate, above_lgate, gated, rs_bwd, fuse_last, proj_grad)
+        above_lowres, above_lgate = lowres_dx, lgate
+    cache[key] = plan
+    return plan
 
 
 class Dense:
@@ -1191,29 +1248,26 @@ class InstanceNormStyleAct:
         return y
 
     def forward_resized(self, x, style, rs, keep_lowres=False):
-        """forward() followed by the factor-2 resize `rs` in ONE pass over x (ladder_in_style_fwd_resize2x): the normalised tensor is
-        never written -- unless `keep_lowres` (then it is left in self.y_lo: the input of an upsample-fused convolution behind the resize);
-        returns None when the pair is not eligible.  The backward passes are those of the two separate layers."""
+        """forward() followed by the factor-2 resize `rs` in ONE pass over x (ladder_in_style_fwd_resize2x; C a multiple of 4): the normalised
+        tensor is never written -- unless `keep_lowres` (the input of an upsample-fused convolution behind the resize).  Returns (resized tensor,
+        normalised tensor or None).  The backward passes are those of the two separate layers."""
         N, H, W, C = x.shape
-        self.y_lo = None
-        if not (C % 4 == 0 and (rs.oh, rs.ow) == (2 * H, 2 * W)):
-            return None
-        up = self.ctx.empty(N, 2 * H, 2 * W, C)
+        up, y_lo = self.ctx.empty(N, 2 * H, 2 * W, C), None
         self.mean_rstd = self.ctx.empty(N, 2 * C)
         wsp, wsn = self.ctx.ws(L.query("ladder_in_style_workspace_bytes", N, H * W, C))
         up_amax = self.ctx.new_amax() if self.ctx.ns == 4 else None
         if keep_lowres:
-            self.y_lo = self.ctx.empty(N, H, W, C)
-            L.call("ladder_in_style_fwd_resize2x_keep", _p(x), _p(style), _p(up), _p(self.y_lo), _p(self.mean_rstd), N, H, W, C, IN_EPS,
+            y_lo = self.ctx.empty(N, H, W, C)
+            L.call("ladder_in_style_fwd_resize2x_keep", _p(x), _p(style), _p(up), _p(y_lo), _p(self.mean_rstd), N, H, W, C, IN_EPS,
                    L.ACT[self.act], wsp, wsn, _p(up_amax), self.ctx.stream)
-            self.ctx.set_amax(self.y_lo, up_amax)              # max |y| = max |up| (the record receives max |y|)
+            self.ctx.set_amax(y_lo, up_amax)                   # max |y| = max |up| (the record receives max |y|)
         else:
             L.call("ladder_in_style_fwd_resize2x", _p(x), _p(style), _p(up), _p(self.mean_rstd), N, H, W, C, IN_EPS, L.ACT[self.act], wsp, wsn,
                    _p(up_amax), self.ctx.stream)
         self.ctx.set_amax(up, up_amax)
         self.x, self.style = x, style
-        rs.in_shape = (N, H, W, C)
-        return up
+        rs.in_shape = (N, H, W, C)                             # (this pass stands in for rs.forward: rs.backward is the transpose of it)
+        return up, y_lo
 
     def backward(self, dy):
         x = self.x

@@ -49,34 +49,40 @@ def test_five_iterations_fullres_vs_oracle_f16x3_and_f32():
     dev, raw = {}, {}
     # "f32-generic": the strict-fp32 build with every convolution on the round-1 gather kernels and nothing fused (the run-time test switches
     # LADDER_DISABLE_HALO / LADDER_DISABLE_BNSTATS) -- the same arithmetic as the default in other summation orders
-    for prec in ("f32", "f16x3", "f32-generic"):
-        cfg = dict(cfg0, matmul_precision=prec.split("-")[0])
-        for k_ in ("LADDER_DISABLE_HALO", "LADDER_DISABLE_BNSTATS"):
-            if prec == "f32-generic":
-                os.environ[k_] = "1"
-            else:
+    saved = {k_: os.environ.get(k_) for k_ in ("LADDER_DISABLE_HALO", "LADDER_DISABLE_BNSTATS")}
+    try:
+        for prec in ("f32", "f16x3", "f32-generic"):
+            cfg = dict(cfg0, matmul_precision=prec.split("-")[0])
+            for k_ in ("LADDER_DISABLE_HALO", "LADDER_DISABLE_BNSTATS"):
+                if prec == "f32-generic":
+                    os.environ[k_] = "1"
+                else:
+                    os.environ.pop(k_, None)
+            eng = LadderEngine(cfg, "cuda:0", values=P, seed=1)
+            eng.set_mixture(gm["weights"], gm["means"], gm["covs"])
+            d = []
+            for i in range(n_it):
+                eng.run_ae(x, lr_ae, noises[i][0], False, False)
+                f1 = eng.fetch()
+                eng.run_sigma(x, lr_s, noises[i][1], False, False)
+                sg = eng.fetch(["sigma"])["sigma"]
+                eng.run_prior(x, lr_p, noises[i][2], False, False)
+                f3 = eng.fetch()
+                eng.run_inner_sigma(x, lr_i, noises[i][3], False, False)
+                r = ref[i]
+                d.append(dict(elbo=abs(f1["elbo"] - float(r["run1"]["elbo"])) / abs(float(r["run1"]["elbo"])),
+                              l1=abs(f1["l1_reconstruction_error"] - float(r["run1"]["l1_reconstruction_error"])) / abs(float(r["run1"]["l1_reconstruction_error"])),
+                              sigma=abs(sg - float(r["run2"]["sigma"])) / abs(float(r["run2"]["sigma"])),
+                              elbo_prior=abs(f3["elbo_prior"] - float(r["run3"]["elbo_prior"])) / max(abs(float(r["run3"]["elbo_prior"])), 1.0)))
+                raw.setdefault(prec, []).append((f1["elbo"], f3["elbo_prior"]))
+            dev[prec] = d
+            print(prec, [{k: "%.1e" % v for k, v in e.items()} for e in d])
+    finally:          # (restored whatever the loop did: a leaked switch would silently re-route every later test of the process)
+        for k_, v_ in saved.items():
+            if v_ is None:
                 os.environ.pop(k_, None)
-        eng = LadderEngine(cfg, "cuda:0", values=P, seed=1)
-        eng.set_mixture(gm["weights"], gm["means"], gm["covs"])
-        d = []
-        for i in range(n_it):
-            eng.run_ae(x, lr_ae, noises[i][0], False, False)
-            f1 = eng.fetch()
-            eng.run_sigma(x, lr_s, noises[i][1], False, False)
-            sg = eng.fetch(["sigma"])["sigma"]
-            eng.run_prior(x, lr_p, noises[i][2], False, False)
-            f3 = eng.fetch()
-            eng.run_inner_sigma(x, lr_i, noises[i][3], False, False)
-            r = ref[i]
-            d.append(dict(elbo=abs(f1["elbo"] - float(r["run1"]["elbo"])) / abs(float(r["run1"]["elbo"])),
-                          l1=abs(f1["l1_reconstruction_error"] - float(r["run1"]["l1_reconstruction_error"])) / abs(float(r["run1"]["l1_reconstruction_error"])),
-                          sigma=abs(sg - float(r["run2"]["sigma"])) / abs(float(r["run2"]["sigma"])),
-                          elbo_prior=abs(f3["elbo_prior"] - float(r["run3"]["elbo_prior"])) / max(abs(float(r["run3"]["elbo_prior"])), 1.0)))
-            raw.setdefault(prec, []).append((f1["elbo"], f3["elbo_prior"]))
-        dev[prec] = d
-        print(prec, [{k: "%.1e" % v for k, v in e.items()} for e in d])
-    for k_ in ("LADDER_DISABLE_HALO", "LADDER_DISABLE_BNSTATS"):
-        os.environ.pop(k_, None)
+            else:
+                os.environ[k_] = v_
     # Measured on MI355X (deviation from the float64 oracle, iterations 0..4):
     #   f32    elbo 5.7e-08 9.9e-05 5.2e-04 1.7e-03 7.7e-04   l1 3.9e-08 1.5e-04 1.5e-04 6.6e-03 8.6e-03   elbo_prior 6.2e-05 .. 5.9e-02
     #   f16x3  elbo 5.7e-08 3.3e-05 6.3e-04 8.5e-04 8.3e-04   l1 3.9e-08 4.9e-05 9.0e-04 4.0e-03 1.8e-03   elbo_prior 4.4e-05 .. 1.7e-02
