@@ -13,7 +13,7 @@ from . import arch
 from . import layers as _layers
 from .comm import Comm, VirtualComm, VirtualGroup, run_virtual_ranks, _NoComm, _DoneWork, _TracedWork  # noqa: F401  (re-exported: tests, bench.py)
 from .layers import (ADAM_B1, ADAM_B2, ADAM_EPS, BN_EPS, DEFAULT_PRECISION, IN_EPS, PRECISION_NOTES, PRECISIONS, BatchNormAct, Conv2D, Ctx, Dense,  # noqa: F401
-                     DepthToSpace, InstanceNormStyleAct, ParamStore, PlanesOnly, Resize, _igemm, _p, _timed, add_, pad_symmetric, plan_decoder)
+                     DepthToSpace, InstanceNormStyleAct, ParamStore, PlanesOnly, Resize, _p, _timed, add_, pad_symmetric, plan_decoder)
 from .profiler import KernelProfiler  # noqa: F401
 
 
@@ -29,7 +29,7 @@ class Encoder:
         self.exp = cfg["exp_name"]
         self.convs, self.bns = [], []
         for i, (cin, cout, k, s, pad, act, bn) in enumerate(arch.encoder_convs(cfg)):
-            self.convs.append(Conv2D(ctx, ps, "encoder/" + arch.tfname("conv2d", i), k, cin, cout, s, pad, act, bias_grad=not bn))
+            self.convs.append(Conv2D(ctx, ps, "encoder/" + arch.tfname("conv2d", i), k, cin, cout, s, pad, act, bias_grad=not bn, want_bn_sums=bool(bn)))
             self.bns.append(BatchNormAct(ctx, ps, "encoder/" + arch.tfname("batch_normalization", i), cout, "leaky_relu") if bn else None)
         feat, hid = arch.encoder_flat_dim(cfg), arch.encoder_hidden(cfg)
         self.hidden = Dense(ctx, ps, "encoder/dense", feat, hid, "leaky_relu") if hid is not None else None
@@ -41,7 +41,6 @@ class Encoder:
     def forward(self, x):
         h = pad_symmetric(self.ctx, x, 2) if self.exp != "celeba" else x
         for i, (conv, bn) in enumerate(zip(self.convs, self.bns)):
-            conv.want_bn_sums = bn is not None                  # a conv that can emit the statistics of its output does (conv.bn_sums)
             h = conv.forward(h)
             if bn is not None:
                 nxt = self.convs[i + 1] if i + 1 < len(self.convs) else None

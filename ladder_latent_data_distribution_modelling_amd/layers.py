@@ -1,5 +1,6 @@
 """Device context, parameter store and the layers with explicit backward passes of the HIP LaDDer path.  PyTorch supplies device memory, streams and
 torch.distributed only; every arithmetic op below is a call into libladder_hip.so (see _lib.py) -- there is no CPU path."""
+import functools
 import os
 from collections import namedtuple
 
@@ -36,41 +37,22 @@ PRECISION_NOTES = {
     "bf16x3": "REDUCED precision: 2 bf16 planes (16 bits), 3 bf16 MFMAs per product (between TF32 and fp32)"}
 
 PROF = None   # set to a KernelProfiler by bench.py
-_WS_NEED, _KID = {}, {}
 
 
-def _igemm(ctx, name, M, Cin, Cout, Kdim, *args, conv=None):
-    """Forward-type implicit-GEMM call (conv fwd / bwd_data / dense fwd / bwd_data): appends the split-K workspace and the
-    stream; when a profiler is installed the launch is bracketed by HIP events and attributed to its kernel."""
-    key = (M, Kdim, Cout)
-    nb = _WS_NEED.get(key)
-    if nb is None:
-        nb = _WS_NEED[key] = L.query("ladder_igemm_fwd_workspace_bytes", M, Kdim, Cout)
-    wsp, wsn = ctx.ws(nb) if nb else (None, 0)
-    args = args + (wsp, wsn, ctx.stream)
-    if PROF is None or conv == "skip":
-        L.call(name, *args)
-        return
-    kkey = (M, Cin, Cout, conv)
-    kid = _KID.get(kkey)
-    if kid is None:
-        kid = L.query("ladder_conv2d_fwd_kernel_id", *conv) if conv else L.query("ladder_igemm_fwd_tile", M, Cin, Cout)
-        if kid != 256128 and nb and L.query("ladder_igemm_fwd_splits", M, Kdim, Cout) > 1:
-            kid = 0         # split-K launch: two kernels, not attributed
-        _KID[kkey] = kid
-    if kid in (256128, 128128):
-        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        s.record()
-        L.call(name, *args)
-        e.record()
-        PROF.add(kid, s, e, 2.0 * M * Kdim * Cout)
-    else:
-        L.call(name, *args)
+def _igemm_plan(M, Cin, Cout, Kdim, conv=None):
+    """(split-K workspace bytes -- None: the call is handed a null workspace --, profiler kernel id) of a forward-type implicit-GEMM call (conv fwd /
+    bwd_data with the 13 geometry arguments `conv` of ladder_conv2d_fwd_kernel_id, dense fwd / bwd_data without)."""
+    nb = L.query("ladder_igemm_fwd_workspace_bytes", M, Kdim, Cout)
+    kid = L.query("ladder_conv2d_fwd_kernel_id", *conv) if conv else L.query("ladder_igemm_fwd_tile", M, Cin, Cout)
+    if kid != 256128 and nb and L.query("ladder_igemm_fwd_splits", M, Kdim, Cout) > 1:
+        kid = 0         # split-K launch: two kernels, not attributed
+    return nb or None, kid if kid in (256128, 128128) else 0
 
 
 def _timed(kid, flops, name, args, executed=None):
-    """One launch, bracketed by HIP events on the launch stream when a profiler is installed (bench.py's roofline leg)."""
-    if PROF is None:
+    """One launch, bracketed by HIP events on the launch stream and attributed to kernel `kid` when a profiler is installed (bench.py's roofline
+    leg; kid 0: a launch the profiler does not attribute)."""
+    if PROF is None or not kid:
         L.call(name, *args)
         return
     s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -162,6 +144,8 @@ class Ctx:
             self._ws_side_retired.clear()
 
     def ws(self, nbytes):
+        if nbytes is None:       # (a launch that is handed no workspace)
+            return None, 0
         if self.aux is not None and torch.cuda.current_stream(self.device) == self.aux:        # ... and so has the prior-run stream
             if self._ws_aux is None or self._ws_aux.numel() < nbytes:
                 # (stream-ordered: the old buffer belongs to this stream's allocator pool, kernels already enqueued on it run first)
@@ -343,10 +327,12 @@ class ParamStore:
 
 
 # ------------------------------------------------------------------------------------------ layers
-# environment switches of this module: name -> (default, meaning).  The first two are read at every use (tests flip them between engines of one
+# environment switches of this module: name -> (default, meaning).  The first three are read at every use (tests flip them between engines of one
 # process), the others once, at import.
 SWITCHES = {
     "LADDER_DISABLE_HALO": ("0", "1: strict fp32 runs on the round-1 generic gather kernels everywhere, no halo kernels and no projected pairs (test switch)"),
+    "LADDER_DISABLE_BNSTATS": (None, "set (to anything): no convolution epilogue emits batch-norm statistics, they come from the separate pass (test switch; "
+                                     "the library reads it itself at every workspace query -- here it is part of Conv2D.route's cache key)"),
     "LADDER_ENABLE_LOWRES_GATE": ("0", "1: the low-resolution backward-data of a resize -> conv pair also applies the activation backward of the layer below"),
     "LADDER_PROJ_MAX_BYTES": (str(32 << 30), "largest Z / D temporary of a projected pair (conv2d_7 at batch 128: 2.4 GB)"),
     "LADDER_UP2T_MIN_PIXELS": ("256", "smallest low-resolution map whose backward-data runs upsample-fused"),
@@ -371,53 +357,168 @@ UP2W_MIN_PIXELS = int(switch("LADDER_UP2W_MIN_PIXELS"))
 #           "projected" (nine 1x1 convolutions on the low-resolution tensor + combination, 9 of 36)
 #   x       the kept input operand; x_kind says what it is: "input" (the layer's input itself) | "upsampled" (the materialised resize of the tensor
 #           the forward read) | "lowres" (the low-resolution tensor: its upsample by `factor` was never materialised)
-#   y       the activated output;  x_amax  the absolute-maximum record of x (f16x3) or None;  pt, pl  top / left padding
-Kept = namedtuple("Kept", "form x x_kind factor y x_amax pt pl")
+#   y       the activated output;  x_amax  the absolute-maximum record of x (f16x3) or None;  route  the ConvRoute of the layer over its input
+Kept = namedtuple("Kept", "form x x_kind factor y x_amax route")
+
+# one planned launch:
+#   run     the Conv2D method that assembles its arguments and launches it;  fn  the C entry point (include/ladder_hip.h)
+#   ws      bytes of workspace it is handed (0: whatever the grow-only workspace holds; None: it takes none, or a null one)
+#   kid     profiler kernel id (profiler.KernelProfiler.NAMES; 0: not attributed)
+#   bank    orientation of the packed filter bank it reads (BANK_*; None: the HWIO bank itself, or a transpose made on the fly)
+Launch = namedtuple("Launch", "run fn ws kid bank", defaults=(None, 0, None))
+
+# how one Conv2D runs over one input shape (Conv2D.route plans it once; forward and backward follow it):
+#   N H W Ho Wo pt pl   the geometry: input map, output map, top / left padding;  geo: the twelve geometry arguments of the generic entry points;
+#                       flops: operation count of one pass
+#   fwd, wgrad          the forward and the filter-gradient launch;  stats: the forward's epilogue also emits the batch-norm statistics (Conv2D.bn_sums)
+#   dx, dx_gated        the backward-data launch without / with the activation derivative of the layer below in its epilogue (`gate_prev`)
+#   fused_bwd           dx, dW and db from ONE pass over x where that exists (taken when the filter gradient is wanted), else None
+#   halo                the forward runs on the fused 3x3 halo kernels
+#   up2_kids            profiler ids of the upsample-fused forward / backward-data launches over the half-resolution map (where the input is a factor-2 upsample)
+#   wants_planes, needs_fp32    what planes_demand answers the batch norm in front
+ConvRoute = namedtuple("ConvRoute", "N H W Ho Wo pt pl geo flops fwd stats wgrad dx dx_gated fused_bwd halo up2_kids wants_planes needs_fp32")
+
+# orientations of a packed filter bank: the `transpose_flip` values of ladder_filter_pack_split, which documents each layout (include/ladder_hip.h)
+BANK_FWD, BANK_BWD, BANK_S2_BWD, BANK_UP2_FWD, BANK_UP2_BWD, BANK_S2_FWD, BANK_PROJ, BANK_PROJ_T = range(8)
+# orientation -> (taps, cin, cout) of the packed bank of a layer with t = k * k taps, i input and o output channels
+BANK_SHAPE = {BANK_FWD: lambda t, i, o: (t, i, o), BANK_BWD: lambda t, i, o: (t, o, i), BANK_S2_BWD: lambda t, i, o: (t, o, 4 * i),
+              BANK_UP2_FWD: lambda t, i, o: (t, i, 4 * o), BANK_UP2_BWD: lambda t, i, o: (t, 4 * o, i), BANK_S2_FWD: lambda t, i, o: (t, 4 * i, o),
+              BANK_PROJ: lambda t, i, o: (1, i, 9 * o), BANK_PROJ_T: lambda t, i, o: (1, 9 * o, i)}
 
 
 class Conv2D:
-    """tf.layers.conv2d (NHWC / HWIO), bias + activation fused in the kernel epilogue."""
+    """tf.layers.conv2d (NHWC / HWIO), bias + activation fused in the kernel epilogue.  `want_bn_sums`: a batch norm follows -- a forward whose
+    epilogue can emit the statistics of its output does (bn_sums)."""
 
-    def __init__(self, ctx, ps, name, k, cin, cout, stride=1, padding="same", act=None, bias_grad=True):
+    def __init__(self, ctx, ps, name, k, cin, cout, stride=1, padding="same", act=None, bias_grad=True, want_bn_sums=False):
         self.ctx, self.ps, self.name = ctx, ps, name
         self.k, self.cin, self.cout, self.stride, self.padding, self.act = k, cin, cout, stride, padding, act
         # a conv feeding batch-/instance-norm has an identically-zero bias gradient (the norm subtracts the mean):
         # it is not computed and stays 0 in the flat gradient buffer
         self.bias_grad = bias_grad
         self._packed = {}      # (transpose_flip, ns) -> [weight version, packed bf16 planes]
+        self._routes = {}      # route()'s cache
         self.group = arch.group_of(name + "/kernel")           # optimiser group whose version stamps the packed images
-        self.want_bn_sums, self.bn_sums = False, None          # batch-norm statistics of the output from the conv epilogue (RGB conv)
+        self.want_bn_sums, self.bn_sums = want_bn_sums, None   # batch-norm statistics of the output from the conv epilogue
         self.kept = None                                        # Kept record of the last forward (None: a forward-only run kept nothing, or backward consumed it)
 
-    def _keep(self, form, x, y, x_kind="input", factor=1, x_amax=None, pt=0, pl=0, keep=True):
+    def _keep(self, form, x, y, route, x_kind="input", factor=1, x_amax=None, keep=True):
         """The one place a forward variant records what the backward pass gets (backward() clears it)."""
-        self.kept = Kept(form, x, x_kind, factor, y, x_amax, pt, pl) if keep else None
+        self.kept = Kept(form, x, x_kind, factor, y, x_amax, route) if keep else None
 
-    def _halo_ok(self, N, H, W, cin, cout):
-        """The layer runs on the fused 3x3 halo kernels of the configured precision (strict fp32: csrc/convf32.hip; split formats:
-        csrc/convsplit.hip) -- same tiling, same eligibility."""
-        if self.ctx.ns == 0 and halo_disabled():      # (test switch: the round-1 generic fp32 gather kernels everywhere)
-            return False
-        # (strict fp32 also takes the 16- / 8-pixel-wide maps: csrc/convf32s.hip)
-        return bool(self.k == 3 and self.stride == 1 and self.padding == "same"
-                    and L.query("ladder_conv3x3_f32_eligible" if self.ctx.ns == 0 else "ladder_conv3x3_split_eligible", N, H, W, cin, cout))
+    def route(self, in_shape, x_kind="input"):
+        """The ConvRoute of this layer over an input [N, H, W, cin] = `in_shape` whose kept operand is of kind `x_kind` (Kept.x_kind; for the other two
+        kinds the shape is that of the upsampled tensor).  Every eligibility query, workspace size, profiler id and switch that routes the layer is
+        consulted here and only here -- no device needed; routes are cached by everything that enters them."""
+        ctx, halo_v, stats_v = self.ctx, switch("LADDER_DISABLE_HALO"), switch("LADDER_DISABLE_BNSTATS")      # (the values as set: the library reads both itself)
+        key = (tuple(in_shape[:3]), x_kind != "input", ctx.ns, ctx.up2, ctx.keep_activations, halo_v, stats_v)
+        if key not in self._routes:
+            self._routes[key] = self._plan(*key[:5], halo_v == "1")
+        return self._routes[key]
 
-    def _halo_kid(self, N, H, W, cin, cout, class_cout=None):
-        """Profiler id of the halo-kernel launch over an [N, H, W] map with `cin` gathered and `cout` bank columns: the 8x32-pixel tiling
-        (csrc/convf32.hip, csrc/convsplit.hip) or -- strict fp32 only -- a small-map tiling (csrc/convf32s.hip).  `class_cout`: channels per
-        class of a class-structured launch (the 8x32 tiling needs 128)."""
-        if self.ctx.ns:
-            return 256120 + self.ctx.ns
-        big = L.query("ladder_conv3x3_split_eligible", N, H, W, cin, cout) and (class_cout is None or class_cout == 128)
-        return 256120 if big else 256064
+    def _plan(self, shape, upsampled_x, ns, up2, keep, halo_sw):
+        (N, H, W), k, s, cin, cout = shape, self.k, self.stride, self.cin, self.cout
+        (pt, Ho), (pl, Wo) = (arch.conv_out(d, k, s, self.padding) for d in (H, W))
+        geo, M = (N, H, W, cin, Ho, Wo, cout, k, k, s, pt, pl), N * H * W
+        sfx = "" if ns else "_f32"
+        halo_off = ns == 0 and halo_sw                # (test switch: the round-1 generic fp32 gather kernels everywhere)
+        stats = self.want_bn_sums and self.act is None
 
-    def _split_ok(self, N, H, W, cin, cout):
-        """... and the precision is one of the 16-bit split formats (their filter gradient / planes / absmax machinery)."""
-        return bool(self.ctx.ns and self._halo_ok(N, H, W, cin, cout))
+        def halo_ok(h, w, ci, co):
+            # the fused 3x3 halo kernels of the configured precision (strict fp32: csrc/convf32.hip, and the 16- / 8-pixel-wide maps of
+            # csrc/convf32s.hip; split formats: csrc/convsplit.hip) -- same tiling, same eligibility
+            return bool(not halo_off and k == 3 and s == 1 and self.padding == "same"
+                        and L.query("ladder_conv3x3_f32_eligible" if ns == 0 else "ladder_conv3x3_split_eligible", N, h, w, ci, co))
 
-    def _as_dense(self, M):
-        return bool(self.k == 1 and self.stride == 1 and M <= 512 and self.cin >= 16
-                    and L.query("ladder_dense_small_eligible", M, self.cin, self.cout))
+        def halo_kid(h, w, ci, co, class_cout=None):
+            # profiler id of a halo-kernel launch over an [N, h, w] map with `ci` gathered and `co` bank columns: the 8x32-pixel tiling or -- strict
+            # fp32 only -- a small-map tiling (csrc/convf32s.hip).  `class_cout`: channels per class of a class-structured launch (8x32 needs 128)
+            if ns:
+                return 256120 + ns
+            big = L.query("ladder_conv3x3_split_eligible", N, h, w, ci, co) and (class_cout is None or class_cout == 128)
+            return 256120 if big else 256064
+
+        halo = halo_ok(H, W, cin, cout)
+        # 1x1 conv over a tiny map (decoder conv0 on the 1x1 map) = a batch-sized dense layer
+        dense = bool(k == 1 and s == 1 and M <= 512 and cin >= 16 and L.query("ladder_dense_small_eligible", M, cin, cout))
+        # the image-side encoder conv (3 -> Cout channels, stride 2; csrc/convrgb.hip).  The kernels are f16x3 inside -- the filter gradient takes tensor-wide
+        # absmax records -- so they belong to that precision mode; strict fp32 runs the fp32 instantiations
+        rgb = bool(cin == 3 and (ns == 4 or (ns == 0 and not halo_sw)) and L.query("ladder_conv_rgb_s2_eligible", N, H, W, cin, cout, k, k, s, pt, pl))
+
+        def plan_fwd():
+            if halo:
+                return Launch(self._fwd_halo, "ladder_conv3x3_split", None, halo_kid(H, W, cin, cout), BANK_FWD)
+            if dense:
+                return Launch(self._fwd_dense, "ladder_dense_fwd_small" + sfx)
+            if rgb:
+                return Launch(self._fwd_rgb, "ladder_conv_rgb_s2_fwd" + ("_bnstats" if stats else "") + sfx,
+                              L.query("ladder_conv_rgb_s2_fwd_bnstats_workspace_bytes", N, H, W, cout) if stats else None)
+            if ns and L.query("ladder_conv2d_fwd_split_eligible", *geo):
+                nb = L.query("ladder_conv2d_fwd_split_workspace_bytes", *geo)
+                snb = L.query("ladder_conv2d_fwd_split_bnstats_workspace_bytes", *geo) if stats and not nb else 0
+                if snb:                                  # the epilogue also emits the batch-norm statistics of y (no second pass over it)
+                    return Launch(self._fwd_gather_split, "ladder_conv2d_fwd_split_bnstats", snb, 0, BANK_FWD)
+                return Launch(self._fwd_gather_split, "ladder_conv2d_fwd_split", nb, 0 if nb else 128120 + ns, BANK_FWD)    # (split-K launch: two kernels, not attributed)
+            if ns == 0 and stats:
+                snb = L.query("ladder_conv2d_fwd_bnstats_workspace_bytes", *geo)
+                if snb:                                  # strict fp32: the epilogue also emits the batch-norm statistics of y (no second pass over it)
+                    return Launch(self._fwd_gather, "ladder_conv2d_fwd_bnstats", snb)
+            if ns == 0 and k == 3 and s == 2 and pt == 0 and pl == 0 and not halo_sw and L.query("ladder_conv3x3_s2_fwd_f32_eligible", N, H, W, cin, Ho, Wo, cout):
+                # strict fp32, 3x3 / stride 2 over an even map (encoder conv2d_2 / conv2d_3): a stride-1 correlation over the four pixel-parity classes
+                # of x on the halo kernels (x staged once per slab for all taps; csrc/convf32s.hip): 185 / 115 us against 202 / 127 on the gather kernel.
+                # (Behind the statistics-epilogue branch above: conv2d_1 measures 344 us + a statistics pass here against 356 us with them.)
+                return Launch(self._fwd_s2, "ladder_conv3x3_s2_fwd_f32", None, halo_kid(Ho, Wo, 4 * cin, cout), BANK_S2_FWD)
+            return Launch(self._fwd_gather, "ladder_conv2d_fwd", *_igemm_plan(N * Ho * Wo, cin, cout, k * k * cin, (N, H, W, cin, Ho, Wo, cout, k, k, s, 1, pt, pl)))
+
+        def plan_wgrad():
+            if dense:
+                return Launch(self._wg_dense, "ladder_dense_bwd_weight_small" + sfx)
+            if rgb:                                      # (strict fp32: the fp32 filter-gradient kernel of the same layer)
+                return Launch(self._wg_rgb, "ladder_conv_rgb_s2_bwd_filter" + sfx, L.query("ladder_conv_rgb_s2_bwd_filter_workspace_bytes", N, H, W, cout))
+            # the 16-bit split formats on the halo kernels: their filter gradient / planes / absmax machinery
+            if ns and halo and L.query("ladder_conv3x3_wgrad_split_eligible", N, H, W, cin, cout, ns):
+                return Launch(self._wg_halo_split, "ladder_conv3x3_wgrad_split", L.query("ladder_conv3x3_wgrad_split_workspace_bytes", N, H, W, cin, cout), 9120 + ns)
+            if ns and L.query("ladder_conv2d_bwd_filter_split_eligible", *geo):
+                return Launch(self._wg_gather_split, "ladder_conv2d_bwd_filter_split", L.query("ladder_conv2d_bwd_filter_split_workspace_bytes", *geo[:9]))
+            if (ns == 0 and upsampled_x and up2 >= 2 and (H // 2) * (W // 2) >= UP2W_MIN_PIXELS
+                    and L.query("ladder_conv3x3_up2_wgrad_eligible", N, H // 2, W // 2, cin, cout)):
+                # strict fp32, x = resize2x(x_lo): 25 instead of 36 tap tiles, read from the even sub-grid of the kept upsample (csrc/convf32.hip)
+                return Launch(self._wg_up2, "ladder_conv3x3_up2_wgrad", L.query("ladder_conv3x3_up2_wgrad_workspace_bytes", N, H // 2, W // 2, cin, cout), 9120)
+            return Launch(self._wg_gather, "ladder_conv2d_bwd_filter", L.query("ladder_conv2d_bwd_filter_workspace_bytes", *geo[:9]),
+                          9128 if L.query("ladder_conv2d_bwd_filter_kernel_id", *geo) == 9128 else 0)
+
+        def plan_dx(gated):
+            if dense:
+                return Launch(self._dx_dense, "ladder_dense_bwd_data_small" + sfx)
+            if not gated and halo_ok(Ho, Wo, cout, cin):
+                return Launch(self._dx_halo, "ladder_conv3x3_split", None, halo_kid(H, W, cout, cin), BANK_BWD)
+            if (ns in (0, 4) and not gated and s == 2 and not halo_off
+                    and (L.query("ladder_conv3x3_s2_bwd_data_split_eligible", *geo)
+                         or (ns == 0 and k == 3 and pt == 0 and pl == 0 and L.query("ladder_conv3x3_s2_bwd_data_f32_eligible", N, H, W, cin, Ho, Wo, cout)))):
+                # 3x3 / stride 2 over a map whose gradient is halo-kernel sized (enc.conv1): the four output-parity classes in ONE launch
+                return Launch(self._dx_s2, "ladder_conv3x3_s2_bwd_data_split", None, halo_kid(Ho, Wo, cout, 4 * cin, cin), BANK_S2_BWD)
+            if ns and L.query("ladder_conv2d_bwd_data_split_eligible", *geo, 1 if gated else 0):
+                return Launch(self._dx_gather_split, "ladder_conv2d_bwd_data_split", L.query("ladder_conv2d_bwd_data_split_workspace_bytes", *geo), 0, BANK_BWD)
+            # (a strided backward-data call is several parity-class launches: not attributed by the profiler)
+            nb, kid = _igemm_plan(M, cout, cin, k * k * cout, (N, Ho, Wo, cout, H, W, cin, k, k, 1, 1, k - 1 - pt, k - 1 - pl))
+            # strict fp32 3x3: the flipped / transposed fp32 bank is re-packed with all others in one launch per step, else transposed on the fly
+            return Launch(self._dx_gather, "ladder_conv2d_bwd_data", nb, kid if s == 1 else 0, BANK_BWD if (ns == 0 and cout % 16 == 0 and k == 3) else None)
+
+        fwd, wgrad = plan_fwd(), plan_wgrad()
+        # 1x1 to <= 4 channels over a wide map (the CelebA output conv): dx, dW and db from ONE pass over x
+        fused_bwd = Launch(self._bwd_smallcout, "ladder_conv1x1_smallcout_bwd_absmax", L.query("ladder_conv1x1_smallcout_bwd_workspace_bytes", M, cin, cout)) if (
+            k == 1 and s == 1 and L.query("ladder_conv1x1_smallcout_eligible", M, cin, cout)) else None
+        up2_kids = (halo_kid(H // 2, W // 2, cin, 4 * cout, cout), halo_kid(H // 2, W // 2, 4 * cout, cin))
+        wants_planes = bool(ns == 4 and cin != 3 and fwd.fn.startswith("ladder_conv2d_fwd_split"))
+        needs_fp32 = bool(not wants_planes or (keep and wgrad.fn != "ladder_conv2d_bwd_filter_split"))
+        return ConvRoute(N, H, W, Ho, Wo, pt, pl, geo, 2.0 * N * Ho * Wo * k * k * cin * cout, fwd, "bnstats" in fwd.fn, wgrad, plan_dx(False), plan_dx(True),
+                         fused_bwd, halo, up2_kids, wants_planes, needs_fp32)
+
+    def planes_demand(self, in_shape):
+        """(wants_planes, needs_fp32) for an input of `in_shape`: whether this layer's forward reads the fp16 plane images of its input
+        (split gather kernel) and whether anything of it still needs the fp32 tensor (a filter gradient outside the split kernel)."""
+        r = self.route(in_shape)
+        return r.wants_planes, r.needs_fp32
 
     @staticmethod
     def _ps(Ho, Wo):
@@ -425,50 +526,19 @@ class Conv2D:
         can re-scale at sample boundaries (a sample's output pixels = whole 32-pixel chunks)."""
         return (Ho * Wo) % 32 == 0
 
-    def _rgb(self, N, H, W, pt, pl):
-        # (the kernels are f16x3 inside -- the filter gradient takes tensor-wide absmax records -- so they belong to that precision mode)
-        return bool(self.ctx.ns == 4 and self.cin == 3 and L.query("ladder_conv_rgb_s2_eligible", N, H, W, self.cin, self.cout, self.k, self.k,
-                                                               self.stride, pt, pl))
+    def _wb(self):
+        return _p(self.ps.w[self.name + "/kernel"]), _p(self.ps.w[self.name + "/bias"])
 
-    def _rgb_fwd32(self, N, H, W, pt, pl):
-        # strict fp32: the forward of the same layer on the fp32 instantiation of the kernel (its filter gradient stays on the generic kernel)
-        return bool(self.ctx.ns == 0 and self.cin == 3 and not halo_disabled() and
-                    L.query("ladder_conv_rgb_s2_eligible", N, H, W, self.cin, self.cout, self.k, self.k, self.stride, pt, pl))
-
-    def planes_demand(self, in_shape):
-        """(wants_planes, needs_fp32) for an input of `in_shape`: whether this layer's forward reads the fp16 plane images of its input
-        (split gather kernel) and whether anything of it still needs the fp32 tensor (a filter gradient outside the split kernel)."""
-        ctx = self.ctx
-        N, H, W, _ = in_shape
-        if ctx.ns != 4 or self.cin == 3 or self._split_ok(N, H, W, self.cin, self.cout):
-            return False, True
-        pt, Ho = arch.conv_out(H, self.k, self.stride, self.padding)
-        pl, Wo = arch.conv_out(W, self.k, self.stride, self.padding)
-        geo = (N, H, W, self.cin, Ho, Wo, self.cout, self.k, self.k, self.stride, pt, pl)
-        if self._as_dense(N * H * W) or not L.query("ladder_conv2d_fwd_split_eligible", *geo):
-            return False, True
-        return True, bool(ctx.keep_activations and not L.query("ladder_conv2d_bwd_filter_split_eligible", *geo))
+    def _grads(self):
+        return _p(self.ps.g[self.name + "/kernel"]), _p(self.ps.g[self.name + "/bias"]) if self.bias_grad else None
 
     def _packed_filter(self, transpose_flip):
         """Split bf16 planes of the filter bank in the kernel's LDS layout, re-packed when the weights changed (always while a
         hipGraph is being captured, so that a replay re-packs the then-current weights)."""
         ns, ps = self.ctx.ns, self.ps
-        if ns == 0 and transpose_flip == 0:           # strict fp32: the HWIO bank IS the forward bank [tap][Cin][Cout]
+        if ns == 0 and transpose_flip == BANK_FWD:    # strict fp32: the HWIO bank IS the forward bank [tap][Cin][Cout]
             return ps.w[self.name + "/kernel"]
-        cin, cout = (self.cout, self.cin) if transpose_flip in (1, 2) else (self.cin, self.cout)
-        if transpose_flip == 2:                       # the four parity classes of a stride-2 backward-data as output-channel blocks
-            cout = 4 * self.cin
-        elif transpose_flip == 3:                     # the four output-parity classes of the upsample-fused forward (effective taps)
-            cout = 4 * self.cout
-        elif transpose_flip == 4:                     # backward-data of the upsample-fused pair: the four pixel-parity classes of dy as input groups
-            cin, cout = 4 * self.cout, self.cin
-        elif transpose_flip == 5:                     # stride-2 forward: the four pixel-parity classes of x as input groups (strict fp32)
-            cin, cout = 4 * self.cin, self.cout
-        taps = self.k * self.k
-        if transpose_flip == 6:                       # project-then-upsample: the nine taps side by side, ONE [cin][9 cout] matrix (strict fp32) ...
-            taps, cin, cout = 1, self.cin, 9 * self.cout
-        elif transpose_flip == 7:                     # ... and its transpose [9 cout][cin], the backward-data operand
-            taps, cin, cout = 1, 9 * self.cout, self.cin
+        taps, cin, cout = BANK_SHAPE[transpose_flip](self.k * self.k, self.cin, self.cout)
         ent = self._packed.get((transpose_flip, ns))
         if ent is None:
             nb = L.query("ladder_filter_pack_split_bytes", taps, cin, cout, ns)
@@ -487,18 +557,21 @@ class Conv2D:
         halo kernel (ladder_conv3x3_split_proj); returns proj's output (plan_decoder decides eligibility).  `keep_y` = the
         activation is needed later (training forward: both layers' backward read it); a forward-only run never writes it."""
         N, H, W, _ = x.shape
-        pt, _ = arch.conv_out(H, self.k, self.stride, self.padding)
-        pl, _ = arch.conv_out(W, self.k, self.stride, self.padding)
         y = self.ctx.empty(N, H, W, self.cout) if keep_y else None
         out = self.ctx.empty(N, H, W, proj.cout)
         x_amax = self.ctx.absmax(x)
-        args = (_p(x), _p(x_amax), _p(self._packed_filter(0)), _p(self.ps.w[self.name + "/bias"]), _p(y),
+        args = (_p(x), _p(x_amax), _p(self._packed_filter(BANK_FWD)), _p(self.ps.w[self.name + "/bias"]), _p(y),
                 _p(self.ps.w[proj.name + "/kernel"]), _p(self.ps.w[proj.name + "/bias"]), _p(out), proj.cout, N, H, W, self.cin, self.cout,
                 L.ACT[self.act], self.ctx.ns, self.ctx.stream)
         _timed(256120 + self.ctx.ns, 2.0 * N * H * W * 9 * self.cin * self.cout, "ladder_conv3x3_split_proj", args)
-        self._keep("plain", x, y, x_amax=x_amax, pt=pt, pl=pl)
-        proj._keep("plain", y, out)
+        self._keep("plain", x, y, self.route(x.shape), x_amax=x_amax)
+        proj._keep("plain", y, out, proj.route(out.shape))
         return out
+
+    def _count_up2(self, tag, skipped):
+        """bench.py's executed-FLOP model: one more upsample-fused launch `tag` of this layer, which never issues `skipped` of the reference's products."""
+        self.ctx.up2_used[self.name + tag] = self.ctx.up2_used.get(self.name + tag, 0) + 1
+        self.ctx.up2_skipped[self.name + tag] = skipped
 
     def _is_projection(self, proj):
         """`proj` is a 1x1 conv to <= 4 channels without activation on this layer's output (the RGB conv behind the last 3x3 conv)."""
@@ -514,9 +587,7 @@ class Conv2D:
         M, n9 = N * H * W, 9 * self.cout
         flops = 2.0 * N * f * f * H * W * 9 * self.cin * self.cout      # the reference's operation count (algorithmic) ...
         executed = 2.0 * M * self.cin * n9                               # ... of which 9 / 36 are issued (factor 2; 1 / 16 at factor 4)
-        ukey = self.name + (":train" if keep_y else "")
-        ctx.up2_used[ukey] = ctx.up2_used.get(ukey, 0) + 1
-        ctx.up2_skipped[ukey] = 1.0 - 1.0 / (f * f)
+        self._count_up2(":train" if keep_y else "", 1.0 - 1.0 / (f * f))
         bias = self.ps.w[self.name + "/bias"]
         y = ctx.empty(N, f * H, f * W, self.cout) if (keep_y or proj is None) else None
         out, pw, pb, pco = y, None, None, 0
@@ -528,23 +599,23 @@ class Conv2D:
             nb = L.query("ladder_up2proj_fused_workspace_bytes", N, H, W, self.cout, pco)
             wsp, wsn = ctx.ws(nb) if nb else (None, 0)
             _timed(128136, flops, "ladder_up2proj_fused_fwd",
-                   (_p(x), _p(self._packed_filter(7)), _p(bias), _p(y), _p(pw), _p(pb), _p(out) if proj is not None else None, pco, N, H, W, self.cin, self.cout,
+                   (_p(x), _p(self._packed_filter(BANK_PROJ_T)), _p(bias), _p(y), _p(pw), _p(pb), _p(out) if proj is not None else None, pco, N, H, W, self.cin, self.cout,
                     L.ACT[self.act], wsp, wsn, st), executed)
             return y, out
         # (the nine planes Z are a transient [N H W, 9 cout] fp32 tensor: beyond PROJ_MAX_BYTES the layer takes the forms that allocate none)
         z = ctx.empty(M, n9)
         wsp, wsn = ctx.ws(L.query("ladder_igemm_fwd_workspace_bytes", M, self.cin, n9))
         _timed(128132 if L.query("ladder_dense_fwd_is_persistent", M, self.cin, n9) else abs(L.query("ladder_igemm_fwd_tile", M, self.cin, n9)), flops, "ladder_dense_fwd",
-               (_p(x), _p(self._packed_filter(6)), None, _p(z), M, self.cin, n9, 0, wsp, wsn, st), executed)
+               (_p(x), _p(self._packed_filter(BANK_PROJ)), None, _p(z), M, self.cin, n9, 0, wsp, wsn, st), executed)
         if proj is not None:
             L.call("ladder_up2proj_fwd_combine", _p(z), _p(bias), _p(y), _p(pw), _p(pb), _p(out), proj.cout, N, H, W, self.cout, L.ACT[self.act], st)
         else:
             L.call("ladder_upfproj_fwd_combine", _p(z), _p(bias), _p(y), f, N, H, W, self.cout, L.ACT[self.act], st)
         return y, out
 
-    def _forward_tapfold(self, x, proj, keep_y):
+    def _forward_tapfold(self, x, proj, keep_y, kid):
         """forward_up2 in the tap-folded form (ladder_conv3x3_up2_split: four output-parity classes with effective taps, 25 instead of 36
-        low-resolution tap products and no upsampled tensor) + its exact border lines.  Returns (y, out, absmax record of x)."""
+        low-resolution tap products and no upsampled tensor; `kid`: its profiler id) + its exact border lines.  Returns (y, out, absmax record of x)."""
         ctx = self.ctx
         N, H, W = x.shape[0], x.shape[1], x.shape[2]
         strided = 0
@@ -552,24 +623,22 @@ class Conv2D:
         x_amax = ctx.absmax(x)                                           # (max |upsampled| = max |x|: the resize is a convex combination)
         flops = 2.0 * N * 4 * H * W * 9 * self.cin * self.cout          # the reference's operation count (algorithmic) ...
         executed = flops * 25.0 / 36.0                                   # ... of which 25 / 36 are issued
-        ukey = self.name + (":train" if keep_y else "")                   # (bench.py's executed-FLOP model: forward-only / training forward)
-        ctx.up2_used[ukey] = ctx.up2_used.get(ukey, 0) + 1
-        ctx.up2_skipped[ukey] = 11.0 / 36.0
+        self._count_up2(":train" if keep_y else "", 11.0 / 36.0)          # (forward-only / training forward)
         wsp, wsn = ctx.ws(L.query("ladder_conv3x3_up2_edges_workspace_bytes", N, H, W, self.cin, self.cout))
         if proj is not None:
             y = ctx.empty(N, 2 * H, 2 * W, self.cout) if keep_y else None
             out = ctx.empty(N, 2 * H, 2 * W, proj.cout)
             pw, pb = self.ps.w[proj.name + "/kernel"], self.ps.w[proj.name + "/bias"]
-            _timed(self._halo_kid(N, H, W, self.cin, 4 * self.cout, self.cout), flops, "ladder_conv3x3_up2_split_proj",
-                   (_p(x), _p(x_amax), _p(self._packed_filter(3)), _p(bias), _p(y), _p(pw), _p(pb), _p(out), proj.cout, N, H, W, self.cin, self.cout,
+            _timed(kid, flops, "ladder_conv3x3_up2_split_proj",
+                   (_p(x), _p(x_amax), _p(self._packed_filter(BANK_UP2_FWD)), _p(bias), _p(y), _p(pw), _p(pb), _p(out), proj.cout, N, H, W, self.cin, self.cout,
                     L.ACT[self.act], ctx.ns, strided, ctx.stream), executed)
             L.call("ladder_conv3x3_up2_edges", _p(x), _p(wk), _p(bias), _p(y), None, _p(pw), _p(pb), _p(out), proj.cout, N, H, W, self.cin, self.cout,
                    L.ACT[self.act], strided, wsp, wsn, ctx.stream)
             return y, out, x_amax
         y = ctx.empty(N, 2 * H, 2 * W, self.cout)
         y_amax = ctx.new_amax() if ctx.ns == 4 else None
-        _timed(self._halo_kid(N, H, W, self.cin, 4 * self.cout, self.cout), flops, "ladder_conv3x3_up2_split",
-               (_p(x), _p(x_amax), _p(self._packed_filter(3)), _p(bias), _p(y), _p(y_amax), N, H, W, self.cin, self.cout, L.ACT[self.act], ctx.ns,
+        _timed(kid, flops, "ladder_conv3x3_up2_split",
+               (_p(x), _p(x_amax), _p(self._packed_filter(BANK_UP2_FWD)), _p(bias), _p(y), _p(y_amax), N, H, W, self.cin, self.cout, L.ACT[self.act], ctx.ns,
                 strided, ctx.stream), executed)
         L.call("ladder_conv3x3_up2_edges", _p(x), _p(wk), _p(bias), _p(y), _p(y_amax), None, None, None, 0, N, H, W, self.cin, self.cout,
                L.ACT[self.act], strided, wsp, wsn, ctx.stream)
@@ -588,95 +657,64 @@ class Conv2D:
             if not keep_y:
                 proj.kept = None
             return out
-        x_amax = None
+        # (upsampled: x = the factor-2 upsample of a tensor, the filter gradient reads its even sub-grid)
+        kept_x, x_kind, x_amax = (x, "lowres", None) if upsampled is None else (upsampled, "upsampled", None)
+        r = self.route((x.shape[0], pair.factor * x.shape[1], pair.factor * x.shape[2], self.cin), x_kind)
         if pair.form == "projected":
             y, out = self._forward_proj(x, proj, keep_y, pair.factor, pair.one_launch)
         else:
-            y, out, x_amax = self._forward_tapfold(x, proj, keep_y)
-        if upsampled is not None:          # x = the factor-2 upsample of a tensor: the filter gradient reads its even sub-grid
-            self._keep(pair.form, upsampled, y, "upsampled", pair.factor, x_amax, 1, 1, keep=keep_y)
-        else:
-            self._keep(pair.form, x, y, "lowres", pair.factor, x_amax, 1, 1, keep=keep_y)
+            y, out, x_amax = self._forward_tapfold(x, proj, keep_y, r.up2_kids[0])
+        self._keep(pair.form, kept_x, y, r, x_kind, pair.factor, x_amax, keep=keep_y)
         if proj is not None:
-            proj._keep("plain", y, out, keep=keep_y)
+            proj._keep("plain", y, out, proj.route(out.shape), keep=keep_y)
         return out
 
     def forward(self, x):
-        N, H, W, _ = x.shape
-        pt, Ho = arch.conv_out(H, self.k, self.stride, self.padding)
-        pl, Wo = arch.conv_out(W, self.k, self.stride, self.padding)
-        y = self.ctx.empty(N, Ho, Wo, self.cout)
-        self._keep("plain", x, y, x_amax=self._forward_plain(x, y, N, H, W, Ho, Wo, pt, pl), pt=pt, pl=pl)
+        r = self.route(x.shape)
+        y = self.ctx.empty(r.N, r.Ho, r.Wo, self.cout)
+        self._keep("plain", x, y, r, x_amax=r.fwd.run(r, x, y))
         return y
 
-    def _forward_plain(self, x, y, N, H, W, Ho, Wo, pt, pl):
-        """The launch(es) of forward(); returns the absolute-maximum record of x where the kernel took one (the filter gradient re-uses it)."""
-        x_amax = None
-        if self._halo_ok(N, H, W, self.cin, self.cout):
-            x_amax = self.ctx.absmax(x)
-            y_amax = self.ctx.new_amax() if self.ctx.ns == 4 else None
-            args = (_p(x), _p(x_amax), _p(self._packed_filter(0)), _p(self.ps.w[self.name + "/bias"]), _p(y), _p(y_amax), N, H, W,
-                    self.cin, self.cout, L.ACT[self.act], self.ctx.ns, self.ctx.stream)
-            self.ctx.set_amax(y, y_amax)
-            _timed(self._halo_kid(N, H, W, self.cin, self.cout), 2.0 * N * H * W * 9 * self.cin * self.cout, "ladder_conv3x3_split", args)
-            return x_amax
-        if self._as_dense(N * H * W):                   # 1x1 conv over a tiny map (decoder conv0 on the 1x1 map) = a batch-sized dense layer
-            L.call("ladder_dense_fwd_small" + self.ctx.sfx, _p(x), _p(self.ps.w[self.name + "/kernel"]), _p(self.ps.w[self.name + "/bias"]), _p(y), N * H * W,
-                   self.cin, self.cout, L.ACT[self.act], self.ctx.stream)
-            return x_amax
-        geo = (N, H, W, self.cin, Ho, Wo, self.cout, self.k, self.k, self.stride, pt, pl)
-        if self._rgb(N, H, W, pt, pl) or self._rgb_fwd32(N, H, W, pt, pl):   # the image-side encoder conv (3 -> Cout channels, stride 2): csrc/convrgb.hip
-            sfx = "" if self.ctx.ns else "_f32"
-            if self.want_bn_sums and self.act is None:
-                wsp, wsn = self.ctx.ws(L.query("ladder_conv_rgb_s2_fwd_bnstats_workspace_bytes", N, H, W, self.cout))
-                self.bn_sums = self.ctx.empty(6 * self.cout)       # sum | sum of squares | min | max per channel
-                L.call("ladder_conv_rgb_s2_fwd_bnstats" + sfx, _p(x), _p(self.ps.w[self.name + "/kernel"]), _p(self.ps.w[self.name + "/bias"]), _p(y),
-                       N, H, W, self.cout, 0, _p(self.bn_sums), wsp, wsn, self.ctx.stream)
-            else:
-                L.call("ladder_conv_rgb_s2_fwd" + sfx, _p(x), _p(self.ps.w[self.name + "/kernel"]), _p(self.ps.w[self.name + "/bias"]), _p(y), N, H,
-                       W, self.cout, L.ACT[self.act], self.ctx.stream)
-            return x_amax
-        if self.ctx.ns and L.query("ladder_conv2d_fwd_split_eligible", *geo):
-            x_amax = self.ctx.absmax(x)
-            nb = L.query("ladder_conv2d_fwd_split_workspace_bytes", *geo)
-            wsp, wsn = self.ctx.ws(nb)
-            if self.want_bn_sums and self.act is None and not nb:
-                snb = L.query("ladder_conv2d_fwd_split_bnstats_workspace_bytes", *geo)
-                if snb:                                  # the epilogue also emits the batch-norm statistics of y (no second pass over it)
-                    swp, swn = self.ctx.ws(snb)
-                    self.bn_sums = self.ctx.empty(6 * self.cout)
-                    L.call("ladder_conv2d_fwd_split_bnstats", _p(self.ctx.planes(x, self._ps(Ho, Wo))), _p(x_amax), _p(self._packed_filter(0)),
-                           _p(self.ps.w[self.name + "/bias"]), _p(y), *geo, 0, self.ctx.ns, _p(self.bn_sums), swp, swn, self.ctx.stream)
-                    return x_amax
-            args = (_p(self.ctx.planes(x, self._ps(Ho, Wo))), _p(x_amax), _p(self._packed_filter(0)), _p(self.ps.w[self.name + "/bias"]), _p(y)) + geo + (
-                L.ACT[self.act], self.ctx.ns, wsp, wsn, self.ctx.stream)
-            if nb:                                       # split-K launch: two kernels, not attributed by the profiler
-                L.call("ladder_conv2d_fwd_split", *args)
-            else:
-                _timed(128120 + self.ctx.ns, 2.0 * N * Ho * Wo * self.k * self.k * self.cin * self.cout, "ladder_conv2d_fwd_split", args)
-            return x_amax
-        if self.ctx.ns == 0 and self.want_bn_sums and self.act is None:
-            snb = L.query("ladder_conv2d_fwd_bnstats_workspace_bytes", *geo)
-            if snb:                                      # strict fp32: the epilogue also emits the batch-norm statistics of y (no second pass over it)
-                swp, swn = self.ctx.ws(snb)
-                self.bn_sums = self.ctx.empty(6 * self.cout)
-                L.call("ladder_conv2d_fwd_bnstats", _p(x), _p(self.ps.w[self.name + "/kernel"]), _p(self.ps.w[self.name + "/bias"]), _p(y), *geo, 0,
-                       _p(self.bn_sums), swp, swn, self.ctx.stream)
-                return x_amax
-        if (self.ctx.ns == 0 and self.k == 3 and self.stride == 2 and pt == 0 and pl == 0 and not halo_disabled()
-                and L.query("ladder_conv3x3_s2_fwd_f32_eligible", N, H, W, self.cin, Ho, Wo, self.cout)):
-            # strict fp32, 3x3 / stride 2 over an even map (encoder conv2d_2 / conv2d_3): a stride-1 correlation over the four pixel-parity classes
-            # of x on the halo kernels (x staged once per slab for all taps; csrc/convf32s.hip): 185 / 115 us against 202 / 127 on the gather kernel.
-            # (Behind the statistics-epilogue branch above: conv2d_1 measures 344 us + a statistics pass here against 356 us with them.)
-            args = (_p(x), _p(self._packed_filter(5)), _p(self.ps.w[self.name + "/bias"]), _p(y), N, H, W, self.cin, Ho, Wo, self.cout,
-                    L.ACT[self.act], self.ctx.stream)
-            _timed(self._halo_kid(N, Ho, Wo, 4 * self.cin, self.cout), 2.0 * N * Ho * Wo * 9 * self.cin * self.cout, "ladder_conv3x3_s2_fwd_f32", args)
-            return x_amax
-        _igemm(self.ctx, "ladder_conv2d_fwd", N * Ho * Wo, self.cin, self.cout, self.k * self.k * self.cin,
-               _p(x), _p(self.ps.w[self.name + "/kernel"]), _p(self.ps.w[self.name + "/bias"]), _p(y),
-               N, H, W, self.cin, Ho, Wo, self.cout, self.k, self.k, self.stride, pt, pl, L.ACT[self.act],
-               conv=(N, H, W, self.cin, Ho, Wo, self.cout, self.k, self.k, self.stride, 1, pt, pl))
+    # -- one launch function per forward route: each assembles the arguments of r.fwd.fn and launches; returns the absolute-maximum record of x where
+    # the kernel took one (the filter gradient re-uses it)
+    def _fwd_halo(self, r, x, y):
+        ctx = self.ctx
+        x_amax = ctx.absmax(x)
+        y_amax = ctx.new_amax() if ctx.ns == 4 else None
+        ctx.set_amax(y, y_amax)
+        _timed(r.fwd.kid, r.flops, r.fwd.fn, (_p(x), _p(x_amax), _p(self._packed_filter(BANK_FWD)), self._wb()[1], _p(y), _p(y_amax), r.N, r.H, r.W,
+                                              self.cin, self.cout, L.ACT[self.act], ctx.ns, ctx.stream))
         return x_amax
+
+    def _fwd_dense(self, r, x, y):
+        L.call(r.fwd.fn, _p(x), *self._wb(), _p(y), r.N * r.H * r.W, self.cin, self.cout, L.ACT[self.act], self.ctx.stream)
+
+    def _sums(self, r):
+        """Where the forward's epilogue emits the batch-norm statistics (such a layer has no activation): (pointer to a fresh record bn_sums,), else ()."""
+        if not r.stats:
+            return ()
+        self.bn_sums = self.ctx.empty(6 * self.cout)       # sum | sum of squares | min | max per channel
+        return (_p(self.bn_sums),)
+
+    def _fwd_rgb(self, r, x, y):
+        ws = self.ctx.ws(r.fwd.ws) if r.stats else ()
+        L.call(r.fwd.fn, _p(x), *self._wb(), _p(y), r.N, r.H, r.W, self.cout, L.ACT[self.act], *self._sums(r), *ws, self.ctx.stream)
+
+    def _fwd_gather_split(self, r, x, y):
+        ctx = self.ctx
+        x_amax = ctx.absmax(x)
+        wsp, wsn = ctx.ws(r.fwd.ws)
+        args = (_p(ctx.planes(x, self._ps(r.Ho, r.Wo))), _p(x_amax), _p(self._packed_filter(BANK_FWD)), self._wb()[1], _p(y)) + r.geo
+        _timed(r.fwd.kid, r.flops, r.fwd.fn, args + (L.ACT[self.act], ctx.ns, *self._sums(r), wsp, wsn, ctx.stream))
+        return x_amax
+
+    def _fwd_s2(self, r, x, y):
+        _timed(r.fwd.kid, r.flops, r.fwd.fn, (_p(x), _p(self._packed_filter(BANK_S2_FWD)), self._wb()[1], _p(y), r.N, r.H, r.W, self.cin, r.Ho, r.Wo,
+                                              self.cout, L.ACT[self.act], self.ctx.stream))
+
+    def _fwd_gather(self, r, x, y):
+        wsp, wsn = self.ctx.ws(r.fwd.ws)
+        _timed(r.fwd.kid, r.flops, r.fwd.fn, (_p(x), *self._wb(), _p(y), *r.geo, L.ACT[self.act], *self._sums(r), wsp, wsn, self.ctx.stream))
 
     def _backward_proj(self, dy, need_dx, wgrad, gate, proj_grad=None):
         """Backward of the project-then-upsample form from the low-resolution x: D [M, 9 cout] = (shift o up)^T dy once (elementwise), then
@@ -700,8 +738,7 @@ class Conv2D:
         else:
             L.call("ladder_upfproj_bwd_combine", _p(dy), _p(d), f, N, H, W, self.cout, st)
         if wgrad:
-            ctx.up2_used[self.name + ":wgrad"] = ctx.up2_used.get(self.name + ":wgrad", 0) + 1
-            ctx.up2_skipped[self.name + ":wgrad"] = 1.0 - 1.0 / (f * f)
+            self._count_up2(":wgrad", 1.0 - 1.0 / (f * f))
             dwcat, db9 = ctx.empty(self.cin, n9), (ctx.empty(n9) if self.bias_grad else None)   # (a conv in front of a norm has no bias gradient)
             wsp, wsn = ctx.ws(L.query("ladder_dense_bwd_weight_workspace_bytes", M, self.cin, n9))
             _timed(9132 if L.query("ladder_dense_bwd_weight_is_persistent", M, self.cin, n9) else 9130, flops, "ladder_dense_bwd_weight",
@@ -710,8 +747,7 @@ class Conv2D:
                    _p(self.ps.g[self.name + "/bias"]) if self.bias_grad else None, self.cin, self.cout, st)
         dx = None
         if need_dx:
-            ctx.up2_used[self.name + ":bwd"] = ctx.up2_used.get(self.name + ":bwd", 0) + 1
-            ctx.up2_skipped[self.name + ":bwd"] = 1.0 - 1.0 / (f * f)
+            self._count_up2(":bwd", 1.0 - 1.0 / (f * f))
             dx = ctx.empty(N, H, W, self.cin)
             wsp, wsn = ctx.ws(L.query("ladder_igemm_fwd_workspace_bytes", M, n9, self.cin))
             gy, gact = gate if gate is not None else (None, None)
@@ -720,16 +756,16 @@ class Conv2D:
                 # K-contiguous weight operand = wcat itself (orientation 6): gemm_nt16_f32_kernel (v_mfma_f32_16x16x4_f32; 3-5 % ahead of the 32x32x2 kernel
                 # on this long-K shape: conv2d_7 1 202 against 1 266 us, profiles/r05_gemm_library_probe.txt)
                 _timed(128134, flops, "ladder_dense_bwd_data_nt",
-                       (_p(d), _p(self._packed_filter(6)), _p(dx), M, self.cin, n9, _p(gy), L.ACT[gact] if gact else 0, st), executed)
+                       (_p(d), _p(self._packed_filter(BANK_PROJ)), _p(dx), M, self.cin, n9, _p(gy), L.ACT[gact] if gact else 0, st), executed)
             else:
                 _timed(abs(L.query("ladder_igemm_fwd_tile", M, n9, self.cin)), flops, "ladder_dense_bwd_data",
-                       (_p(d), _p(self._packed_filter(7)), _p(dx), M, self.cin, n9, _p(gy), L.ACT[gact] if gact else 0, wsp, wsn, st), executed)
+                       (_p(d), _p(self._packed_filter(BANK_PROJ_T)), _p(dx), M, self.cin, n9, _p(gy), L.ACT[gact] if gact else 0, wsp, wsn, st), executed)
         return dx
 
-    def _dx_lowres(self, dy, dy_amax, gate=None):
+    def _dx_lowres(self, dy, dy_amax, kid, gate=None):
         """d loss / d x_lo for y = conv(resize2x(x_lo)): the composite transpose is a zero-padded 5x5 / stride-2 correlation over dy (one launch of
         the halo kernel, 25 instead of 36 tap products per low-resolution pixel, the [N, 2H, 2W, cin] intermediate never written), exact on
-        every pixel but the four border lines of dx, where the resize's clamp and the convolution's padding change the coefficients: those
+        every pixel (`kid`: that launch's profiler id) but the four border lines of dx, where the resize's clamp and the convolution's padding change the coefficients: those
         come from 4-pixel-wide strips of dy through the plain backward-data + resize-transpose kernels (exact there by construction)."""
         ctx, st = self.ctx, self.ctx.stream
         N, OH, OW, _ = dy.shape
@@ -737,25 +773,24 @@ class Conv2D:
         dx = ctx.empty(N, H, W, self.cin)
         dx_amax = ctx.new_amax() if ctx.ns == 4 else None
         flops = 2.0 * N * OH * OW * 9 * self.cin * self.cout
-        ctx.up2_used[self.name + ":bwd"] = ctx.up2_used.get(self.name + ":bwd", 0) + 1
-        ctx.up2_skipped[self.name + ":bwd"] = 11.0 / 36.0
-        pk4 = self._packed_filter(4)
+        self._count_up2(":bwd", 11.0 / 36.0)
+        pk4 = self._packed_filter(BANK_UP2_BWD)
         if ctx.ns == 0:
             # strict fp32: the main launch, then its four border lines made exact in place from ONE d_up line per border (csrc/convf32.hip:
             # ladder_conv3x3_up2_bwd_borders -- 9 instead of 45 line-taps per axis; the strip path below cost 1.07 ms per iteration)
             wsp, wsn = ctx.ws(L.query("ladder_conv3x3_up2_bwd_borders_workspace_bytes", N, H, W, self.cout, self.cin))
             if gate is not None:        # (y of the layer below, its activation): dx *= act'(y) in the epilogue and in the border fix-up
                 gy, gact = gate
-                _timed(self._halo_kid(N, H, W, 4 * self.cout, self.cin), flops, "ladder_conv3x3_up2_bwd_data_gated_f32",
+                _timed(kid, flops, "ladder_conv3x3_up2_bwd_data_gated_f32",
                        (_p(dy), _p(pk4), _p(dx), _p(gy), L.ACT[gact], N, H, W, self.cout, self.cin, st), flops * 25.0 / 36.0)
                 L.call("ladder_conv3x3_up2_bwd_borders_gated", _p(dy), _p(self.ps.w[self.name + "/kernel"]), _p(dx), _p(gy), L.ACT[gact], N, H, W, self.cout,
                        self.cin, wsp, wsn, st)
                 return dx
-            _timed(self._halo_kid(N, H, W, 4 * self.cout, self.cin), flops, "ladder_conv3x3_up2_bwd_data_split",
+            _timed(kid, flops, "ladder_conv3x3_up2_bwd_data_split",
                    (_p(dy), None, _p(pk4), _p(dx), None, N, H, W, self.cout, self.cin, 0, st), flops * 25.0 / 36.0)
             L.call("ladder_conv3x3_up2_bwd_borders", _p(dy), _p(self.ps.w[self.name + "/kernel"]), _p(dx), N, H, W, self.cout, self.cin, wsp, wsn, st)
             return dx
-        pk = self._packed_filter(1)
+        pk = self._packed_filter(BANK_BWD)
         # border lines: dx row 0 = R(d_up[0] + d_up[1] / 2), row H-1 = R(d_up[2H-3] / 2 + d_up[2H-2] + d_up[2H-1]) with d_up = the plain
         # backward-data (needs dy rows 0..2 resp. 2H-4..2H-1) and R = the resize transpose ALONG the line; columns alike
         strips = []
@@ -798,163 +833,124 @@ class Conv2D:
             self.kept = None          # the one place the record of the forward is dropped
 
     def _backward(self, k, dy, need_dx, wgrad, act_done, gate_prev, lowres_dx, lowres_gate, proj_grad):
-        x, y, x_amax, pt, pl = k.x, k.y, k.x_amax, k.pt, k.pl
-        N, H, W, _ = x.shape
+        r, x, x_amax, ctx = k.route, k.x, k.x_amax, self.ctx
         lo = k.x_kind == "lowres"                         # x is the low-resolution tensor: the layer's input is its (never materialised) upsample
-        if lo:
-            H, W = k.factor * H, k.factor * W
         if proj_grad is not None:
             if not (wgrad and lo and k.form == "projected" and k.factor == 2):
                 raise RuntimeError("%s: the projection-gradient form of the backward combination does not apply" % self.name)
             return self._backward_proj(None, need_dx, wgrad, lowres_gate, proj_grad)
-        _, Ho, Wo, _ = y.shape
-        st = self.ctx.stream
         if self.act is not None and not act_done:
-            L.call("ladder_act_bwd", _p(dy), _p(y), _p(dy), dy.numel(), L.ACT[self.act], st)
+            L.call("ladder_act_bwd", _p(dy), _p(k.y), _p(dy), dy.numel(), L.ACT[self.act], ctx.stream)
         if lo and k.form == "projected":
             return self._backward_proj(dy, need_dx, wgrad, lowres_gate)
-        if (wgrad and self.k == 1 and self.stride == 1 and L.query("ladder_conv1x1_smallcout_eligible", N * H * W, self.cin, self.cout)):
-            # 1x1 to <= 4 channels over a wide map (the CelebA output conv): dx, dW and db from ONE pass over x
-            M = N * H * W
-            wsp, wsn = self.ctx.ws(L.query("ladder_conv1x1_smallcout_bwd_workspace_bytes", M, self.cin, self.cout))
-            dx = self.ctx.empty(N, H, W, self.cin) if need_dx else None
-            dx_amax = self.ctx.new_amax() if (need_dx and self.ctx.ns == 4) else None
-            L.call("ladder_conv1x1_smallcout_bwd_absmax", _p(x), _p(dy), _p(self.ps.w[self.name + "/kernel"]), _p(dx),
-                   _p(self.ps.g[self.name + "/kernel"]), _p(self.ps.g[self.name + "/bias"]) if self.bias_grad else None, M, self.cin,
-                   self.cout, L.ACT[gate_prev] if gate_prev else 0, wsp, wsn, _p(dx_amax), H * W, st)
-            if dx is not None:
-                self.ctx.set_amax(dx, dx_amax)
-            return dx
-        if self._as_dense(N * H * W):
-            M = N * H * W
-            if wgrad:
-                L.call("ladder_dense_bwd_weight_small" + self.ctx.sfx, _p(x), _p(dy), _p(self.ps.g[self.name + "/kernel"]),
-                       _p(self.ps.g[self.name + "/bias"]) if self.bias_grad else None, M, self.cin, self.cout, st)
-            dx = None
-            if need_dx:
-                dx = self.ctx.empty(N, H, W, self.cin)
-                L.call("ladder_dense_bwd_data_small" + self.ctx.sfx, _p(dy), _p(self.ps.w[self.name + "/kernel"]), _p(dx), M, self.cin, self.cout,
-                       _p(x) if gate_prev else None, L.ACT[gate_prev] if gate_prev else 0, st)
-            return dx
-        if wgrad and self._rgb(N, H, W, pt, pl):
-            xa, da = self.ctx.absmax(x), self.ctx.absmax(dy)
-            with self.ctx.side_or_main(x, dy, xa, da):
-                wsp, wsn = self.ctx.ws(L.query("ladder_conv_rgb_s2_bwd_filter_workspace_bytes", N, H, W, self.cout))
-                L.call("ladder_conv_rgb_s2_bwd_filter", _p(x), _p(xa), _p(dy), _p(da), _p(self.ps.g[self.name + "/kernel"]),
-                       _p(self.ps.g[self.name + "/bias"]) if self.bias_grad else None, N, H, W, self.cout, wsp, wsn, self.ctx.stream)
-            wgrad = False
-        if wgrad and self._rgb_fwd32(N, H, W, pt, pl):            # strict fp32: the fp32 filter-gradient kernel of the same layer
-            with self.ctx.side_or_main(x, dy):
-                wsp, wsn = self.ctx.ws(L.query("ladder_conv_rgb_s2_bwd_filter_workspace_bytes", N, H, W, self.cout))
-                L.call("ladder_conv_rgb_s2_bwd_filter_f32", _p(x), _p(dy), _p(self.ps.g[self.name + "/kernel"]),
-                       _p(self.ps.g[self.name + "/bias"]) if self.bias_grad else None, N, H, W, self.cout, wsp, wsn, self.ctx.stream)
-            wgrad = False
-        dy_amax = None
-        split_w = bool(wgrad and self._split_ok(N, H, W, self.cin, self.cout)
-                       and L.query("ladder_conv3x3_wgrad_split_eligible", N, H, W, self.cin, self.cout, self.ctx.ns))
-        if split_w and self.ctx.ns == 4 and x_amax is None:
-            x_amax = self.ctx.absmax(x)
-        split_d = bool(need_dx and not gate_prev and self._halo_ok(N, Ho, Wo, self.cout, self.cin))
-        if split_w or split_d:
-            dy_amax = self.ctx.absmax(dy)               # one pass serves the filter gradient and the backward-data call
-        if split_w:
-            # (on the side stream: the filter gradient is MFMA-bound and only the optimiser step needs it; the backward-data call below
-            # and the HBM-bound resize / norm backward kernels of the layers underneath run beside it)
-            with self.ctx.side_or_main(x, dy, x_amax, dy_amax):
-                wsp, wsn = self.ctx.ws(L.query("ladder_conv3x3_wgrad_split_workspace_bytes", N, H, W, self.cin, self.cout))
-                args = (_p(x), _p(x_amax), _p(dy), _p(dy_amax), _p(self.ps.g[self.name + "/kernel"]),
-                        _p(self.ps.g[self.name + "/bias"]) if self.bias_grad else None, N, H, W, self.cin, self.cout, self.ctx.ns, wsp, wsn,
-                        self.ctx.stream)
-                _timed(9120 + self.ctx.ns, 2.0 * N * H * W * 9 * self.cin * self.cout, "ladder_conv3x3_wgrad_split", args)
-        elif wgrad and self.ctx.ns and L.query("ladder_conv2d_bwd_filter_split_eligible", N, H, W, self.cin, Ho, Wo, self.cout, self.k,
-                                               self.k, self.stride, pt, pl):
-            if self.ctx.ns == 4:
-                if x_amax is None:
-                    x_amax = self.ctx.absmax(x)
-                dy_amax = self.ctx.absmax(dy)
-            ps_ = self._ps(Ho, Wo)
-            xpl, dpl = self.ctx.planes(x, ps_), self.ctx.planes(dy, ps_)          # (split on the main stream: backward-data reads dy's planes too)
-            with self.ctx.side_or_main(x, dy, xpl, dpl, x_amax, dy_amax):
-                wsp, wsn = self.ctx.ws(L.query("ladder_conv2d_bwd_filter_split_workspace_bytes", N, H, W, self.cin, Ho, Wo, self.cout, self.k,
-                                               self.k))
-                L.call("ladder_conv2d_bwd_filter_split", _p(xpl), _p(x_amax), _p(dpl), _p(dy_amax), _p(self.ps.g[self.name + "/kernel"]),
-                       _p(self.ps.g[self.name + "/bias"]) if self.bias_grad else None, N, H, W, self.cin, Ho, Wo, self.cout, self.k, self.k,
-                       self.stride, pt, pl, self.ctx.ns, wsp, wsn, self.ctx.stream)
-        elif (wgrad and self.ctx.ns == 0 and k.x_kind != "input" and self.ctx.up2 >= 2 and (H // 2) * (W // 2) >= UP2W_MIN_PIXELS
-              and L.query("ladder_conv3x3_up2_wgrad_eligible", N, H // 2, W // 2, self.cin, self.cout)):
-            # strict fp32, x = resize2x(x_lo): 25 instead of 36 tap tiles, read from the even sub-grid of the kept upsample (csrc/convf32.hip)
-            wsp, wsn = self.ctx.ws(L.query("ladder_conv3x3_up2_wgrad_workspace_bytes", N, H // 2, W // 2, self.cin, self.cout))
-            fl = 2.0 * N * H * W * 9 * self.cin * self.cout
-            self.ctx.up2_used[self.name + ":wgrad"] = self.ctx.up2_used.get(self.name + ":wgrad", 0) + 1
-            self.ctx.up2_skipped[self.name + ":wgrad"] = 11.0 / 36.0
-            _timed(9120, fl, "ladder_conv3x3_up2_wgrad",
-                   (_p(x), 0 if lo else 1, _p(dy), _p(self.ps.g[self.name + "/kernel"]), _p(self.ps.g[self.name + "/bias"]) if self.bias_grad else None, N, H // 2, W // 2,
-                    self.cin, self.cout, wsp, wsn, st), fl * 25.0 / 36.0)
-        elif wgrad:
-            # (a low-resolution x is [N, H/2, W/2, cin]: the generic kernel would read 4x past it.  plan_decoder plans a virtual upsample only where
-            # the branch above takes the filter gradient)
-            assert not lo, "%s: virtual upsample without the low-resolution filter gradient" % self.name
-            nb = L.query("ladder_conv2d_bwd_filter_workspace_bytes", N, H, W, self.cin, Ho, Wo, self.cout, self.k, self.k)
-            wsp, wsn = self.ctx.ws(nb)
-            wargs = (_p(x), _p(dy), _p(self.ps.g[self.name + "/kernel"]), _p(self.ps.g[self.name + "/bias"]) if self.bias_grad else None,
-                     N, H, W, self.cin, Ho, Wo, self.cout, self.k, self.k, self.stride, pt, pl, wsp, wsn, st)
-            if PROF is not None and L.query("ladder_conv2d_bwd_filter_kernel_id", N, H, W, self.cin, Ho, Wo, self.cout, self.k, self.k,
-                                            self.stride, pt, pl) == 9128:
-                s_, e_ = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                s_.record()
-                L.call("ladder_conv2d_bwd_filter", *wargs)         # (+ its fixed-order split reduction: counted with the kernel)
-                e_.record()
-                PROF.add(9128, s_, e_, 2.0 * N * Ho * Wo * self.k * self.k * self.cin * self.cout)
-            else:
-                L.call("ladder_conv2d_bwd_filter", *wargs)
-        dx = None
-        if lowres_dx and not split_d:
-            raise RuntimeError("%s: the low-resolution backward-data was requested for a call the split halo kernels do not take" % self.name)
-        if split_d and lowres_dx:
-            dx = self._dx_lowres(dy, dy_amax, lowres_gate)
-        elif split_d:
-            dx = self.ctx.empty(N, H, W, self.cin)
-            dx_amax = self.ctx.new_amax() if self.ctx.ns == 4 else None
-            args = (_p(dy), _p(dy_amax), _p(self._packed_filter(1)), None, _p(dx), _p(dx_amax), N, H, W, self.cout, self.cin, 0,
-                    self.ctx.ns, st)
-            self.ctx.set_amax(dx, dx_amax)
-            _timed(self._halo_kid(N, H, W, self.cout, self.cin), 2.0 * N * H * W * 9 * self.cin * self.cout, "ladder_conv3x3_split", args)
-        elif (need_dx and self.ctx.ns in (0, 4) and not gate_prev and self.stride == 2 and not (self.ctx.ns == 0 and halo_disabled())
-              and (L.query("ladder_conv3x3_s2_bwd_data_split_eligible", N, H, W, self.cin, Ho, Wo, self.cout, self.k, self.k, self.stride,
-                           pt, pl) or (self.ctx.ns == 0 and self.k == 3 and pt == 0 and pl == 0 and
-                                                 L.query("ladder_conv3x3_s2_bwd_data_f32_eligible", N, H, W, self.cin, Ho, Wo, self.cout)))):
-            # 3x3 / stride 2 over a map whose gradient is halo-kernel sized (enc.conv1): the four output-parity classes in ONE launch
-            if dy_amax is None:
-                dy_amax = self.ctx.absmax(dy)
-            dx = self.ctx.empty(N, H, W, self.cin)
-            dx_amax = self.ctx.new_amax() if self.ctx.ns == 4 else None
-            args = (_p(dy), _p(dy_amax), _p(self._packed_filter(2)), _p(dx), _p(dx_amax), N, H, W, self.cin, Ho, Wo, self.cout, self.ctx.ns, st)
-            self.ctx.set_amax(dx, dx_amax)
-            _timed(self._halo_kid(N, Ho, Wo, self.cout, 4 * self.cin, self.cin), 2.0 * N * Ho * Wo * 9 * self.cin * self.cout, "ladder_conv3x3_s2_bwd_data_split", args)
-        elif need_dx and self.ctx.ns and L.query("ladder_conv2d_bwd_data_split_eligible", N, H, W, self.cin, Ho, Wo, self.cout, self.k,
-                                                 self.k, self.stride, pt, pl, 1 if gate_prev else 0):
-            geo = (N, H, W, self.cin, Ho, Wo, self.cout, self.k, self.k, self.stride, pt, pl)
-            if dy_amax is None:
-                dy_amax = self.ctx.absmax(dy)
-            wsp, wsn = self.ctx.ws(L.query("ladder_conv2d_bwd_data_split_workspace_bytes", *geo))
-            dx = self.ctx.empty(N, H, W, self.cin)
-            L.call("ladder_conv2d_bwd_data_split", _p(self.ctx.planes(dy, self._ps(Ho, Wo))), _p(dy_amax), _p(self._packed_filter(1)), _p(dx), *geo,
-                   _p(x) if gate_prev else None, L.ACT[gate_prev] if gate_prev else 0, self.ctx.ns, wsp, wsn, st)
-        elif need_dx:
-            if self.ctx.ns == 0 and self.cout % 16 == 0 and self.k == 3:
-                wT = self._packed_filter(1)               # flipped / transposed fp32 bank, re-packed with all others in one launch per step
-            else:
-                w = self.ps.w[self.name + "/kernel"]
-                wT = self.ctx.empty(w.numel())
-                L.call("ladder_filter_flip_transpose", _p(w), _p(wT), self.k, self.k, self.cin, self.cout, st)
-            dx = self.ctx.empty(N, H, W, self.cin)
-            _igemm(self.ctx, "ladder_conv2d_bwd_data", N * H * W, self.cout, self.cin, self.k * self.k * self.cout,
-                   _p(dy), _p(wT), _p(dx), N, H, W, self.cin, Ho, Wo, self.cout, self.k, self.k,
-                   self.stride, pt, pl, _p(x) if gate_prev else None, L.ACT[gate_prev] if gate_prev else 0,
-                   # a strided backward-data call is several parity-class launches: not attributed by the profiler
-                   conv=(N, Ho, Wo, self.cout, H, W, self.cin, self.k, self.k, 1, 1, self.k - 1 - pt, self.k - 1 - pl)
-                   if self.stride == 1 else "skip")
+        if wgrad and r.fused_bwd is not None:
+            return r.fused_bwd.run(r, x, dy, need_dx, gate_prev)
+        wg, dl = r.wgrad if wgrad else None, (r.dx_gated if gate_prev else r.dx) if need_dx else None
+        halo_w, halo_d = bool(wg and wg.fn == "ladder_conv3x3_wgrad_split"), bool(dl and dl.fn == "ladder_conv3x3_split")
+        if halo_w and x_amax is None:
+            x_amax = ctx.absmax(x)                      # (a record only under f16x3, else None)
+        dy_amax = ctx.absmax(dy) if (halo_w or halo_d) else None        # one pass serves the filter gradient and the backward-data call
+        if wg is not None:
+            wg.run(r, x, dy, x_amax, dy_amax, lo)
+        if lowres_dx:
+            if not halo_d:
+                raise RuntimeError("%s: the low-resolution backward-data was requested for a call the split halo kernels do not take" % self.name)
+            return self._dx_lowres(dy, dy_amax, r.up2_kids[1], lowres_gate)
+        if dl is None:
+            return None
+        dx = ctx.empty(r.N, r.H, r.W, self.cin)
+        dl.run(r, dl, x, dy, dx, dy_amax, gate_prev)
         return dx
+
+    # -- one launch function per backward route (filter gradient: r.wgrad; backward-data: `dl` = r.dx or r.dx_gated, `gate` = the activation name)
+    def _bwd_smallcout(self, r, x, dy, need_dx, gate):
+        ctx, M = self.ctx, r.N * r.H * r.W
+        wsp, wsn = ctx.ws(r.fused_bwd.ws)
+        dx = ctx.empty(r.N, r.H, r.W, self.cin) if need_dx else None
+        dx_amax = ctx.new_amax() if (need_dx and ctx.ns == 4) else None
+        L.call(r.fused_bwd.fn, _p(x), _p(dy), self._wb()[0], _p(dx), *self._grads(), M, self.cin, self.cout, L.ACT[gate] if gate else 0, wsp, wsn,
+               _p(dx_amax), r.H * r.W, ctx.stream)
+        if dx is not None:
+            ctx.set_amax(dx, dx_amax)
+        return dx
+
+    def _wg_dense(self, r, x, dy, x_amax, dy_amax, lo):
+        L.call(r.wgrad.fn, _p(x), _p(dy), *self._grads(), r.N * r.H * r.W, self.cin, self.cout, self.ctx.stream)
+
+    def _wg_rgb(self, r, x, dy, x_amax, dy_amax, lo):
+        ctx = self.ctx
+        xa, da = (ctx.absmax(x), ctx.absmax(dy)) if ctx.ns else (None, None)
+        with ctx.side_or_main(x, dy, xa, da):
+            wsp, wsn = ctx.ws(r.wgrad.ws)
+            ops = (_p(x), _p(xa), _p(dy), _p(da)) if ctx.ns else (_p(x), _p(dy))
+            L.call(r.wgrad.fn, *ops, *self._grads(), r.N, r.H, r.W, self.cout, wsp, wsn, ctx.stream)
+
+    def _wg_halo_split(self, r, x, dy, x_amax, dy_amax, lo):
+        # (on the side stream: the filter gradient is MFMA-bound and only the optimiser step needs it; the backward-data call
+        # and the HBM-bound resize / norm backward kernels of the layers underneath run beside it)
+        ctx = self.ctx
+        with ctx.side_or_main(x, dy, x_amax, dy_amax):
+            wsp, wsn = ctx.ws(r.wgrad.ws)
+            _timed(r.wgrad.kid, r.flops, r.wgrad.fn, (_p(x), _p(x_amax), _p(dy), _p(dy_amax), *self._grads(), r.N, r.H, r.W, self.cin, self.cout,
+                                                            ctx.ns, wsp, wsn, ctx.stream))
+
+    def _wg_gather_split(self, r, x, dy, x_amax, dy_amax, lo):
+        ctx = self.ctx
+        x_amax, dy_amax = ctx.absmax(x) if x_amax is None else x_amax, ctx.absmax(dy)
+        ps_ = self._ps(r.Ho, r.Wo)
+        xpl, dpl = ctx.planes(x, ps_), ctx.planes(dy, ps_)          # (split on the main stream: backward-data reads dy's planes too)
+        with ctx.side_or_main(x, dy, xpl, dpl, x_amax, dy_amax):
+            wsp, wsn = ctx.ws(r.wgrad.ws)
+            L.call(r.wgrad.fn, _p(xpl), _p(x_amax), _p(dpl), _p(dy_amax), *self._grads(), *r.geo, ctx.ns, wsp, wsn, ctx.stream)
+
+    def _wg_up2(self, r, x, dy, x_amax, dy_amax, lo):
+        ctx, fl = self.ctx, r.flops
+        wsp, wsn = ctx.ws(r.wgrad.ws)
+        self._count_up2(":wgrad", 11.0 / 36.0)
+        _timed(r.wgrad.kid, fl, r.wgrad.fn, (_p(x), 0 if lo else 1, _p(dy), *self._grads(), r.N, r.H // 2, r.W // 2, self.cin, self.cout, wsp, wsn,
+                                            ctx.stream), fl * 25.0 / 36.0)
+
+    def _wg_gather(self, r, x, dy, x_amax, dy_amax, lo):
+        # (a low-resolution x is [N, H/2, W/2, cin]: the generic kernel would read 4x past it.  plan_decoder plans a virtual upsample only where
+        # ladder_conv3x3_up2_wgrad takes the filter gradient)
+        assert not lo, "%s: virtual upsample without the low-resolution filter gradient" % self.name
+        wsp, wsn = self.ctx.ws(r.wgrad.ws)
+        _timed(r.wgrad.kid, r.flops, r.wgrad.fn, (_p(x), _p(dy), *self._grads(), *r.geo, wsp, wsn, self.ctx.stream))    # (+ its fixed-order split reduction)
+
+    def _dx_dense(self, r, dl, x, dy, dx, dy_amax, gate):
+        gate_args = (_p(x), L.ACT[gate]) if gate else (None, 0)
+        L.call(dl.fn, _p(dy), self._wb()[0], _p(dx), r.N * r.H * r.W, self.cin, self.cout, *gate_args, self.ctx.stream)
+
+    def _dx_halo(self, r, dl, x, dy, dx, dy_amax, gate):
+        ctx = self.ctx
+        dx_amax = ctx.new_amax() if ctx.ns == 4 else None
+        ctx.set_amax(dx, dx_amax)
+        _timed(dl.kid, r.flops, dl.fn,
+               (_p(dy), _p(dy_amax), _p(self._packed_filter(BANK_BWD)), None, _p(dx), _p(dx_amax), r.N, r.H, r.W, self.cout, self.cin, 0, ctx.ns, ctx.stream))
+
+    def _dx_s2(self, r, dl, x, dy, dx, dy_amax, gate):
+        ctx = self.ctx
+        dy_amax = ctx.absmax(dy)
+        dx_amax = ctx.new_amax() if ctx.ns == 4 else None
+        ctx.set_amax(dx, dx_amax)
+        _timed(dl.kid, 2.0 * r.N * r.Ho * r.Wo * 9 * self.cin * self.cout, dl.fn,
+               (_p(dy), _p(dy_amax), _p(self._packed_filter(BANK_S2_BWD)), _p(dx), _p(dx_amax), r.N, r.H, r.W, self.cin, r.Ho, r.Wo, self.cout, ctx.ns, ctx.stream))
+
+    def _dx_gather_split(self, r, dl, x, dy, dx, dy_amax, gate):
+        ctx = self.ctx
+        dy_amax = ctx.absmax(dy)
+        wsp, wsn = ctx.ws(dl.ws)
+        L.call(dl.fn, _p(ctx.planes(dy, self._ps(r.Ho, r.Wo))), _p(dy_amax), _p(self._packed_filter(BANK_BWD)), _p(dx), *r.geo,
+               _p(x) if gate else None, L.ACT[gate] if gate else 0, ctx.ns, wsp, wsn, ctx.stream)
+
+    def _dx_gather(self, r, dl, x, dy, dx, dy_amax, gate):
+        ctx = self.ctx
+        wT = self._packed_filter(dl.bank) if dl.bank is not None else ctx.empty(self.k * self.k * self.cin * self.cout)
+        if dl.bank is None:
+            L.call("ladder_filter_flip_transpose", self._wb()[0], _p(wT), self.k, self.k, self.cin, self.cout, ctx.stream)
+        wsp, wsn = ctx.ws(dl.ws)
+        _timed(dl.kid, 2.0 * r.N * r.H * r.W * self.k * self.k * self.cin * self.cout, dl.fn,
+               (_p(dy), _p(wT), _p(dx), *r.geo, _p(x) if gate else None, L.ACT[gate] if gate else 0, wsp, wsn, ctx.stream))
 
 
 # How one block of the CelebA decoder (resize in front -> 3x3 conv -> [instance norm] -> resize behind) runs, forward and backward:
@@ -1046,7 +1042,7 @@ def plan_decoder(cache, ctx, up0, blocks, conv_out, shape):
         last = i == n - 1 and norm is None and (rs is None or (rs.oh, rs.ow) == (h, w))
         if resize in (None, "materialise"):
             form, one_launch = "plain", False
-            proj = "rides" if (last and conv.cout <= 128 and conv._is_projection(conv_out) and conv._halo_ok(N, h, w, conv.cin, conv.cout)) else None
+            proj = "rides" if (last and conv.cout <= 128 and conv._is_projection(conv_out) and conv.route((N, h, w, conv.cin)).halo) else None
         else:
             form = "projected" if proj_ok(conv, lo_hw[0], lo_hw[1], f) else "tapfold"
             one_launch = bool(form == "projected" and f == 2 and ctx.fuse_fwd and L.query(
@@ -1093,6 +1089,13 @@ class Dense:
     def __init__(self, ctx, ps, name, cin, cout, act=None):
         self.ctx, self.ps, self.name, self.cin, self.cout, self.act = ctx, ps, name, cin, cout, act
 
+    _plan = staticmethod(functools.lru_cache(maxsize=None)(_igemm_plan))      # (no switch enters the plan of a dense GEMM)
+
+    def _igemm(self, name, M, K, Cout, *args):
+        """Implicit-GEMM call [M, K] . [K, Cout] (dense fwd / bwd_data): appends the split-K workspace and the stream."""
+        nb, kid = self._plan(M, K, Cout, K)
+        _timed(kid, 2.0 * M * K * Cout, name, args + self.ctx.ws(nb) + (self.ctx.stream,))
+
     def _small(self, M):
         """Batch-sized layer: the one-launch kernels of csrc/densesplit.hip (strict fp32 MFMA when matmul_precision is "f32", else bf16x6)."""
         return bool(L.query("ladder_dense_small_eligible", M, self.cin, self.cout))
@@ -1103,11 +1106,9 @@ class Dense:
         if self._small(M):
             L.call("ladder_dense_fwd_small" + self.ctx.sfx, _p(x), _p(self.ps.w[self.name + "/kernel"]), _p(self.ps.w[self.name + "/bias"]), _p(y),
                    M, self.cin, self.cout, L.ACT[self.act], self.ctx.stream)
-            self.x, self.y = x, y
-            return y
-        _igemm(self.ctx, "ladder_dense_fwd", M, self.cin, self.cout, self.cin,
-               _p(x), _p(self.ps.w[self.name + "/kernel"]), _p(self.ps.w[self.name + "/bias"]), _p(y),
-               M, self.cin, self.cout, L.ACT[self.act])
+        else:
+            self._igemm("ladder_dense_fwd", M, self.cin, self.cout, _p(x), _p(self.ps.w[self.name + "/kernel"]), _p(self.ps.w[self.name + "/bias"]), _p(y),
+                        M, self.cin, self.cout, L.ACT[self.act])
         self.x, self.y = x, y
         return y
 
@@ -1145,8 +1146,8 @@ class Dense:
             wT = self.ctx.empty(w.numel())
             L.call("ladder_filter_flip_transpose", _p(w), _p(wT), 1, 1, self.cin, self.cout, st)
             dx = self.ctx.empty(M, self.cin)
-            _igemm(self.ctx, "ladder_dense_bwd_data", M, self.cout, self.cin, self.cout, _p(dy), _p(wT), _p(dx), M, self.cin, self.cout,
-                   _p(x) if gate_prev else None, L.ACT[gate_prev] if gate_prev else 0)
+            self._igemm("ladder_dense_bwd_data", M, self.cout, self.cin, _p(dy), _p(wT), _p(dx), M, self.cin, self.cout,
+                        _p(x) if gate_prev else None, L.ACT[gate_prev] if gate_prev else 0)
         self.x = self.y = None
         return dx
 
