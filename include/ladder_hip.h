@@ -743,6 +743,34 @@ int ladder_vbgmm_shard_mstep(const double* stats, const double* moments, int K, 
                              double mean_prec_prior, double reg_covar, double tol, int max_iter, int it, float* weights, float* means,
                              float* covs, ladder_stream_t stream);
 
+/* ---------------------------------------------------------------- N15: ancestral sampling of the priors + bulk image generation
+ * A sampler is a prepared parameter buffer of ladder_mixture_sample_param_bytes(K, R) bytes (0 for K < 1 or R outside 1..64; layout and
+ * the Philox counter layout: head of csrc/sample.hip):  int32 status | K | R | 0,  float64 cdf[K],  fp32 means [K,R],  fp32 Cholesky
+ * factors [K, R(R+1)/2] (float64 factorisation, rounded; lower-triangular, row-major).  cdf_k = (w'_0 + .. + w'_k) / sum w' with
+ * w'_k = max((double)w_k, 0), both sums sequential in index order.  status = -1: usable; k >= 0: first component whose factorisation met
+ * a non-positive pivot; -2: the weights have no positive sum -- the caller reads it once after prepare and must not sample otherwise.
+ * ladder_mixture_sample_prepare: the full-covariance mixtures that `GM_prior_training.sample(n)` / `GM_prior_final.sample(n)` draw from
+ * (codes/base.py:1065-1122, priors "GMM" and "ours"; also tfd.Mixture(...).sample of demo/demo_tools.py:118-120). */
+size_t ladder_mixture_sample_param_bytes(int K, int R);
+int ladder_mixture_sample_prepare(const float* weights, const float* means, const float* covs, int K, int R, void* params,
+                                  ladder_stream_t stream);
+/* The same layout for K equally weighted DIAGONAL components (comp_mean, comp_sd [K,R]): `psedeu_prior.sample(n)` of the VampPrior
+ * (codes/base.py:1065-1122 at :1120, the mixture of :241-254); K = 1, mean 0, sd 1 is the N(0, I_R) that
+ * `multivariate_normal(...).rvs(n)` draws for "standard_gaussian" (on z) and "hierarchical" (on t) in the same function. */
+int ladder_mixture_sample_prepare_diag(const float* comp_mean, const float* comp_sd, int K, int R, void* params, ladder_stream_t stream);
+/* Samples first .. first+n-1 of the prepared mixture (codes/base.py:1065-1122; demo/demo_tools.py:118-120): component k = number of
+ * cdf_j <= (double)u_i clamped to K-1, out[i-first, :] = m_k + L_k eps_i as an fp32 FMA chain (j ascending from m_k), comp[i-first] = k
+ * (comp may be NULL).  u [n] and eps [n,R] are both given, or both NULL: then they come from Philox4x32-10 (the generator of
+ * ladder_randn) and the draws of sample index i depend on (seed, offset, i) only -- not on n, first or the launch grid.
+ * first >= 0, first + n <= 2^56.  R <= 8: one thread per sample, parameters in LDS; R > 8: a sample's rows over the lanes of a wavefront.
+ * K and R must be those of prepare: the kernel checks the buffer's header on the device, and a buffer whose status is not -1 or that was
+ * prepared for another (K, R) gives out = NaN and comp = -1 for every sample (nothing is read through a wrong layout). */
+int ladder_mixture_sample(const void* params, int K, int R, int n, int64_t first, const float* u, const float* eps, uint64_t seed,
+                          uint64_t offset, float* out, int* comp, ladder_stream_t stream);
+/* out[i] = (uint8) rint(255 * min(max(x[i], 0), 1)), ties to even, NaN -> 0: the generated images as the bytes an FID pipeline reads
+ * (the `sampled_images` array of utils.py:134-138 after its clip to [0, 1]); 16-byte loads, 16-byte packed stores, any n. */
+int ladder_images_to_u8(const float* x, uint8_t* out, size_t n, ladder_stream_t stream);
+
 /* ---------------------------------------------------------------- helpers */
 /* HOST function (no device work): CRC-32C (Castagnoli) of host memory, crc = 0 to start, chainable.  Used by the
  * tf.train.Saver checkpoint-v2 reader/writer (codes/base.py:37-85: saver_ae / saver_prior) for block and tensor checksums. */

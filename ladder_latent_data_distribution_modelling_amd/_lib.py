@@ -209,6 +209,11 @@ PROTOTYPES = {
     "ladder_conv2d_bwd_filter_split_eligible": (_i, [_i] * 12),
     "ladder_conv2d_bwd_filter_split_workspace_bytes": (_z, [_i] * 9),
     "ladder_conv2d_bwd_filter_split": (_i, [_p, _p, _p, _p, _p, _p] + [_i] * 13 + [_p, _z, _p]),
+    "ladder_mixture_sample_param_bytes": (_z, [_i, _i]),
+    "ladder_mixture_sample_prepare": (_i, [_p, _p, _p, _i, _i, _p, _p]),
+    "ladder_mixture_sample_prepare_diag": (_i, [_p, _p, _i, _i, _p, _p]),
+    "ladder_mixture_sample": (_i, [_p, _i, _i, _i, C.c_int64, _p, _p, _u64, _u64, _p, _p, _p]),
+    "ladder_images_to_u8": (_i, [_p, _p, _z, _p]),
 }
 
 _lib = None

@@ -10,6 +10,10 @@ import math
 import numpy as np
 
 
+# the priors the reference can generate from (codes/base.py:1065-1122), i.e. the values of config["prior"]
+PRIOR_METHODS = ("standard_gaussian", "GMM", "ours", "hierarchical", "vampPrior")
+
+
 def same_pad(n_in, k, s):
     """TF 'SAME': out = ceil(in/s); pad_total = max((out-1)s + k - in, 0); before = total//2."""
     out = -(-n_in // s)

@@ -418,3 +418,45 @@ class BaseTrain_joint(BaseTrain):
             code = rng.standard_normal((n, int(cfg["code_size"])))
         self.generated_samples = eng.decode(code).cpu().numpy()
         return self.generated_samples
+
+    # ------------------------------------------------------------------ generation on the device (base.py:1065-1122)
+    def _prior_sampler(self, mode, method, seed):
+        """The engine's device sampler for `method`, fed the mixture that `mode` names: "crude-GM" -> the per-epoch fit (gm_params,
+        the reference's GM_prior_training), any other mode -> the accurate fit (gm_final_params, GM_prior_final).  Sampled as fitted: no
+        covariance jitter, like sklearn's .sample()."""
+        method = method or self.config["prior"]
+        mixture = None
+        if method in ("GMM", "ours"):
+            mixture = self.gm_params if mode == "crude-GM" else getattr(self, "gm_final_params", None)
+            if mixture is None:
+                raise RuntimeError("generation with method %r, mode %r needs the %s mixture, which has not been fitted yet (fit_GMM_VI(mode=%r))"
+                                   % (method, mode, "per-epoch" if mode == "crude-GM" else "accurate", "fast" if mode == "crude-GM" else "accurate"))
+        sampler = self.engine.prior_sampler(method, mixture, seed=self.cur_epoch if seed is None else int(seed))
+        if seed is None:            # fresh draws on every call, as the reference's: each default-seeded call takes the next Philox offset
+            self._generation_calls = getattr(self, "_generation_calls", 0) + 1
+            sampler.offset = self._generation_calls
+        return method, sampler
+
+    def _samples_filename(self, mode, method):
+        if method in ("GMM", "ours"):
+            return self.config["result_dir"] + "generated_samples_prior_{}_{}.pdf".format(self.cur_epoch, mode)
+        return self.config["result_dir"] + "generated_samples_prior_{}.pdf".format(self.cur_epoch)
+
+    def generate_samples_from_prior_by_method(self, mode="crude-GM", n_sample=10, method=None, noise=None, seed=None):
+        """codes/base.py:1065-1122: n_sample^2 codes drawn from the prior `method` (default: the configured one) -> (samples_code_prior
+        float32 [n_sample^2, code_size], filename) with the reference's file-name strings.  The five branches draw on the device:
+        z ~ N(0, I) | z ~ mixture | t ~ mixture -> inner decoder | t ~ N(0, I) -> inner decoder | z ~ the pseudo-input mixture.
+        `noise` = {"u": [n], "eps": [n, R]} feeds the component and normal draws; `seed` seeds the sampler's own stream and makes the call
+        reproducible.  Without one, the seed is the epoch and every call (of this method or generate_images) takes the next offset of that
+        stream, so two calls return different samples, as in the reference."""
+        self.flush()
+        method, sampler = self._prior_sampler(mode, method, seed)
+        code, _, _ = sampler.sample(int(n_sample) ** 2, noise=noise)
+        return code.cpu().numpy(), self._samples_filename(mode, method)
+
+    def generate_images(self, n, mode="accurate-GM", method=None, chunk=128, as_uint8=False, seed=None):
+        """n images decoded from prior samples, [n, H, W, C] on the host -- the `sampled_images` array the reference's FID evaluation reads
+        (utils.py:134-138); float32 raw decoder output (the clip to [0, 1] is the consumer's, as in the reference) or uint8 with `as_uint8`."""
+        self.flush()
+        _, sampler = self._prior_sampler(mode, method, seed)
+        return self.engine.generate(n, sampler, chunk=chunk, as_uint8=as_uint8)

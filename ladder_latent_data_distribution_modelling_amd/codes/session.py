@@ -55,11 +55,31 @@ class Deferred:
         self.thunk = thunk
 
 
+class PseudoInputPrior:
+    """`model.psedeu_prior` of a VampPrior model (sic; reference base.py:241-254): the equally weighted mixture of the encoder's diagonal
+    posteriors at the trainable pseudo-inputs.  `sample(n)` is deferred like a TFP method in graph mode, so the reference's
+    `sess.run(self.model.psedeu_prior.sample(n_sample ** 2))` (base.py:1120) runs verbatim; the components are those of the weights at
+    the time `sess.run` evaluates it, the draw happens on the device (engine.prior_sampler)."""
+
+    def __init__(self, model):
+        self._model = weakref.ref(model)
+
+    def sample(self, n, seed=None, noise=None):
+        def thunk():
+            eng = self._model().engine
+            self._draws = getattr(self, "_draws", 0) + 1           # fresh samples on every run, like a TF sampling op
+            sampler = eng.prior_sampler("vampPrior", seed=self._draws if seed is None else int(seed))
+            return sampler.sample(int(n), noise=noise)[0].cpu().numpy()
+        return Deferred(thunk)
+
+
 def attach_handles(model):
     """Give `model` the attribute surface of SURVEY Appendix E2."""
     for names, kind in ((PLACEHOLDERS, "placeholder"), (TENSORS, "tensor"), (SCALARS, "scalar"), (TRAIN_OPS, "op")):
         for n in names:
             setattr(model, n, Handle(n, kind, model))
+    if model.config["prior"] == "vampPrior":
+        model.psedeu_prior = PseudoInputPrior(model)
 
 
 class Session:

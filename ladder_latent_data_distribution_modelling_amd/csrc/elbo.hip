@@ -4,6 +4,7 @@
 // fused clip+Adam, and a Philox normal generator.
 #include <mutex>
 #include "common.h"
+#include "philox.h"
 
 namespace {
 
@@ -853,37 +854,16 @@ __global__ void u64_add_kernel(unsigned long long* __restrict__ p, unsigned long
   if (threadIdx.x == 0 && blockIdx.x == 0) atomicAdd(p, inc);      // (atomic: two streams may advance the noise position concurrently)
 }
 
-// ----------------------------------------------------------------------------- Philox4x32-10 normals
-__device__ __forceinline__ void philox_round(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
-  const uint64_t p0 = (uint64_t)0xD2511F53u * c[0], p1 = (uint64_t)0xCD9E8D57u * c[2];
-  const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0, n1 = (uint32_t)p1;
-  const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1, n3 = (uint32_t)p0;
-  c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
-}
+// ----------------------------------------------------------------------------- Philox4x32-10 normals (generator: philox.h)
 __global__ void randn_kernel(float* __restrict__ out, size_t n, uint64_t seed, uint64_t offset,
                              const unsigned long long* __restrict__ offset_base) {
   const size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x;   // 4 normals per thread
   if (q * 4 >= n) return;
   if (offset_base != nullptr) offset += *offset_base;                // device-resident stream position (graph replay)
   uint32_t c[4] = {(uint32_t)q, (uint32_t)(q >> 32), (uint32_t)offset, (uint32_t)(offset >> 32)};
-  uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    philox_round(c, k0, k1);
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
+  philox4x32_10(c, seed);
   float o[4];
-#pragma unroll
-  for (int p = 0; p < 2; ++p) {
-    const float u1 = ((float)(c[2 * p] >> 8) + 0.5f) * (1.0f / 16777216.0f);
-    const float u2 = ((float)(c[2 * p + 1] >> 8) + 0.5f) * (1.0f / 16777216.0f);
-    const float rr = sqrtf(-2.f * logf(u1));
-    float sn, cs;
-    sincosf(6.28318530717958647692f * u2, &sn, &cs);
-    o[2 * p] = rr * cs;
-    o[2 * p + 1] = rr * sn;
-  }
+  philox_box_muller4(c, o);
   for (int j = 0; j < 4; ++j)
     if (q * 4 + j < n) out[q * 4 + j] = o[j];
 }

@@ -269,6 +269,38 @@ DEC_SCALARS = frozenset(("sigma", "mean_pixel_error", "l1_reconstruction_error",
                          "sigma_regularisor", "elbo", "loss_ae"))
 
 
+PRIOR_METHODS = arch.PRIOR_METHODS
+
+
+class PriorSampler:
+    """Handle of LadderEngine.prior_sampler(): ancestral samples of one prior, drawn on the device (reference codes/base.py:1065-1122).
+
+    Owns the prepared parameter buffer of csrc/sample.hip.  Its Philox stream is its own -- (seed, offset) of this object, never the
+    engine's training noise position -- and sample index i draws the same values whatever the chunking: sample(n, first) returns samples
+    first .. first+n-1 of ONE stream, so a bulk run may be cut into chunks (or, later, sharded over ranks) freely."""
+
+    def __init__(self, eng, method, K, R, params, seed=0, offset=0):
+        self.eng, self.method, self.K, self.R, self.params = eng, method, int(K), int(R), params
+        self.seed, self.offset = int(seed), int(offset)
+        self.to_code = method in ("ours", "hierarchical")      # the draw is t: the code is the inner decoder's output (base.py:1088-1118)
+
+    def sample(self, n, first=0, noise=None, seed=None):
+        """-> (code [n, Z], latent [n, R or Z], comp [n] int32), device tensors.  `noise` = {"u": [n], "eps": [n, R]} feeds the draws."""
+        eng, n = self.eng, int(n)
+        ctx = eng.ctx
+        latent = ctx.empty(n, self.R)
+        comp = torch.empty(n, dtype=torch.int32, device=ctx.device)
+        u = eps = None
+        if noise is not None:
+            u, eps = eng._dev(noise["u"]).reshape(-1), eng._dev(noise["eps"])
+            if tuple(u.shape) != (n,) or tuple(eps.shape) != (n, self.R):
+                raise ValueError("noise: u %s, eps %s; expected (%d,) and (%d, %d)" % (tuple(u.shape), tuple(eps.shape), n, n, self.R))
+        L.call("ladder_mixture_sample", _p(self.params), self.K, self.R, n, int(first), _p(u), _p(eps),
+               self.seed if seed is None else int(seed), self.offset, _p(latent), _p(comp), ctx.stream)
+        code = eng.decode_representation(latent) if self.to_code else latent
+        return code, latent, comp
+
+
 # ------------------------------------------------------------------------------------------ engine
 class LadderEngine:
     """Owns parameters + optimiser state and evaluates the reference's four per-minibatch runs.
@@ -858,6 +890,115 @@ class LadderEngine:
         """decoded_code given representation_input (base.py:171-186)."""
         self._join_aux()
         return self.inner.decode(self._dev(t))
+
+    def prior_sampler(self, method=None, mixture=None, seed=0):
+        """Device sampler of the prior `method` (default: the configured one) for generation (reference codes/base.py:1065-1122):
+        "standard_gaussian" N(0, I_Z) on z; "hierarchical" N(0, I_R) on t; "GMM" / "ours" the full-covariance mixture `mixture` =
+        (weights, means, covs) on z / on t; "vampPrior" the K equally weighted diagonal components the encoder gives at the pseudo-inputs
+        NOW (base.py:241-254; a later optimiser step needs a new sampler).  Raises ValueError for a mixture that cannot be sampled."""
+        method = method or self.cfg["prior"]
+        if method not in PRIOR_METHODS:
+            raise ValueError("unknown prior %r: expected one of %s" % (method, list(PRIOR_METHODS)))
+        if method in ("ours", "hierarchical") and self.inner is None:
+            raise ValueError("method %r needs the inner VAE; this model's prior is %r" % (method, self.cfg["prior"]))
+        self._join_aux()
+        ctx, st = self.ctx, self.ctx.stream
+        keep = None
+        if method in ("GMM", "ours"):
+            if mixture is None:
+                raise ValueError("method %r samples a fitted mixture: pass mixture=(weights, means, covs)" % method)
+            w, m, c = (self._dev(a) for a in mixture)
+            K, R = int(w.numel()), int(self.Z if method == "GMM" else self.cfg["representation_size"])
+            if tuple(m.shape) != (K, R) or tuple(c.shape) != (K, R, R):
+                raise ValueError("mixture shapes %s %s %s do not fit K = %d, R = %d" % (tuple(w.shape), tuple(m.shape), tuple(c.shape), K, R))
+            prep, keep = "ladder_mixture_sample_prepare", (w, m, c)
+        elif method == "vampPrior":
+            if not self.vamp:
+                raise ValueError("method 'vampPrior' needs the pseudo-inputs; this model's prior is %r" % self.cfg["prior"])
+            K, R = self.K, self.Z
+            mu_p, sdraw_p = self.encoder_p.forward(self.ps.w["prior/Variable"])          # as _vamp_term forms the components
+            sd_p, scratch = ctx.empty(K, R), ctx.zeros(4)
+            L.call("ladder_latent_fwd", _p(mu_p), _p(sdraw_p), _p(ctx.zeros(K, R)), self.lvp, None, _p(sd_p), _p(scratch), _p(scratch[1:]), None,
+                   K, R, st)
+            prep, keep = "ladder_mixture_sample_prepare_diag", (mu_p, sd_p)
+        else:
+            K, R = 1, int(self.Z if method == "standard_gaussian" else self.cfg["representation_size"])
+            prep, keep = "ladder_mixture_sample_prepare_diag", (ctx.zeros(1, R), torch.ones(1, R, dtype=torch.float32, device=ctx.device))
+        nbytes = L.query("ladder_mixture_sample_param_bytes", K, R)
+        if nbytes == 0:
+            raise ValueError("the device sampler takes 1 <= R <= 64 and K >= 1 (got K = %d, R = %d)" % (K, R))
+        params = torch.empty(nbytes, dtype=torch.uint8, device=ctx.device)
+        if len(keep) == 3:
+            L.call(prep, _p(keep[0]), _p(keep[1]), _p(keep[2]), K, R, _p(params), st)
+        else:
+            L.call(prep, _p(keep[0]), _p(keep[1]), K, R, _p(params), st)
+        status = int(params[:4].view(torch.int32).item())        # (the one read of the status word; also keeps the temporaries alive until the kernels ran)
+        if status >= 0:
+            raise ValueError("component %d of the %s mixture has no Cholesky factor (covariance / scale not positive definite)" % (status, method))
+        if status != -1:
+            raise ValueError("the weights of the %s mixture have no positive finite sum" % method)
+        return PriorSampler(self, method, K, R, params, seed)
+
+    def images_to_u8(self, x):
+        """uint8 device tensor of x's shape: rint(255 * clip(x, 0, 1)), NaN -> 0 (ladder_images_to_u8)."""
+        x = x.contiguous()
+        out = torch.empty(x.shape, dtype=torch.uint8, device=x.device)
+        L.call("ladder_images_to_u8", _p(x), _p(out), x.numel(), self.ctx.stream)
+        return out
+
+    def generate(self, n, sampler, chunk=128, as_uint8=False, first=0):
+        """Images of samples first .. first+n-1 of `sampler` as ONE host array [n, H, W, C] (float32 raw decoder output, or uint8 with
+        `as_uint8`): per chunk sample -> decode -> optional byte packing -> asynchronous copy into one of two pinned host buffers on a
+        copy stream, so the copy of chunk j runs beside the decode of chunk j+1."""
+        n, chunk = int(n), int(chunk)
+        if n < 0 or chunk < 1:
+            raise ValueError("generate: n >= 0 and chunk >= 1 (got %d, %d)" % (n, chunk))
+        cfg, ctx = self.cfg, self.ctx
+        shape = (int(cfg["dim_input_x"]), int(cfg["dim_input_y"]), int(cfg["dim_input_channel"]))
+        dt_t, dt_n = (torch.uint8, np.uint8) if as_uint8 else (torch.float32, np.float32)
+        out = np.empty((n,) + shape, dtype=dt_n)
+        if n == 0:
+            return out
+        self._join_aux()
+        main = torch.cuda.current_stream(ctx.device)
+        if getattr(self, "_copy_stream", None) is None:
+            self._copy_stream = torch.cuda.Stream(device=ctx.device)
+        nb = min(chunk, n)
+        pinned = [torch.empty((nb,) + shape, dtype=dt_t, pin_memory=True) for _ in range(2)]
+        inflight = [None, None]                  # per pinned buffer: (copy-done event, offset, rows, device tensor kept alive)
+
+        def drain(slot):
+            if inflight[slot] is not None:
+                ev, lo, b, _keep = inflight[slot]
+                ev.synchronize()
+                out[lo:lo + b] = pinned[slot][:b].numpy()
+                inflight[slot] = None
+
+        ctx.keep_activations = False
+        try:
+            for j, lo in enumerate(range(0, n, chunk)):
+                b, slot = min(chunk, n - lo), j & 1
+                code, _, _ = sampler.sample(b, first=int(first) + lo)
+                img = self.decoder.forward(code)
+                if as_uint8:
+                    img = self.images_to_u8(img)
+                ready = torch.cuda.Event()
+                ready.record(main)
+                drain(slot)                      # (host: the buffer's previous copy has landed and been consumed)
+                with torch.cuda.stream(self._copy_stream):
+                    self._copy_stream.wait_event(ready)
+                    pinned[slot][:b].copy_(img.reshape((b,) + shape), non_blocking=True)
+                    done = torch.cuda.Event()
+                    done.record(self._copy_stream)
+                inflight[slot] = (done, lo, b, img)
+            drain(0)
+            drain(1)
+        finally:
+            ctx.keep_activations = True
+            for e in inflight:                   # an exception mid-way: nothing may outlive its copy
+                if e is not None:
+                    e[0].synchronize()
+        return out
 
     def sample_code(self, x, noise=None):
         """code_sample for fit_GMM_VI(space="z") (base.py:699-710): encoder -> z."""
