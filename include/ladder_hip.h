@@ -771,6 +771,27 @@ int ladder_mixture_sample(const void* params, int K, int R, int n, int64_t first
  * (the `sampled_images` array of utils.py:134-138 after its clip to [0, 1]); 16-byte loads, 16-byte packed stores, any n. */
 int ladder_images_to_u8(const float* x, uint8_t* out, size_t n, ladder_stream_t stream);
 
+/* ---------------------------------------------------------------- N16: batched shortest-likely-path interpolation
+ * latent-space-interpolation-mnist.ipynb cells 18-23 (`opt_interpolation`, cell 19; the 500-iteration `sess.run` loop, cells 20-21) for P
+ * paths at once: ONE launch runs n_iter iterations of element-wise clip to [-clip, clip] + Adam on
+ *     w_path * sum_i |p_{i+1} - p_i|  +  w_equal * std_i |p_{i+1} - p_i|  -  sum_i log p_GM(p_i)
+ * over the n_step intermediate points of every path, one workgroup per path (csrc/slp.hip).  Points, both Adam moments and all path
+ * algebra are float64 (guards max(len, 1e-30), max(std, 1e-30); population std; bias-corrected step of iteration t =
+ * lr * sqrt(1 - beta2^t) / (1 - beta1^t)); the mixture term and its gradient are fp32 at the fp32-rounded points, from the buffer
+ * `packed` that ladder_gmm_prepare fills; -log p is summed over the points in double in a fixed order.  Deterministic; a path's result
+ * depends neither on P nor on its index.
+ *   start, end [P,R] fixed end points;  pts [P,n_step,R]: in = the initial points (read when t0 == 0), out = the fp32 rounding of the result.
+ *   The launch runs iterations t0+1 .. t0+n_iter.  state (ladder_slp_state_bytes: three planes of P*n_step*R doubles, points | m | v;
+ *   NULL = not kept) receives the float64 points and moments; with t0 > 0 the launch RESUMES from it and ignores the incoming pts, so
+ *   launches chained through `state` equal one long launch bit for bit.
+ *   record (may be NULL) [P,n_iter,4] DOUBLES per iteration, before its step: loss, path_length, step_var (the std term), neg_ll.
+ * LADDER_E_SHAPE (nothing launched) unless 1 <= R <= 8, 1 <= K <= 1024, 1 <= n_step <= 64, P >= 1, 1 <= n_iter <= 4096 (one launch stays
+ * short; longer runs are chained), t0 >= 0, state != NULL when t0 > 0, and start / end / pts / packed != NULL. */
+size_t ladder_slp_state_bytes(int P, int n_step, int R);
+int ladder_slp_optimise(const float* start, const float* end, float* pts, const float* packed, int K, int R, int P, int n_step, int n_iter,
+                        int t0, double lr, double beta1, double beta2, double eps, double clip, double w_path, double w_equal, double* state,
+                        double* record, ladder_stream_t stream);
+
 /* ---------------------------------------------------------------- helpers */
 /* HOST function (no device work): CRC-32C (Castagnoli) of host memory, crc = 0 to start, chainable.  Used by the
  * tf.train.Saver checkpoint-v2 reader/writer (codes/base.py:37-85: saver_ae / saver_prior) for block and tensor checksums. */

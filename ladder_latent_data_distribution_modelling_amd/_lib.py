@@ -214,6 +214,8 @@ PROTOTYPES = {
     "ladder_mixture_sample_prepare_diag": (_i, [_p, _p, _i, _i, _p, _p]),
     "ladder_mixture_sample": (_i, [_p, _i, _i, _i, C.c_int64, _p, _p, _u64, _u64, _p, _p, _p]),
     "ladder_images_to_u8": (_i, [_p, _p, _z, _p]),
+    "ladder_slp_state_bytes": (_z, [_i, _i, _i]),
+    "ladder_slp_optimise": (_i, [_p, _p, _p, _p] + [_i] * 6 + [_d] * 7 + [_p, _p, _p]),
 }
 
 _lib = None

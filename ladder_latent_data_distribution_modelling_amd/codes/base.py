@@ -460,3 +460,23 @@ class BaseTrain_joint(BaseTrain):
         self.flush()
         _, sampler = self._prior_sampler(mode, method, seed)
         return self.engine.generate(n, sampler, chunk=chunk, as_uint8=as_uint8)
+
+    def interpolate_paths(self, starts, ends, mode="accurate-GM", n_step=5, n_iter=500, decode=True, **kw):
+        """Shortest-likely-path interpolation between P pairs of representations (latent-space-interpolation-mnist.ipynb cells 18-23) under
+        the fitted mixture that `mode` names, as _prior_sampler picks it: "crude-GM" -> gm_params, any other mode -> gm_final_params.
+        starts, ends [P, R]; **kw goes to SLPInterpolator.optimise_batch (lr, w_equal_length, w_path_dist, init, clip, record).
+        -> (pts [P, n_step, R], rec, images [P, n_step + 2, H, W, C] or None without `decode`)."""
+        prior, R = self.config["prior"], int(self.config.get("representation_size", 0))
+        if prior != "ours" or not 1 <= R <= 8:
+            raise ValueError("interpolate_paths needs the mixture on the representation t with R <= 8 (prior 'ours'); this model's prior is %r, R = %d"
+                             % (prior, R))
+        mixture = self.gm_params if mode == "crude-GM" else getattr(self, "gm_final_params", None)
+        if mixture is None:
+            raise RuntimeError("interpolation with mode %r needs the %s mixture, which has not been fitted yet (fit_GMM_VI(mode=%r))"
+                               % (mode, "per-epoch" if mode == "crude-GM" else "accurate", "fast" if mode == "crude-GM" else "accurate"))
+        from .interpolation import SLPInterpolator
+        self.flush()
+        w, m, c = (np.asarray(a.cpu() if isinstance(a, torch.Tensor) else a, np.float32) for a in mixture)
+        slp = SLPInterpolator(self.engine, w, m, c)
+        pts, rec = slp.optimise_batch(starts, ends, n_step=n_step, n_iter=n_iter, **kw)
+        return pts, rec, (slp.decode_paths(starts, pts, ends) if decode else None)

@@ -16,6 +16,9 @@ import torch
 
 from .. import _lib as L
 
+MAX_STEP = 64                   # ladder_slp_optimise: 1 <= n_step <= 64
+MAX_ITER_PER_LAUNCH = 4096      # ... and at most 4096 iterations per launch; longer runs are chained through its float64 state
+
 
 def path_terms(pts, start, end):
     """-> (entire_path_length, equal_length_constraint, d/dpts of each) for the intermediate points `pts` [n, R]."""
@@ -79,3 +82,74 @@ class SLPInterpolator:
         t = np.concatenate([np.asarray(start)[None], pts, np.asarray(end)[None]], 0)
         code = self.eng.decode_representation(t) if self.eng.has_inner else self.eng._dev(t)
         return np.clip(self.eng.decode(code).cpu().numpy(), 0.0, 1.0)
+
+    # ------------------------------------------------------------------ many paths at once (csrc/slp.hip)
+    def _check_batch(self, starts, ends, n_step):
+        starts, ends = np.asarray(starts, np.float64), np.asarray(ends, np.float64)
+        if starts.ndim != 2 or starts.shape != ends.shape or starts.shape[0] < 1:
+            raise ValueError("optimise_batch: starts and ends must both be [P, R] with P >= 1 (got %s and %s)" % (starts.shape, ends.shape))
+        if starts.shape[1] != self.R:
+            raise ValueError("optimise_batch: the end points have R = %d, the mixture has R = %d" % (starts.shape[1], self.R))
+        if not 1 <= int(n_step) <= MAX_STEP:
+            raise ValueError("optimise_batch: n_step must be in 1..%d (got %r)" % (MAX_STEP, n_step))
+        return starts, ends
+
+    def optimise_batch(self, starts, ends, n_step=5, n_iter=500, lr=1e-2, w_equal_length=100.0, w_path_dist=10.0, init=None, clip=1.0,
+                       record=True):
+        """`optimise` for P pairs at once, the whole loop on the device (ladder_slp_optimise: one workgroup per path, one launch per
+        4096 iterations, chained through the float64 state; no host synchronisation in between, one copy to the host at the end).
+        starts, ends [P, R]; init [P, n_step, R] (default: the notebook's linspace per pair); `clip` is the element-wise gradient bound.
+        The kernel takes its inputs as fp32 and keeps points and moments in float64 from there on.
+        Returns (pts [P, n_step, R]: the fp32 results as float64, rec: {loss, path_length, step_var, neg_ll} each [P, n_iter] -- None
+        when `record` is False)."""
+        starts, ends = self._check_batch(starts, ends, n_step)
+        n_step, n_iter = int(n_step), int(n_iter)
+        if n_iter < 1:
+            raise ValueError("optimise_batch: n_iter must be >= 1 (got %d)" % n_iter)
+        P, R = starts.shape
+        if init is None:
+            init = np.stack([np.linspace(s, e, n_step + 1, endpoint=False)[1:] for s, e in zip(starts, ends)])
+        init = np.asarray(init, np.float64)
+        if init.shape != (P, n_step, R):
+            raise ValueError("optimise_batch: init must be [P, n_step, R] = %s (got %s)" % ((P, n_step, R), init.shape))
+        from .utils import register_trainable_scope
+        register_trainable_scope("interpolation", init.size)     # notebook cell 19: count_trainable_variables('interpolation')
+        dev, st = self.eng.ctx.device, self.eng.ctx.stream
+        f = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.float32)).to(dev)
+        s_d, e_d, pts = f(starts), f(ends), f(init)
+        state = torch.empty(L.query("ladder_slp_state_bytes", P, n_step, R) // 8, dtype=torch.float64, device=dev)
+        recs = []
+        for t0 in range(0, n_iter, MAX_ITER_PER_LAUNCH):
+            k = min(MAX_ITER_PER_LAUNCH, n_iter - t0)
+            r = torch.empty(P, k, 4, dtype=torch.float64, device=dev) if record else None
+            L.call("ladder_slp_optimise", s_d.data_ptr(), e_d.data_ptr(), pts.data_ptr(), self.packed.data_ptr(), self.K, R, P, n_step, k, t0,
+                   float(lr), 0.9, 0.95, 1e-8, float(clip), float(w_path_dist), float(w_equal_length), state.data_ptr(),
+                   None if r is None else r.data_ptr(), st)
+            recs.append(r)
+        flat = [pts.to(torch.float64).reshape(-1)] + ([torch.cat(recs, 1).reshape(-1)] if record else [])
+        host = torch.cat(flat).cpu().numpy()                     # the one copy (and the one synchronisation)
+        out = host[:init.size].reshape(P, n_step, R).copy()
+        rec = None
+        if record:
+            r = host[init.size:].reshape(P, n_iter, 4)
+            rec = {k: r[:, :, i].copy() for i, k in enumerate(("loss", "path_length", "step_var", "neg_ll"))}
+        return out, rec
+
+    def decode_paths(self, starts, pts, ends, chunk=128):
+        """Images along P paths [start, pts..., end] -> [P, n_step + 2, H, W, C] clipped to [0, 1]; a decoder batch holds whole paths and at
+        most `chunk` points."""
+        starts, ends, pts = np.asarray(starts), np.asarray(ends), np.asarray(pts)
+        if pts.ndim != 3 or starts.shape != (pts.shape[0], pts.shape[2]) or ends.shape != starts.shape:
+            raise ValueError("decode_paths: starts / ends [P, R] and pts [P, n_step, R] expected (got %s, %s, %s)" % (starts.shape, ends.shape, pts.shape))
+        P, n = pts.shape[0], pts.shape[1] + 2
+        per = int(chunk) // n
+        if per < 1:
+            raise ValueError("decode_paths: chunk = %d holds no whole path of %d points" % (chunk, n))
+        t = np.concatenate([starts[:, None], pts, ends[:, None]], 1)
+        out = []
+        for lo in range(0, P, per):
+            tb = t[lo:lo + per].reshape(-1, t.shape[2])
+            code = self.eng.decode_representation(tb) if self.eng.has_inner else self.eng._dev(tb)
+            img = np.clip(self.eng.decode(code).cpu().numpy(), 0.0, 1.0)
+            out.append(img.reshape((-1, n) + img.shape[1:]))
+        return np.concatenate(out, 0)

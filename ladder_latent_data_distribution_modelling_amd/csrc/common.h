@@ -9,6 +9,21 @@
     if (hipGetLastError() != hipSuccess) return LADDER_E_LAUNCH; \
   } while (0)
 
+// Host-side dispatch on the narrow latent width of the mixture kernels (csrc/elbo.hip, csrc/slp.hip): runs the statement with
+// `constexpr int RR = R` for R in 1..8, returns LADDER_E_SHAPE from the calling export otherwise.
+#define LADDER_R_SWITCH(R, ...) \
+  switch (R) {                   \
+    case 1: { constexpr int RR = 1; __VA_ARGS__; } break; \
+    case 2: { constexpr int RR = 2; __VA_ARGS__; } break; \
+    case 3: { constexpr int RR = 3; __VA_ARGS__; } break; \
+    case 4: { constexpr int RR = 4; __VA_ARGS__; } break; \
+    case 5: { constexpr int RR = 5; __VA_ARGS__; } break; \
+    case 6: { constexpr int RR = 6; __VA_ARGS__; } break; \
+    case 7: { constexpr int RR = 7; __VA_ARGS__; } break; \
+    case 8: { constexpr int RR = 8; __VA_ARGS__; } break; \
+    default: return LADDER_E_SHAPE;                \
+  }
+
 static inline bool ladder_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 __device__ __forceinline__ float ladder_act_fn(float v, int act) {

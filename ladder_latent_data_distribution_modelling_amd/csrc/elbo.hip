@@ -940,19 +940,6 @@ int ladder_elbo_finalize(const float* partials, const float* sigma_var, const fl
 
 int ladder_gmm_packed_stride(int R) { return 1 + R + R * (R + 1) / 2; }
 
-#define LADDER_R_SWITCH(R, ...) \
-  switch (R) {                   \
-    case 1: { constexpr int RR = 1; __VA_ARGS__; } break; \
-    case 2: { constexpr int RR = 2; __VA_ARGS__; } break; \
-    case 3: { constexpr int RR = 3; __VA_ARGS__; } break; \
-    case 4: { constexpr int RR = 4; __VA_ARGS__; } break; \
-    case 5: { constexpr int RR = 5; __VA_ARGS__; } break; \
-    case 6: { constexpr int RR = 6; __VA_ARGS__; } break; \
-    case 7: { constexpr int RR = 7; __VA_ARGS__; } break; \
-    case 8: { constexpr int RR = 8; __VA_ARGS__; } break; \
-    default: return LADDER_E_SHAPE;                \
-  }
-
 int ladder_gmm_prepare(const float* weights, const float* means, const float* covs, int K, int R, float* packed, ladder_stream_t stream) {
   if (K <= 0 || K > 1024) return LADDER_E_SHAPE;
   LADDER_R_SWITCH(R, hipLaunchKernelGGL(gmm_prepare_kernel<RR>, dim3((K + 63) / 64), dim3(64), 0, stream, weights, means, covs, K, packed));
