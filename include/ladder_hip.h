@@ -792,6 +792,34 @@ int ladder_slp_optimise(const float* start, const float* end, float* pts, const 
                         int t0, double lr, double beta1, double beta2, double eps, double clip, double w_path, double w_equal, double* state,
                         double* record, ladder_stream_t stream);
 
+/* ---------------------------------------------------------------- N17: FID evaluation (csrc/fid.hip)
+ * codes/utils.py:127-200 (`compute_FID_score`, FID_network == "VGG").  The 13 convolutions of VGG16 run on ladder_conv2d_fwd / ladder_conv3x3_split
+ * with LADDER_ACT_RELU; these exports are the rest of the pipeline.
+ * ladder_fid_preprocess: codes/utils.py:127-138 + 156-157 in one pass.  x [N,H,W,C] uint8 (x_is_u8 != 0) or float, C == 3; y [N,OH,OW,C] float.
+ *   mode LADDER_FID_ORIGINAL: v/255, then (v-0.5)*2, no clip;  LADDER_FID_GENERATED: clip(v,0,1), then (v-0.5)*2 -- applied per source pixel, then
+ *   tf.image.resize_images (TF1 legacy bilinear: src = dst * in/out, lo = floor(src), hi = min(lo+1, in-1)) for ANY pair of sizes; an axis whose
+ *   weight is zero (every pixel of 128 -> 64) reads its low tap only. */
+enum { LADDER_FID_ORIGINAL = 0, LADDER_FID_GENERATED = 1 };
+enum { LADDER_POOL_AVG = 0, LADDER_POOL_MAX = 1 };
+int ladder_fid_preprocess(const void* x, int x_is_u8, float* y, int N, int H, int W, int C, int OH, int OW, int mode, ladder_stream_t stream);
+/* MaxPooling2D(2, strides 2, VALID) of tf.keras.applications.VGG16 (codes/utils.py:184-188): x [N,H,W,C] -> y [N,H/2,W/2,C] (odd extents floor; an empty
+ * output is LADDER_E_SHAPE); 128-bit accesses when C % 4 == 0. */
+int ladder_maxpool2x2_fwd(const float* x, float* y, int N, int H, int W, int C, ladder_stream_t stream);
+/* pooling = "avg" / "max" of the same model: x [N,HW,C] -> y [N,C]; the HW terms are taken in index order (average = fp32 sum / HW). */
+int ladder_global_pool(const float* x, float* y, int N, int HW, int C, int kind, ladder_stream_t stream);
+/* Streaming float64 mean / covariance of fp32 activations x [n,D], chunk after chunk: the statistics that
+ * tf.contrib.gan.eval.frechet_classifier_distance_from_activations (codes/utils.py:197-199) takes from the whole activation matrix.
+ *   state: ladder_moments_state_doubles doubles, ZERO-FILLED by the caller before the first chunk:  rows so far | D | c [D] | s [D] | S [D][D]  with
+ *   s = sum (x - c), S = sum (x - c)(x - c)^T.  The first chunk (rows so far == 0) sets c to its own column mean rounded to fp32.  Of S only the 64 x 64
+ *   tiles on and above the diagonal are written: the reader takes S[i][j] for i <= j and mirrors.  mean = c + s/n, cov = (S - s s^T / n) / (n - 1).
+ *   S runs on v_mfma_f64_16x16x4_f64; the chunk's rows are split into partial tiles in `ws` (>= ladder_moments_workspace_bytes of the chunk), added in a
+ *   fixed order: a given sequence of chunk sizes is bit-reproducible.  Any n >= 0 and 1 <= D <= 32768; no read goes past n*D floats.
+ *   The D of a state is fixed by its first chunk.  The host cannot see it without a synchronisation, so a later call with another D is refused ON THE
+ *   DEVICE: the state is left as it is except that its row count becomes NaN (the reader must check it; the Python binding raises). */
+size_t ladder_moments_state_doubles(int D);
+size_t ladder_moments_workspace_bytes(int n, int D);
+int ladder_moments_accumulate(const float* x, int n, int D, double* state, void* ws, size_t ws_bytes, ladder_stream_t stream);
+
 /* ---------------------------------------------------------------- helpers */
 /* HOST function (no device work): CRC-32C (Castagnoli) of host memory, crc = 0 to start, chainable.  Used by the
  * tf.train.Saver checkpoint-v2 reader/writer (codes/base.py:37-85: saver_ae / saver_prior) for block and tensor checksums. */

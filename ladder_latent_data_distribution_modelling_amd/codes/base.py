@@ -461,6 +461,20 @@ class BaseTrain_joint(BaseTrain):
         _, sampler = self._prior_sampler(mode, method, seed)
         return self.engine.generate(n, sampler, chunk=chunk, as_uint8=as_uint8)
 
+    def compute_FID(self, real, n, weights, mode="accurate-GM", method=None, pooling="avg", chunk=128, seed=None, input_size=64):
+        """FID (VGG16 features, reference utils.py:141-200) between the images `real` -- an npz path (key sampled_images) or an array [m, H, W, 3],
+        preprocessed as "original" -- and n images generated from the prior as generate_images draws them, preprocessed as "generated".  The
+        generated images go from the decoder straight into the feature network and the float64 statistics: they never leave the device."""
+        from .. import fid
+        self.flush()
+        _, sampler = self._prior_sampler(mode, method, seed)
+        features = fid.VGG16Features(self.engine.ctx, weights, fid.check_pooling(pooling), input_size)
+        s_real = fid.accumulate_array(fid.load_images(real), features, "original", chunk)
+        s_gen = fid.FrechetStats(features.ctx, features.D)
+        self.engine.generate(n, sampler, chunk=chunk, sink=lambda img, _first: s_gen.update(features(img, "generated")))
+        (_, m1, c1), (_, m2, c2) = s_real.moments(), s_gen.moments()
+        return fid.frechet_distance(m1, c1, m2, c2)
+
     def interpolate_paths(self, starts, ends, mode="accurate-GM", n_step=5, n_iter=500, decode=True, **kw):
         """Shortest-likely-path interpolation between P pairs of representations (latent-space-interpolation-mnist.ipynb cells 18-23) under
         the fitted mixture that `mode` names, as _prior_sampler picks it: "crude-GM" -> gm_params, any other mode -> gm_final_params.

@@ -97,6 +97,17 @@ def count_trainable_variables(scope_name, model=None):
     return n
 
 
+def compute_FID_score(data_file1, data_file2, FID_network, pooling_option, second_set='generated', weights=None, chunk=256, input_size=64,
+                      device="cuda:0"):
+    """FID between the `sampled_images` arrays of two archives on VGG16 features; same leading arguments and printed line as the reference
+    (utils.py:141-200), and the score is also returned as a Python float.  Set 1 is preprocessed as "original" (x/255), set 2 as "generated"
+    (clip to [0, 1]) unless second_set says otherwise -- a uint8 archive is on the 0..255 scale and needs second_set='original' (the fid.py
+    command line picks that by itself).  `weights`: npz path or dict keyed by the Keras layer names (ladder_latent_data_distribution_modelling_amd/fid.py);
+    both sets are resized to input_size x input_size (the reference's 64) and streamed through the device `chunk` images at a time."""
+    from .. import fid
+    return fid.score_archives(data_file1, data_file2, FID_network, pooling_option, second_set, weights, chunk, input_size, device)
+
+
 def get_args():
     parser = argparse.ArgumentParser(description="LaDDer training on the MI355X HIP path")
     parser.add_argument("-c", "--config", metavar="C", default="None", help="The Configuration file")

@@ -946,25 +946,26 @@ class LadderEngine:
         L.call("ladder_images_to_u8", _p(x), _p(out), x.numel(), self.ctx.stream)
         return out
 
-    def generate(self, n, sampler, chunk=128, as_uint8=False, first=0):
+    def generate(self, n, sampler, chunk=128, as_uint8=False, first=0, sink=None):
         """Images of samples first .. first+n-1 of `sampler` as ONE host array [n, H, W, C] (float32 raw decoder output, or uint8 with
         `as_uint8`): per chunk sample -> decode -> optional byte packing -> asynchronous copy into one of two pinned host buffers on a
-        copy stream, so the copy of chunk j runs beside the decode of chunk j+1."""
+        copy stream, so the copy of chunk j runs beside the decode of chunk j+1.
+        `sink`: each decoded DEVICE chunk [b, H, W, C] (after the byte packing, if asked for) is handed to sink(chunk, first) on the current stream
+        instead, `first` = the sample index of the chunk's first image; nothing is copied to the host and the call returns None (fid.py: the images
+        never leave the device)."""
         n, chunk = int(n), int(chunk)
         if n < 0 or chunk < 1:
             raise ValueError("generate: n >= 0 and chunk >= 1 (got %d, %d)" % (n, chunk))
         cfg, ctx = self.cfg, self.ctx
         shape = (int(cfg["dim_input_x"]), int(cfg["dim_input_y"]), int(cfg["dim_input_channel"]))
         dt_t, dt_n = (torch.uint8, np.uint8) if as_uint8 else (torch.float32, np.float32)
-        out = np.empty((n,) + shape, dtype=dt_n)
+        out = None if sink is not None else np.empty((n,) + shape, dtype=dt_n)
         if n == 0:
             return out
         self._join_aux()
         main = torch.cuda.current_stream(ctx.device)
-        if getattr(self, "_copy_stream", None) is None:
-            self._copy_stream = torch.cuda.Stream(device=ctx.device)
         nb = min(chunk, n)
-        pinned = [torch.empty((nb,) + shape, dtype=dt_t, pin_memory=True) for _ in range(2)]
+        pinned = [torch.empty((nb,) + shape, dtype=dt_t, pin_memory=True) for _ in range(2)] if sink is None else None
         inflight = [None, None]                  # per pinned buffer: (copy-done event, offset, rows, device tensor kept alive)
 
         def drain(slot):
@@ -974,23 +975,31 @@ class LadderEngine:
                 out[lo:lo + b] = pinned[slot][:b].numpy()
                 inflight[slot] = None
 
+        def to_host(img, j, lo, b):              # the consumer of a chunk when no sink is given
+            slot, cs = j & 1, ctx.copy_stream
+            ready = torch.cuda.Event()
+            ready.record(main)
+            drain(slot)                          # (host: the buffer's previous copy has landed and been consumed)
+            with torch.cuda.stream(cs):
+                cs.wait_event(ready)
+                pinned[slot][:b].copy_(img, non_blocking=True)
+                done = torch.cuda.Event()
+                done.record(cs)
+            inflight[slot] = (done, lo, b, img)
+
         ctx.keep_activations = False
         try:
             for j, lo in enumerate(range(0, n, chunk)):
-                b, slot = min(chunk, n - lo), j & 1
+                b = min(chunk, n - lo)
                 code, _, _ = sampler.sample(b, first=int(first) + lo)
                 img = self.decoder.forward(code)
                 if as_uint8:
                     img = self.images_to_u8(img)
-                ready = torch.cuda.Event()
-                ready.record(main)
-                drain(slot)                      # (host: the buffer's previous copy has landed and been consumed)
-                with torch.cuda.stream(self._copy_stream):
-                    self._copy_stream.wait_event(ready)
-                    pinned[slot][:b].copy_(img.reshape((b,) + shape), non_blocking=True)
-                    done = torch.cuda.Event()
-                    done.record(self._copy_stream)
-                inflight[slot] = (done, lo, b, img)
+                img = img.reshape((b,) + shape)
+                if sink is not None:
+                    sink(img, int(first) + lo)
+                else:
+                    to_host(img, j, lo, b)
             drain(0)
             drain(1)
         finally:

@@ -231,6 +231,25 @@ class Ctx:
     def zeros(self, *shape):
         return torch.zeros(*shape, dtype=torch.float32, device=self.device)
 
+    def fork(self, precision=None, forward_only=False):
+        """A fresh context on the same device and communicator for a network that is not the model's (fid.VGG16Features): its own workspace, records,
+        packed-bank list and streams; only the copy stream is shared with this one.  `precision`: a LADDER_PREC_* value (default: this context's);
+        `forward_only`: nothing is ever kept for a backward pass."""
+        c = Ctx(self.device, self.comm)
+        c.ns = self.ns if precision is None else int(precision)
+        c.keep_activations = not forward_only
+        c._copy_root = getattr(self, "_copy_root", self)
+        return c
+
+    @property
+    def copy_stream(self):
+        """The one stream for host <-> device copies that run beside compute (LadderEngine.generate, fid._device_chunks), created on first use and shared
+        by every context forked from this one."""
+        root = getattr(self, "_copy_root", self)
+        if getattr(root, "_copy_stream", None) is None:
+            root._copy_stream = torch.cuda.Stream(device=root.device)
+        return root._copy_stream
+
     def local(self):
         """The same device context without cross-rank exchange (batch statistics of a replicated batch stay local)."""
         import copy
@@ -398,7 +417,8 @@ class Conv2D:
         self.bias_grad = bias_grad
         self._packed = {}      # (transpose_flip, ns) -> [weight version, packed bf16 planes]
         self._routes = {}      # route()'s cache
-        self.group = arch.group_of(name + "/kernel")           # optimiser group whose version stamps the packed images
+        # optimiser group whose version stamps the packed images (a store of frozen weights outside the model names its own: fid.VGG16Features)
+        self.group = getattr(ps, "group_of", arch.group_of)(name + "/kernel")
         self.want_bn_sums, self.bn_sums = want_bn_sums, None   # batch-norm statistics of the output from the conv epilogue
         self.kept = None                                        # Kept record of the last forward (None: a forward-only run kept nothing, or backward consumed it)
 

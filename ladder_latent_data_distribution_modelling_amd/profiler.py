@@ -55,7 +55,8 @@ class KernelProfiler:
             fl = sum(f for _, _, f, _ in recs)
             fx = sum(x for _, _, _, x in recs)
             n = len(recs)
-            out[kid] = dict(kernel=self.NAMES.get(kid, "igemm tile %d" % kid), launches=n, total_ms=ms, avg_ms=ms / n,
+            # (a string key is a named stage of a pipeline outside the training step: fid._stage)
+            out[kid] = dict(kernel=kid if isinstance(kid, str) else self.NAMES.get(kid, "igemm tile %d" % kid), launches=n, total_ms=ms, avg_ms=ms / n,
                             flops_per_launch=fl / n, tflops=(fl / (ms * 1e-3) / 1e12) if ms > 0 else 0.0,
                             executed_flops_per_launch=fx / n, executed_tflops=(fx / (ms * 1e-3) / 1e12) if ms > 0 else 0.0,
                             bound="latency" if kid in self.LATENCY_BOUND else "mfma")
