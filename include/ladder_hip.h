@@ -673,7 +673,7 @@ int ladder_randn_dev(float* out, size_t n, uint64_t seed, const uint64_t* offset
 int ladder_u64_add(uint64_t* p, uint64_t inc, ladder_stream_t stream);
 
 /* ---- the same mixture on a WIDE latent (prior "GMM": the mixture sits on z, R = code_size; codes/base.py:101-106, 322-329).
- * 8 < R <= 64, R % 4 == 0.  The whitening of all components is one GEMM on the dense MFMA kernel (see csrc/elbo.hip);
+ * 8 < R <= 64, R % 4 == 0.  The whitening of all components is one GEMM on the dense MFMA kernel (see csrc/mixture.hip);
  * params = ladder_gmm_dense_param_floats(K,R) floats filled by ladder_gmm_prepare_dense (float64 Cholesky per component).
  * Same outputs / conventions as ladder_gmm_logprob_fwd_bwd; dmu = dsd = NULL evaluates the log-prob only. */
 size_t ladder_gmm_dense_param_floats(int K, int R);

@@ -5,7 +5,7 @@ notebook `latent-space-interpolation-mnist.ipynb` (cells 18-23), without TensorF
 
 over `n_step` intermediate points between two fixed embeddings, minimised with clip-[-1,1] + Adam(beta1=.9, beta2=.95) exactly like
 the notebook's `opt_interpolation` (cell 19).  The mixture term and its gradient come from the HIP mixture kernel
-(`ladder_gmm_logprob_fwd_bwd` with one "MC sample" and eps = 0, so t = mean = the path points); the remaining algebra is a handful
+(`DeviceMixture.fwd_bwd` with one "MC sample" and eps = 0, so t = mean = the path points); the remaining algebra is a handful
 of numbers and stays on the host.  `decode_path` maps the optimised path to images (t -> inner decoder -> z -> decoder), as
 demo/demo_tools.py:163-186 does through `sess.run`.
 """
@@ -15,6 +15,7 @@ import numpy as np
 import torch
 
 from .. import _lib as L
+from ..mixture import DeviceMixture
 
 MAX_STEP = 64                   # ladder_slp_optimise: 1 <= n_step <= 64
 MAX_ITER_PER_LAUNCH = 4096      # ... and at most 4096 iterations per launch; longer runs are chained through its float64 state
@@ -38,24 +39,16 @@ class SLPInterpolator:
     def __init__(self, engine, weights, means, covs):
         """`engine`: a LadderEngine (for the device / stream / decoders); (weights, means, covs): the fitted mixture (R <= 8)."""
         self.eng = engine
-        dev = engine.ctx.device
-        f = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.float32)).to(dev)
-        w, m, c = f(weights), f(means), f(covs)
-        self.K, self.R = int(m.shape[0]), int(m.shape[1])
-        self.packed = torch.empty(self.K * L.query("ladder_gmm_packed_stride", self.R), device=dev)
-        L.call("ladder_gmm_prepare", w.data_ptr(), m.data_ptr(), c.data_ptr(), self.K, self.R, self.packed.data_ptr(), engine.ctx.stream)
-        torch.cuda.current_stream(dev).synchronize()
+        self.K, self.R = (int(n) for n in np.shape(means))
+        self.mixture = DeviceMixture(engine.ctx, self.K, self.R)
+        self.mixture.set(weights, means, covs)
 
     def neg_log_likelihood(self, pts):
         """-> (-sum_i log p(p_i), gradient [n, R]) from the HIP mixture kernel."""
-        dev, st = self.eng.ctx.device, self.eng.ctx.stream
-        n = pts.shape[0]
+        dev = self.eng.ctx.device
         mu = torch.as_tensor(np.ascontiguousarray(pts, dtype=np.float32)).to(dev)
-        sd, eps = torch.ones_like(mu), torch.zeros(1, n, self.R, device=dev)
-        out, dmu, dsd = torch.empty(1, device=dev), torch.empty_like(mu), torch.empty_like(mu)
-        ws = torch.empty(max(L.query("ladder_gmm_workspace_bytes", 1, n), 16), dtype=torch.uint8, device=dev)
-        L.call("ladder_gmm_logprob_fwd_bwd", mu.data_ptr(), sd.data_ptr(), eps.data_ptr(), self.packed.data_ptr(), 1, n, self.R, self.K,
-               out.data_ptr(), dmu.data_ptr(), dsd.data_ptr(), ws.data_ptr(), ws.numel(), st)
+        out = torch.empty(1, device=dev)
+        dmu, _ = self.mixture.fwd_bwd(mu, torch.ones_like(mu), torch.zeros(1, pts.shape[0], self.R, device=dev), out)
         return -float(out.item()), -dmu.cpu().numpy().astype(np.float64)
 
     def optimise(self, start, end, n_step=5, n_iter=500, lr=1e-2, w_equal_length=100.0, w_path_dist=10.0, init=None):
@@ -122,7 +115,7 @@ class SLPInterpolator:
         for t0 in range(0, n_iter, MAX_ITER_PER_LAUNCH):
             k = min(MAX_ITER_PER_LAUNCH, n_iter - t0)
             r = torch.empty(P, k, 4, dtype=torch.float64, device=dev) if record else None
-            L.call("ladder_slp_optimise", s_d.data_ptr(), e_d.data_ptr(), pts.data_ptr(), self.packed.data_ptr(), self.K, R, P, n_step, k, t0,
+            L.call("ladder_slp_optimise", s_d.data_ptr(), e_d.data_ptr(), pts.data_ptr(), self.mixture.buf.data_ptr(), self.K, R, P, n_step, k, t0,
                    float(lr), 0.9, 0.95, 1e-8, float(clip), float(w_path_dist), float(w_equal_length), state.data_ptr(),
                    None if r is None else r.data_ptr(), st)
             recs.append(r)

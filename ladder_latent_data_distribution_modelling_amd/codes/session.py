@@ -189,7 +189,7 @@ class Session:
                 if eng.cfg["prior"] in ("ours", "hierarchical", "vampPrior"):   # the priors whose loss goes through the tf.cond
                     need("use_standard_gaussian_prior")                         # (base.py:318-320, 357-359, 368-370; "GMM" has none)
                 if eng.gmm_z or (eng.has_inner and not eng.hier):
-                    if not fed_mixture and eng._gm_packed is None:
+                    if not fed_mixture and eng.mixture is None:
                         need("prior_weight"), need("prior_mean"), need("prior_cov")
                     parts.append("gmm")
                 elif eng.vamp:

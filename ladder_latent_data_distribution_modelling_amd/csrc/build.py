@@ -5,13 +5,14 @@
 hipcc cross-compiles for gfx950 without a GPU present; the .so travels to the GPU box with the repo
 snapshot (it is git-ignored, not gpurun-ignored).
 """
+import glob
 import os
 import subprocess
 import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
-SOURCES = ["igemm.hip", "convsplit.hip", "convf32.hip", "convf32s.hip", "upproj.hip", "densef32.hip", "densesplit.hip", "convrgb.hip", "norm.hip", "elbo.hip", "hostutil.hip", "vbgmm.hip", "sample.hip", "slp.hip", "fid.hip"]
+SOURCES = ["igemm.hip", "convsplit.hip", "convf32.hip", "convf32s.hip", "upproj.hip", "densef32.hip", "densesplit.hip", "convrgb.hip", "norm.hip", "elbo.hip", "mixture.hip", "hostutil.hip", "vbgmm.hip", "sample.hip", "slp.hip", "fid.hip"]
 LIB = os.path.join(HERE, "libladder_hip.so")
 
 
@@ -19,8 +20,7 @@ def _stale():
     if not os.path.exists(LIB):
         return True
     t = os.path.getmtime(LIB)
-    deps = [os.path.join(HERE, s) for s in SOURCES] + [os.path.join(HERE, h) for h in ("common.h", "split16.h", "filterbank.h", "convf32.h", "philox.h")] + [
-                                                       os.path.join(ROOT, "include", "ladder_hip.h")]
+    deps = [os.path.join(HERE, s) for s in SOURCES] + glob.glob(os.path.join(HERE, "*.h")) + [os.path.join(ROOT, "include", "ladder_hip.h")]
     return any(os.path.getmtime(d) > t for d in deps)
 
 

@@ -9,7 +9,7 @@
     if (hipGetLastError() != hipSuccess) return LADDER_E_LAUNCH; \
   } while (0)
 
-// Host-side dispatch on the narrow latent width of the mixture kernels (csrc/elbo.hip, csrc/slp.hip): runs the statement with
+// Host-side dispatch on the narrow latent width of the mixture kernels (csrc/mixture.hip, csrc/slp.hip): runs the statement with
 // `constexpr int RR = R` for R in 1..8, returns LADDER_E_SHAPE from the calling export otherwise.
 #define LADDER_R_SWITCH(R, ...) \
   switch (R) {                   \

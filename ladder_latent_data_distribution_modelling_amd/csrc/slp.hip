@@ -8,7 +8,7 @@
 //
 // Per iteration:
 //   phase A  mixture term: a wavefront takes a point (points beyond the wave count are looped over), lane = component, K in chunks of 64,
-//            the per-component arithmetic of gmm_rows_kernel / gmm_logprob_kernel (csrc/elbo.hip): lp_k = c_k - 0.5 |Linv_k (t - m_k)|^2 in
+//            the per-component arithmetic of gmm_packed.h (shared with csrc/mixture.hip): lp_k = c_k - 0.5 |Linv_k (t - m_k)|^2 in
 //            fp32 at the fp32-rounded point, online log-sum-exp per lane, then across lanes by wave shuffles; the gradient numerators
 //            sum_k exp(lp_k - max) Linv_k^T y_k ride the same rescaling.  The LAST wavefront -- the one with the fewest points when n_step is
 //            no multiple of 4 -- also forms the segment lengths, their mean / population std, the unit vectors and d std / d len in float64
@@ -19,6 +19,7 @@
 // Points and both moments live in LDS as float64 for the whole launch; `state` carries them between chained launches, and because the
 // step size is a function of the absolute iteration number t (pow, not a running product) a chained run equals a single launch bit for bit.
 #include "common.h"
+#include "gmm_packed.h"
 
 namespace {
 
@@ -42,42 +43,19 @@ struct SlpArgs {
 // log p(t) and -d log p / d t of one point for the calling wavefront (all 64 lanes active); results valid on every lane.
 template <int R>
 __device__ __forceinline__ float slp_point(const float* __restrict__ prm_base, int K, int lane, const float (&t_)[R], float (&gout)[R]) {
-  constexpr int STRIDE = 1 + R + R * (R + 1) / 2;
+  constexpr int STRIDE = GmmPacked<R>::STRIDE, MEAN = GmmPacked<R>::MEAN, TRI = GmmPacked<R>::TRI;
   float mx = -INFINITY, se = 0.f, g_[R];
 #pragma unroll
   for (int j = 0; j < R; ++j) g_[j] = 0.f;
   for (int k = lane; k < K; k += 64) {
     const float* prm = prm_base + (size_t)k * STRIDE;
-    float y_[R];
-    float maha = 0.f;
-    int q = 1 + R;
-#pragma unroll
-    for (int a = 0; a < R; ++a) {
-      float ya = 0.f;
-#pragma unroll
-      for (int j = 0; j < R; ++j)
-        if (j <= a) ya += prm[q++] * (t_[j] - prm[1 + j]);
-      y_[a] = ya;
-      maha += ya * ya;
-    }
+    GMM_WHITEN(R, q, prm[TRI + q], j, t_[j] - prm[MEAN + j], y_, maha);
     const float lp = prm[0] - 0.5f * maha;
-    const float m2 = fmaxf(mx, lp);
-    // (a component of weight exactly 0 has c_k = lp = -inf: while the running maximum is still -inf both differences would be NaN, which
-    // would then live on through every iteration and the chained state -- such a component contributes nothing instead)
-    const float sc = (mx == -INFINITY) ? 0.f : __expf(mx - m2), ex = (m2 == -INFINITY) ? 0.f : __expf(lp - m2);
+    GMM_LSE_STEP(lp, mx, sc, ex);
     se = se * sc + ex;
-    float v_[R];
-#pragma unroll
-    for (int j = 0; j < R; ++j) v_[j] = 0.f;
-    q = 1 + R;
-#pragma unroll
-    for (int a = 0; a < R; ++a)
-#pragma unroll
-      for (int j = 0; j < R; ++j)
-        if (j <= a) v_[j] += prm[q++] * y_[a];               // (Linv^T y)_j
+    GMM_BACK_PROJECT(R, q, prm[TRI + q], y_, v_);
 #pragma unroll
     for (int j = 0; j < R; ++j) g_[j] = g_[j] * sc + ex * v_[j];
-    mx = m2;
   }
   const float gm = wave_max(mx);
   const float sc = (mx == -INFINITY) ? 0.f : __expf(mx - gm);   // lanes without a component
@@ -97,7 +75,7 @@ __global__ __launch_bounds__(SLP_THREADS) void slp_optimise_kernel(SlpArgs A) {
   __shared__ float s_gn[SLP_MAX_STEP * R], s_lp[SLP_MAX_STEP];
   __shared__ float s_packed[SLP_LDS_FLOATS];
 
-  constexpr int STRIDE = 1 + R + R * (R + 1) / 2;
+  constexpr int STRIDE = GmmPacked<R>::STRIDE;
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int n = A.n_step, ne = n * R, K = A.K;
   const size_t p = blockIdx.x, base = p * (size_t)ne;

@@ -9,9 +9,8 @@
 `prior.sample(n)`, `prior.prob(pos)` and `prior.log_prob(pos)`.  Like TFP in graph mode they return DEFERRED values which
 `sess.run(...)` evaluates (`Session.run` accepts them next to model handles), so reference-style code such as
 `sess.run(prior.sample(n_embeddings))` or `sess.run(prior.prob(pos)) + 1e-8` (reference :120, :265) runs unchanged.
-Densities of full-covariance mixtures are evaluated by `ladder_gmm_logprob_fwd_bwd` (csrc/elbo.hip, lane = component) for
-R <= 8 and by the dense-GEMM mixture path (`ladder_gmm_dense_logprob_fwd_bwd`) for wider latents; diagonal priors in closed form
-from a handful of numbers.  Sampling is ancestral (component draw + Cholesky), as tfd.Mixture.sample does.
+Densities of full-covariance mixtures are evaluated by `DeviceMixture.log_prob_rows` (mixture.py; csrc/mixture.hip: lane = component
+for R <= 8, the dense-GEMM mixture path for wider latents); diagonal priors in closed form from a handful of numbers.  Sampling is ancestral (component draw + Cholesky), as tfd.Mixture.sample does.
 
 Plotting: the reference's figure helpers are out of scope; `plot_images_and_its_reconstruction` is kept as a thin
 matplotlib call because `get_embeddings_from_val_set` invokes it, and is skipped when matplotlib is missing or `show_plot=False`.
@@ -21,8 +20,8 @@ import math
 import numpy as np
 import torch
 
-from .. import _lib as L
 from ..codes.session import Deferred
+from ..mixture import DeviceMixture
 
 
 def plot_images_and_its_reconstruction(x, x_decoded, config, x_from_t=None, save_plot=False, idx=0):
@@ -113,18 +112,11 @@ class MixturePrior(_Prior):
 
     def __init__(self, engine, weights, means, covs):
         self.eng = engine
-        dev = engine.ctx.device
         self.w = np.asarray(weights, np.float64) / np.sum(weights)
         self.m, self.c = np.asarray(means, np.float64), np.asarray(covs, np.float64)
         self.K, self.R = self.m.shape
-        f = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.float32)).to(dev)
-        w, m, c = f(self.w), f(self.m), f(self.c)
-        self.dense = self.R > 8
-        n = L.query("ladder_gmm_dense_param_floats", self.K, self.R) if self.dense else self.K * L.query("ladder_gmm_packed_stride", self.R)
-        self.packed = torch.empty(n, device=dev)
-        L.call("ladder_gmm_prepare_dense" if self.dense else "ladder_gmm_prepare", w.data_ptr(), m.data_ptr(), c.data_ptr(), self.K, self.R,
-               self.packed.data_ptr(), engine.ctx.stream)
-        torch.cuda.current_stream(dev).synchronize()
+        self.mixture = DeviceMixture(engine.ctx, self.K, self.R)
+        self.mixture.set(self.w, self.m, self.c)
         self._chol = np.linalg.cholesky(self.c)
         self._rng = np.random.default_rng(0)
 
@@ -134,20 +126,9 @@ class MixturePrior(_Prior):
         return (self.m[comp] + np.einsum("nij,nj->ni", self._chol[comp], rng.standard_normal((n, self.R)))).astype(np.float32)
 
     def _log_prob(self, v):
-        """log p of every point of `v` [..., R] in one launch (ladder_gmm_logprob_rows: one wavefront per point, lane = component;
-        wide latents: whitening GEMM + per-row logsumexp, ladder_gmm_dense_logprob_rows)."""
-        shape = v.shape[:-1]
+        """log p of every point of `v` [..., R] in one launch (DeviceMixture.log_prob_rows)."""
         pts = np.ascontiguousarray(v.reshape(-1, self.R), dtype=np.float32)
-        n = pts.shape[0]
-        dev, st = self.eng.ctx.device, self.eng.ctx.stream
-        t, out = torch.as_tensor(pts).to(dev), torch.empty(n, device=dev)
-        if self.dense:
-            ws = torch.empty(L.query("ladder_gmm_dense_workspace_bytes", 1, n, self.R, self.K), dtype=torch.uint8, device=dev)
-            L.call("ladder_gmm_dense_logprob_rows", t.data_ptr(), self.packed.data_ptr(), n, self.R, self.K, out.data_ptr(), ws.data_ptr(),
-                   ws.numel(), st)
-        else:
-            L.call("ladder_gmm_logprob_rows", t.data_ptr(), self.packed.data_ptr(), n, self.R, self.K, out.data_ptr(), st)
-        return out.cpu().numpy().reshape(shape)
+        return self.mixture.log_prob_rows(torch.as_tensor(pts).to(self.eng.ctx.device)).cpu().numpy().reshape(v.shape[:-1])
 
 
 def define_prior_distribution(config, sess, model, gmm_info=None):

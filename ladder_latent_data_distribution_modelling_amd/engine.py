@@ -14,6 +14,7 @@ from . import layers as _layers
 from .comm import Comm, VirtualComm, VirtualGroup, run_virtual_ranks, _NoComm, _DoneWork, _TracedWork  # noqa: F401  (re-exported: tests, bench.py)
 from .layers import (ADAM_B1, ADAM_B2, ADAM_EPS, BN_EPS, DEFAULT_PRECISION, IN_EPS, PRECISION_NOTES, PRECISIONS, BatchNormAct, Conv2D, Ctx, Dense,  # noqa: F401
                      DepthToSpace, InstanceNormStyleAct, ParamStore, PlanesOnly, Resize, _p, _timed, add_, pad_symmetric, plan_decoder)
+from .mixture import DeviceMixture
 from .profiler import KernelProfiler  # noqa: F401
 
 
@@ -358,7 +359,7 @@ class LadderEngine:
         self.noise_seed = int(noise_seed) + 7919 * self.ctx.comm.rank
         self.rng_counter = torch.zeros(1, dtype=torch.int64, device=self.ctx.device)   # Philox stream position (device)
         self._run_calls = 0
-        self._gm_packed = None
+        self.mixture = None                                  # DeviceMixture, once set_mixture() / set_sg_mixture() was called
         self.use_graphs = False
         # filter gradients on a second stream beside the backward chain (config key `overlap_filter_gradients` / environment variable
         # LADDER_OVERLAP_FILTER_GRADIENTS): +0.7-1 % per iteration with the f16x3 kernels, nothing with the fp32 ones (round 4: 3 328 / 3 327 img/s --
@@ -436,17 +437,9 @@ class LadderEngine:
 
     def set_mixture(self, weights, means, covs):
         """Feed of prior_weight / prior_mean / prior_cov (codes/base.py:110-112, 870-888); fp32 like the placeholders."""
-        K, R = self.K, self.R
-        w, m, c = self._dev(weights), self._dev(means), self._dev(covs)
-        assert tuple(w.shape) == (K,) and tuple(m.shape) == (K, R) and tuple(c.shape) == (K, R, R)
-        self._gm_dense = R > 8                               # wide latent (prior "GMM"): whitening as a GEMM on the dense kernel
-        if getattr(self, "_gm_buf", None) is None:           # persistent: captured graphs keep pointing at the current mixture
-            self._gm_buf = self.ctx.empty(L.query("ladder_gmm_dense_param_floats", K, R) if self._gm_dense
-                                          else K * L.query("ladder_gmm_packed_stride", R))
-        L.call("ladder_gmm_prepare_dense" if self._gm_dense else "ladder_gmm_prepare", _p(w), _p(m), _p(c), K, R, _p(self._gm_buf),
-               self.ctx.stream)
-        torch.cuda.current_stream(self.ctx.device).synchronize()   # w, m, c are temporaries: keep them alive until the kernel ran
-        self._gm_packed = self._gm_buf
+        mix = self.mixture or DeviceMixture(self.ctx, self.K, self.R)    # persistent: captured graphs keep pointing at the current mixture
+        mix.set(weights, means, covs)
+        self.mixture = mix
 
     def set_sg_mixture(self):
         """The dummy N(0,I) mixture of the SG-pretraining feed (codes/base.py:870-876)."""
@@ -522,8 +515,6 @@ class LadderEngine:
             self.zhat = zhat
             self.gmm_grads = None
             if "gmm" in parts and not self.hier:
-                if self._gm_packed is None:
-                    raise L.LadderHipError("set_mixture()/set_sg_mixture() must be called before a run that evaluates the GM prior")
                 self.gmm_grads = self._mixture_term(mu_t, sd_t, noise, B)
         ctx.comm.allreduce_(P, "C3 partials")                    # C3: scalar partials of the GLOBAL batch
         ecfg = L.LadderElboCfg(self.Bg, self.D, Z, R, self.Lmc,
@@ -562,31 +553,25 @@ class LadderEngine:
     def _mixture_term(self, mu, sd, noise, B, need_grad=True):
         """MC estimate of E_q[log p_GM] over L samples of N(mu, sd^2) (base.py:308-313 on t, 322-329 on z): writes the sum of
         the log-probs into the partials and returns (sum_l dlogp/dt, sum_l dlogp/dt * eps) for the latent backward."""
-        ctx, st, R, P = self.ctx, self.ctx.stream, self.R, self.partials
-        if self._gm_packed is None:
+        if self.mixture is None:
             raise L.LadderHipError("set_mixture()/set_sg_mixture() must be called before a run that evaluates the GM prior")
-        eps_mc = self._noise(noise, "eps_mc", (self.Lmc, B, R))
-        dmu, dsd = (ctx.empty(B, R), ctx.empty(B, R)) if need_grad else (None, None)
-        if self._gm_dense:
-            wsp, wsn = ctx.ws(L.query("ladder_gmm_dense_workspace_bytes", self.Lmc, B, R, self.K))
-            L.call("ladder_gmm_dense_logprob_fwd_bwd", _p(mu), _p(sd), _p(eps_mc), _p(self._gm_packed), self.Lmc, B, R, self.K,
-                   _p(P[L.P_LOGP:]), _p(dmu), _p(dsd), wsp, wsn, st)
-        else:
-            if dmu is None:
-                dmu, dsd = ctx.empty(B, R), ctx.empty(B, R)
-            wsp, wsn = ctx.ws(L.query("ladder_gmm_workspace_bytes", self.Lmc, B))
-            # (flop count of the profiler entry: two Mahalanobis passes + the gradient accumulation per component evaluation)
-            _timed(7700, float(self.Lmc) * B * self.K * (3.0 * R * (R + 1) + 4.0 * R + 8.0), "ladder_gmm_logprob_fwd_bwd",
-                   (_p(mu), _p(sd), _p(eps_mc), _p(self._gm_packed), self.Lmc, B, R, self.K, _p(P[L.P_LOGP:]), _p(dmu), _p(dsd), wsp, wsn, st))
-        return dmu, dsd
+        eps_mc = self._noise(noise, "eps_mc", (self.Lmc, B, self.R))
+        return self.mixture.fwd_bwd(mu, sd, eps_mc, self.partials[L.P_LOGP:], need_grad)
 
-    def _vamp_term(self, mu, sd, noise, B):
-        """crossEntropy_prior of the VampPrior (base.py:361-370): encoder pass over the pseudo-inputs -> K diagonal components,
-        then the MC mixture term and its gradients towards both the posterior heads and the components."""
-        ctx, st, Z, K, P = self.ctx, self.ctx.stream, self.Z, self.K, self.partials
+    def _vamp_components(self):
+        """The K diagonal components of the VampPrior as they are NOW: encoder pass over the pseudo-inputs, then the latent head with
+        zero noise -> (means, std devs, raw std-dev head output, the zero noise), each [K, Z]."""
+        ctx, Z, K = self.ctx, self.Z, self.K
         mu_p, sdraw_p = self.encoder_p.forward(self.ps.w["prior/Variable"])
         eps0, sd_p, scratch = ctx.zeros(K, Z), ctx.empty(K, Z), ctx.zeros(4)
-        L.call("ladder_latent_fwd", _p(mu_p), _p(sdraw_p), _p(eps0), self.lvp, None, _p(sd_p), _p(scratch), _p(scratch[1:]), None, K, Z, st)
+        L.call("ladder_latent_fwd", _p(mu_p), _p(sdraw_p), _p(eps0), self.lvp, None, _p(sd_p), _p(scratch), _p(scratch[1:]), None, K, Z, ctx.stream)
+        return mu_p, sd_p, sdraw_p, eps0
+
+    def _vamp_term(self, mu, sd, noise, B):
+        """crossEntropy_prior of the VampPrior (base.py:361-370): the components at the pseudo-inputs, then the MC mixture term and its
+        gradients towards both the posterior heads and the components."""
+        ctx, st, Z, K, P = self.ctx, self.ctx.stream, self.Z, self.K, self.partials
+        mu_p, sd_p, sdraw_p, eps0 = self._vamp_components()
         eps_mc = self._noise(noise, "eps_mc", (self.Lmc, B, Z))
         dmu, dsd, dcm, dcs = ctx.empty(B, Z), ctx.empty(B, Z), ctx.empty(K, Z), ctx.empty(K, Z)
         wsp, wsn = ctx.ws(L.query("ladder_diag_mixture_workspace_bytes", B, Z, K))
@@ -807,8 +792,8 @@ class LadderEngine:
         xin = self._dev(x)
         cache = getattr(self, "_enc_cache", None)
         reuse = bool(reuse_encoder and cache is not None and cache[0] == self.ps.step["ae"] and cache[4] == tok)
-        key = (kind, bool(use_sg), bool(use_mask), tuple(xin.shape), cache[2].data_ptr() if reuse else 0, self._gm_packed.data_ptr()
-               if self._gm_packed is not None else 0, self.ctx.ws_generation)
+        key = (kind, bool(use_sg), bool(use_mask), tuple(xin.shape), cache[2].data_ptr() if reuse else 0, self.mixture.buf.data_ptr()
+               if self.mixture is not None else 0, self.ctx.ws_generation)
         ent = self._graphs.get(key)
         if ent is None:
             if self._warm.get(key, 0) < 2:                         # eager warm-up: sizes the workspace and the allocator
@@ -873,7 +858,7 @@ class LadderEngine:
         self._run("inner_sigma", x, lr, noise, use_sg, use_mask, reuse_encoder)
 
     def evaluate(self, x, noise=None, use_sg=True, use_mask=False):
-        parts = ("dec", "inner", "gmm") if (((self.has_inner or self.gmm_z) and self._gm_packed is not None) or self.vamp) else ("dec", "inner")
+        parts = ("dec", "inner", "gmm") if (((self.has_inner or self.gmm_z) and self.mixture is not None) or self.vamp) else ("dec", "inner")
         self.forward(x, noise, use_sg, use_mask, parts, keep_acts=False)
 
     # -- generation -----------------------------------------------------------------------------
@@ -916,11 +901,7 @@ class LadderEngine:
             if not self.vamp:
                 raise ValueError("method 'vampPrior' needs the pseudo-inputs; this model's prior is %r" % self.cfg["prior"])
             K, R = self.K, self.Z
-            mu_p, sdraw_p = self.encoder_p.forward(self.ps.w["prior/Variable"])          # as _vamp_term forms the components
-            sd_p, scratch = ctx.empty(K, R), ctx.zeros(4)
-            L.call("ladder_latent_fwd", _p(mu_p), _p(sdraw_p), _p(ctx.zeros(K, R)), self.lvp, None, _p(sd_p), _p(scratch), _p(scratch[1:]), None,
-                   K, R, st)
-            prep, keep = "ladder_mixture_sample_prepare_diag", (mu_p, sd_p)
+            prep, keep = "ladder_mixture_sample_prepare_diag", self._vamp_components()[:2]
         else:
             K, R = 1, int(self.Z if method == "standard_gaussian" else self.cfg["representation_size"])
             prep, keep = "ladder_mixture_sample_prepare_diag", (ctx.zeros(1, R), torch.ones(1, R, dtype=torch.float32, device=ctx.device))

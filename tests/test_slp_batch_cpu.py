@@ -15,7 +15,7 @@ def _slp(R=2, K=5):
     """An interpolator without a device: the checks under test run before the engine is used."""
     from ladder_latent_data_distribution_modelling_amd.codes.interpolation import SLPInterpolator
     slp = object.__new__(SLPInterpolator)
-    slp.eng, slp.K, slp.R, slp.packed = None, K, R, None
+    slp.eng, slp.K, slp.R, slp.mixture = None, K, R, None
     return slp
 
 
