@@ -820,6 +820,41 @@ size_t ladder_moments_state_doubles(int D);
 size_t ladder_moments_workspace_bytes(int n, int D);
 int ladder_moments_accumulate(const float* x, int n, int D, double* state, void* ws, size_t ws_bytes, ladder_stream_t stream);
 
+/* ---------------------------------------------------------------- N18: the EM mixture fit of the baseline "GMM" prior (csrc/emgmm.hip)
+ * sklearn.mixture.GaussianMixture(K, covariance_type='full', max_iter=1000, n_init=1, warm_start=True).fit(z samples) of codes/base.py:101-106
+ * (the object), 699-710 (per-epoch "fast" fit) and 749-767 ("accurate" fit: max_iter 2000 on 20 096 samples), in float64 for 1 <= R <= 64,
+ * 1 <= K <= 64: _estimate_gaussian_parameters (nk + 10 eps), _compute_precision_cholesky, _estimate_log_gaussian_prob, _m_step (weights
+ * renormalised, reg_covar on the diagonal) and the loop of BaseMixture.fit_predict.  Same protocol as ladder_vbgmm_shard_*: per iteration `it`
+ * (0 = the M-step on the hard initial labels, then 1 .. max_iter)
+ *     ladder_emgmm_estep(...)  ->  stats [ladder_emgmm_stats_doubles] = sum log_prob_norm | n_k [K] | sum r x~ [K,R] | sum r x~ x~^T [K,R,R]
+ *     all-reduce(stats, SUM)       (the caller, under data parallelism: X is then this rank's shard)
+ *     ladder_emgmm_mstep(...)  ->  parameters, precisions_cholesky_, lower_bound = stats[0] / N_global OF THIS E-step, |change| < tol, n_iter_
+ * with x~ = x - c, c = fp32 rounding of the global mean from `moments` = [ sum_n x_n [R] | N ] (ladder_emgmm_shift_doubles doubles), which
+ * ladder_emgmm_shift fills for the local samples and the caller all-reduces ONCE per fit.  Second moments use the tiles on and above the diagonal on
+ * v_mfma_f64_16x16x4_f64 and are centred in the M-step.  Every sum has a fixed order (no atomics): same bits on every run.
+ *   state: ladder_emgmm_state_doubles doubles, caller-owned, zero-filled before a cold fit:
+ *     weights [K] | means [K,R] | covariances [K,R,R] | precisions_cholesky [K,R,R] | log_det [K] | component status [K] | lower_bound_, n_iter_,
+ *     converged_ (-1 = a non-positive Cholesky pivot: sklearn raises ValueError there), done.
+ *   state[-1] != 0 ends the fit; all kernels are no-ops from then on, so iterations may be enqueued ahead.  The caller clears state[-2] and state[-1]
+ *   before a warm-started fit, which begins at it = 1 from the stored parameters and the stored lower_bound_.
+ *   labels: hard assignment of the local samples for it = 0 (the one-hot responsibilities go through the same statistics kernels), NULL afterwards.
+ *   ws >= ladder_emgmm_workspace_bytes(N_local, K, R): responsibilities [N,K] float64 | per-slice sums | per-split partial statistics.
+ *   weights [K], means [K,R], covs [K,R,R]: fp32 roundings of the float64 parameters, rewritten by every M-step.
+ * ladder_emgmm_prepare: precisions_cholesky_, log_det and the status for covariances already in `state` (parameters set from outside); a non-positive
+ * pivot sets state[-2] = -1 and state[-1] = 1.
+ * LADDER_E_SHAPE (nothing launched) for R > 64, K > 64, N < 1 or a NULL array; LADDER_E_ALIGN for double arrays off 8 bytes; LADDER_E_WORKSPACE for
+ * a short workspace. */
+size_t ladder_emgmm_state_doubles(int K, int R);
+size_t ladder_emgmm_stats_doubles(int K, int R);
+size_t ladder_emgmm_shift_doubles(int R);
+size_t ladder_emgmm_workspace_bytes(int N, int K, int R);
+int ladder_emgmm_shift(const float* X, int N, int R, double* moments, ladder_stream_t stream);
+int ladder_emgmm_estep(const float* X, int N, int K, int R, const int* labels, const double* state, const double* moments, double* stats, void* ws,
+                       size_t ws_bytes, ladder_stream_t stream);
+int ladder_emgmm_mstep(const double* stats, const double* moments, int K, int R, double* state, double reg_covar, double tol, int max_iter, int it,
+                       float* weights, float* means, float* covs, ladder_stream_t stream);
+int ladder_emgmm_prepare(double* state, int K, int R, ladder_stream_t stream);
+
 /* ---------------------------------------------------------------- helpers */
 /* HOST function (no device work): CRC-32C (Castagnoli) of host memory, crc = 0 to start, chainable.  Used by the
  * tf.train.Saver checkpoint-v2 reader/writer (codes/base.py:37-85: saver_ae / saver_prior) for block and tensor checksums. */

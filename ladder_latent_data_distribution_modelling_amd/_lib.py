@@ -112,6 +112,14 @@ PROTOTYPES = {
     "ladder_vbgmm_shard_moments": (_i, [_p, _i, _i, _p, _p]),
     "ladder_vbgmm_shard_estep": (_i, [_p, _i, _i, _i, _p, _p, _i, _p, _p, _z, _p]),
     "ladder_vbgmm_shard_mstep": (_i, [_p, _p, _i, _i, _p, _i, _d, _d, _d, _d, _i, _i, _p, _p, _p, _p]),
+    "ladder_emgmm_state_doubles": (_z, [_i, _i]),
+    "ladder_emgmm_stats_doubles": (_z, [_i, _i]),
+    "ladder_emgmm_shift_doubles": (_z, [_i]),
+    "ladder_emgmm_workspace_bytes": (_z, [_i, _i, _i]),
+    "ladder_emgmm_shift": (_i, [_p, _i, _i, _p, _p]),
+    "ladder_emgmm_estep": (_i, [_p, _i, _i, _i, _p, _p, _p, _p, _p, _z, _p]),
+    "ladder_emgmm_mstep": (_i, [_p, _p, _i, _i, _p, _d, _d, _i, _i, _p, _p, _p, _p]),
+    "ladder_emgmm_prepare": (_i, [_p, _i, _i, _p]),
     "ladder_axpy": (_i, [_p, _p, _z, _f, _i, _p]),
     "ladder_filter_pack_split_bytes": (_z, [_i, _i, _i, _i]),
     "ladder_filter_pack_split": (_i, [_p, _p, _i, _i, _i, _i, _i, _p]),

@@ -105,7 +105,11 @@ class BaseTrain:
                     self._fed = "sg"
             elif getattr(self, "_fed", None) is not self.gm_params:
                 w, m, c = self.gm_params
-                eng.set_mixture(w, m, np.asarray(c) + 0.01 * np.eye(int(cfg["code_size"])))
+                if isinstance(c, torch.Tensor):          # the device fit (codes/emgmm.py): the jitter is added where the parameters live
+                    c = c + 0.01 * torch.eye(int(cfg["code_size"]), dtype=c.dtype, device=c.device)
+                else:
+                    c = np.asarray(c) + 0.01 * np.eye(int(cfg["code_size"]))
+                eng.set_mixture(w, m, c)
                 self._fed = self.gm_params
             return False, False
         use_sg = self.cur_epoch <= int(cfg["sg_pretraining"])
@@ -207,9 +211,15 @@ class BaseTrain:
     def _sharded_fit(self, gm):
         """C5 as an all-reduce of the mixture's sufficient statistics (default under data parallelism with the device fit; config key
         `gm_fit_mode`: "allreduce_stats" | "replicated" = all-gather the samples and run the same deterministic fit on every rank)."""
-        from .vbgmm import DeviceBayesianGaussianMixture
-        return (self.engine.ctx.comm.on and isinstance(gm, DeviceBayesianGaussianMixture)
+        return (self.engine.ctx.comm.on and self._device_fit(gm)
                 and self.config.get("gm_fit_mode", "allreduce_stats") == "allreduce_stats")
+
+    @staticmethod
+    def _device_fit(gm):
+        """Whether `gm` is one of the device mixtures (variational Bayes on t: codes/vbgmm.py; EM on z: codes/emgmm.py)."""
+        from .emgmm import DeviceGaussianMixture
+        from .vbgmm import DeviceBayesianGaussianMixture
+        return isinstance(gm, (DeviceBayesianGaussianMixture, DeviceGaussianMixture))
 
     def _draw_t_samples(self, iterator, n_batch, space="t", gather=True):
         """t- (or z-) samples of n_batch minibatches as ONE device tensor [n, R]: every rank's, rank-major (rank 0's samples first), from
@@ -226,10 +236,10 @@ class BaseTrain:
             t = torch.cat(parts, 0)
         return t
 
-    def _share_gm(self, gm):
-        """sklearn backend: rank 0 fits on the host, every rank receives (weights, means, covs)."""
+    def _share_gm(self, gm, R):
+        """sklearn backend: rank 0 fits on the host, every rank receives (weights, means, covs) of the R-dimensional mixture."""
         eng = self.engine
-        K, R = int(self.config["n_mixtures"]), int(self.config["representation_size"])
+        K = int(self.config["n_mixtures"])
         buf = torch.zeros(K + K * R + K * R * R, dtype=torch.float64, device=eng.ctx.device)
         if eng.ctx.comm.rank == 0:
             flat = np.concatenate([gm.weights_.ravel(), gm.means_.ravel(), gm.covariances_.ravel()])
@@ -242,8 +252,7 @@ class BaseTrain:
         """-> (weights, means, covs) to feed.  Device backend: every rank runs the same deterministic fit on the same gathered
         samples (only a cold start's k-means labels come from rank 0), the parameters never leave the GPU.  sklearn backend:
         rank 0 fits on a host copy and broadcasts."""
-        from .vbgmm import DeviceBayesianGaussianMixture
-        if isinstance(gm, DeviceBayesianGaussianMixture):
+        if self._device_fit(gm):
             if self._sharded_fit(gm):
                 gm.fit_sharded(samples, self.engine.ctx.comm)      # `samples` = this rank's: statistics are all-reduced per iteration
             else:
@@ -251,7 +260,7 @@ class BaseTrain:
             return gm.weights_dev, gm.means_dev, gm.covariances_dev
         if self.engine.ctx.comm.rank == 0:
             gm.fit(samples.cpu().numpy().astype(np.float64))
-        return self._share_gm(gm)
+        return self._share_gm(gm, int(samples.shape[1]))
 
     def fit_GMM_VI(self, iterator, mode="fast", space="t"):
         self.flush()
@@ -300,35 +309,47 @@ class BaseTrain:
         return samples.cpu().numpy().astype(np.float64)
 
     def _fit_GMM_z(self, iterator, mode):
-        """prior "GMM" (base.py:699-710, 749-789): sklearn EM mixture on z samples, host fit on rank 0 + broadcast."""
-        from sklearn.mixture import GaussianMixture
+        """prior "GMM" (base.py:699-710, 749-789): EM mixture on z samples.  sklearn backend (the default for this prior): host fit on rank 0 +
+        broadcast.  Device backend (`gm_fit_backend: "hip"` set explicitly): codes/emgmm.py through _fit, sharded under data parallelism
+        unless `gm_fit_mode` says "replicated"; the parameters stay on the device."""
         comm = self.engine.ctx.comm
         bs_global = int(self.config["batch_size"]) * comm.world
-        samples = self._draw_t_samples(iterator, (2000 if mode == "fast" else 20000) // bs_global + 1, space="z")
+        n_batch = (2000 if mode == "fast" else 20000) // bs_global + 1
         if mode == "fast":
             gm = self.model.GM_prior_training
+        elif self._device_fit(self.model.GM_prior_training):
+            from .emgmm import DeviceGaussianMixture
+            gm = self.GM_prior_final = DeviceGaussianMixture(
+                n_components=int(self.config["n_mixtures"]), covariance_type="full", max_iter=2000, n_init=1, warm_start=False,
+                random_state=self.config.get("gm_random_state"), device=self.engine.ctx.device,
+                label_broadcast=(lambda t: comm.broadcast_(t, 0)) if comm.on else None)
         else:
+            from sklearn.mixture import GaussianMixture
             gm = self.GM_prior_final = GaussianMixture(n_components=int(self.config["n_mixtures"]), covariance_type="full",
                                                        max_iter=2000, n_init=1, warm_start=False)
-        K, R = int(self.config["n_mixtures"]), int(self.config["code_size"])
-        if comm.rank == 0:
-            gm.fit(samples.cpu().numpy().astype(np.float64))
-        buf = torch.zeros(K + K * R + K * R * R, dtype=torch.float64, device=self.engine.ctx.device)
-        if comm.rank == 0:
-            buf.copy_(torch.as_tensor(np.concatenate([gm.weights_.ravel(), gm.means_.ravel(), gm.covariances_.ravel()])))
-        comm.broadcast_(buf, 0)
-        a = buf.cpu().numpy()
-        w, m, c = a[:K].copy(), a[K:K + K * R].reshape(K, R).copy(), a[K + K * R:].reshape(K, R, R).copy()
-        if mode == "fast":
-            self.gm_params = (w, m, c)
+        sharded = self._sharded_fit(gm)
+        samples = self._draw_t_samples(iterator, n_batch, space="z", gather=not sharded)
+        params = self._fit(gm, samples)
+        if not self._device_fit(gm):
+            w, m, c = params
+        elif mode == "fast":
+            w = params[0].cpu().numpy()                # only the count of active mixtures below needs host values
         else:
-            self.gm_final_params = (w, m, c)
+            w, m, c = gm._unpack()[:3]                 # float64, like sklearn's: one copy of the device state
+        if mode == "fast":
+            self.gm_params = params
+        else:
+            self.gm_final_params = params
             idx = np.flatnonzero(w >= 1e-2)
             if comm.rank == 0:
                 np.savez("{}GM_prior_info.npz".format(self.config["result_dir"]), w_active=w[idx] / np.sum(w[idx]) if len(idx) else w[idx],
                          m_active=m[idx], K_active=c[idx], w_full=w, m_full=m, K_full=c)
                 print("Final fitted prior saved.")
         print("There are {} active mixtures.".format(int(np.sum(w >= 1e-2))))
+        if sharded:                                   # the set the mixture was fitted on, as fit_GMM_VI returns it: one all-gather, rank-major
+            parts = [torch.empty_like(samples) for _ in range(comm.world)]
+            comm.dist.all_gather(parts, samples.contiguous(), group=comm.group)
+            samples = torch.cat(parts, 0)
         return samples.cpu().numpy().astype(np.float64)
 
     def save_variables_VAE(self):
@@ -410,7 +431,7 @@ class BaseTrain_joint(BaseTrain):
             t = m[comp] + np.einsum("nij,nj->ni", Lc[comp], rng.standard_normal((n, m.shape[1])))
             code = eng.decode_representation(t)
         elif cfg["prior"] == "GMM" and self.gm_params is not None:     # ancestral sample of the mixture on z
-            w, m, K = (np.asarray(a, np.float64) for a in self.gm_params)
+            w, m, K = (np.asarray(a.cpu() if isinstance(a, torch.Tensor) else a, np.float64) for a in self.gm_params)
             comp = rng.choice(len(w), size=n, p=np.clip(w, 0, None) / np.clip(w, 0, None).sum())
             Lc = np.linalg.cholesky(K + 0.01 * np.eye(K.shape[-1]))
             code = m[comp] + np.einsum("nij,nj->ni", Lc[comp], rng.standard_normal((n, m.shape[1])))

@@ -1,0 +1,108 @@
+"""Device-resident replacement for the sklearn mixture object of the baseline "GMM" prior (codes/base.py:101-106, 699-710, 749-767).
+
+`DeviceGaussianMixture` keeps sklearn.mixture.GaussianMixture's constructor arguments and fitted attributes (`weights_`, `means_`,
+`covariances_`, `precisions_cholesky_`, `n_iter_`, `lower_bound_`, `converged_`) for the options the reference uses
+(covariance_type='full', init_params='kmeans'; warm_start; n_init restarts), but runs the EM loop in float64 on samples that never
+leave the GPU (csrc/emgmm.hip: 1 <= R <= 64, 1 <= K <= 64), on one GPU or with the samples sharded over the data-parallel ranks.  Only the
+k-means initialisation of a cold fit runs on the host (codes/mixture_fit.py, shared with codes/vbgmm.py), so with the same `random_state` a fit
+reproduces sklearn's to float64 round-off (tests/test_gpu_emgmm.py).
+"""
+import numpy as np
+import torch
+
+from .. import _lib as L
+from . import mixture_fit as MF
+
+
+class DeviceGaussianMixture:
+    def __init__(self, n_components=1, covariance_type="full", tol=1e-3, reg_covar=1e-6, max_iter=100, n_init=1, init_params="kmeans",
+                 weights_init=None, means_init=None, precisions_init=None, warm_start=False, random_state=None, device="cuda:0",
+                 label_broadcast=None):
+        if covariance_type != "full" or init_params != "kmeans":
+            raise NotImplementedError("the HIP fit covers covariance_type='full', init_params='kmeans' (what the reference uses)")
+        if weights_init is not None or means_init is not None or precisions_init is not None:
+            raise NotImplementedError("the HIP fit starts from k-means labels: weights_init / means_init / precisions_init are not supported")
+        self.n_components, self.tol, self.reg_covar, self.max_iter, self.n_init = int(n_components), tol, reg_covar, int(max_iter), int(n_init)
+        self.covariance_type, self.init_params = covariance_type, init_params
+        self.warm_start, self.random_state = warm_start, random_state
+        self.device = torch.device(device)
+        self._label_broadcast = label_broadcast       # data-parallel hook: rank 0's k-means labels -> every rank
+        self._state = None
+
+    # -------------------------------------------------------------------------------------------------------------
+    def fit(self, X, y=None):
+        """X: [N,R] torch tensor on the device (preferred) or array-like."""
+        return self.fit_sharded(X, MF.OneRank(), check_every=16)
+
+    def fit_sharded(self, X_local, comm, check_every=8):
+        """The fit with the samples SHARDED over the data-parallel ranks: `X_local` [N_local, R] are THIS rank's samples, `comm` the engine's
+        communicator.  Per EM iteration: E-step + local statistics, all-reduce of 1 + K (1 + R + R^2) doubles (the sum of log_prob_norm
+        travels with the moments: the lower bound is a global mean), M-step + convergence test, identical on every rank.  The `done` flag
+        lives in device memory and is read every `check_every` iterations; iterations enqueued past the end are no-ops, so the result does
+        not depend on `check_every`.  A cold start takes its k-means labels from rank 0, once; warm starts exchange statistics only."""
+        from sklearn.utils import check_random_state
+        K = self.n_components
+        Xd = MF.device_samples(X_local, self.device)
+        Nl, R = Xd.shape
+        st = torch.cuda.current_stream(self.device).cuda_stream
+        f64 = lambda n: torch.zeros(n, dtype=torch.float64, device=self.device)
+        mom = f64(L.query("ladder_emgmm_shift_doubles", R))                   # [ sum_n x_n | N ]: the shift vector and the global count
+        L.call("ladder_emgmm_shift", Xd.data_ptr(), Nl, R, mom.data_ptr(), st)
+        comm.allreduce_(mom)
+        MF.check_sample_count(int(mom[-1].item()), K)                          # sklearn's check, on the GLOBAL sample count
+        stats = f64(L.query("ladder_emgmm_stats_doubles", K, R))
+        ws = torch.empty(L.query("ladder_emgmm_workspace_bytes", Nl, K, R), dtype=torch.uint8, device=self.device)
+        do_init = not (self.warm_start and self._state is not None and hasattr(self, "converged_"))
+        rs = check_random_state(self.random_state)
+        lib = L.load()
+        estep_fn, mstep_fn = lib.ladder_emgmm_estep, lib.ladder_emgmm_mstep
+
+        def one_fit():
+            state = f64(L.query("ladder_emgmm_state_doubles", K, R)) if do_init else self._state
+            state[-2:] = 0.0                                                   # converged_, done
+            labels = MF.initial_labels(Xd, comm, K, rs, self._label_broadcast) if do_init else None
+            w, m, c = (torch.empty(K, device=self.device), torch.empty(K, R, device=self.device), torch.empty(K, R, R, device=self.device))
+            e_head = (Xd.data_ptr(), Nl, K, R)
+            e_tail = (state.data_ptr(), mom.data_ptr(), stats.data_ptr(), ws.data_ptr(), ws.numel(), st)
+            m_head = (stats.data_ptr(), mom.data_ptr(), K, R, state.data_ptr(), float(self.reg_covar), float(self.tol), self.max_iter)
+            m_tail = (w.data_ptr(), m.data_ptr(), c.data_ptr(), st)
+            MF.iterate_until_done(lambda it: estep_fn(*e_head, labels.data_ptr() if (labels is not None and it == 0) else None, *e_tail),
+                                  lambda it: mstep_fn(*m_head, it, *m_tail), comm.allreduce_ if comm.on else None, stats, state[-1:],
+                                  0 if do_init else 1, self.max_iter, check_every, "EM mixture fit")
+            return state, w, m, c
+
+        self.converged_ = False                                                # (sklearn sets it before the first restart: a failed fit leaves it)
+        best = MF.best_of_restarts(self.n_init if do_init else 1, one_fit)
+        self.lower_bound_, self.n_iter_, self.converged_, self._state, self.weights_dev, self.means_dev, self.covariances_dev = best
+        self._R = R
+        MF.warn_if_not_converged(self.converged_, self.max_iter)
+        return self
+
+    def _prepare_state(self, state, R):
+        """precisions_cholesky_ / log-determinants for the covariances already in `state`; raises sklearn's ValueError on an ill-defined one."""
+        L.call("ladder_emgmm_prepare", state.data_ptr(), self.n_components, R, torch.cuda.current_stream(self.device).cuda_stream)
+        MF.read_tail(state)
+
+    # float64 views of the fitted parameters, as sklearn exposes them (layout: head of csrc/emgmm.hip)
+    def _unpack(self):
+        K, R = self.n_components, self._R
+        s = self._state.cpu().numpy()
+        o = np.cumsum([0, K, K * R, K * R * R, K * R * R])
+        return (s[o[0]:o[1]].copy(), s[o[1]:o[2]].reshape(K, R).copy(), s[o[2]:o[3]].reshape(K, R, R).copy(),
+                s[o[3]:o[4]].reshape(K, R, R).copy())
+
+    @property
+    def weights_(self):
+        return self._unpack()[0]
+
+    @property
+    def means_(self):
+        return self._unpack()[1]
+
+    @property
+    def covariances_(self):
+        return self._unpack()[2]
+
+    @property
+    def precisions_cholesky_(self):
+        return self._unpack()[3]

@@ -1,0 +1,124 @@
+"""What the two device mixture fits share (codes/vbgmm.py: variational Bayes on t, codes/emgmm.py: EM on z): the single-process
+communicator, the k-means labels of a cold start (sklearn.cluster.KMeans on the gathered samples of rank 0, exactly the call
+BaseMixture._initialize_parameters makes), the loop that drives the E-step / all-reduce / M-step launches against the device-side
+`done` flag, the choice among `n_init` restarts and sklearn's messages.  Both state vectors end with the same four doubles:
+lower_bound_, n_iter_, converged_ (-1 = ill-defined covariance), done.
+"""
+import warnings
+
+import numpy as np
+import torch
+
+ILL_DEFINED = ("Fitting the mixture model failed because some components have ill-defined empirical covariance "
+               "(for instance caused by singleton or collapsed samples). Try to decrease the number of "
+               "components, increase reg_covar, or scale the input data.")
+NOT_CONVERGED = ("Best performing initialization did not converge. Try different init parameters, or increase max_iter, "
+                 "tol, or check for degenerate data.")
+
+
+class OneRank:
+    """The communicator of a single-process fit: every exchange is the identity."""
+    on, rank, world = False, 0, 1
+
+    @staticmethod
+    def allreduce_(t):
+        return t
+
+    @staticmethod
+    def broadcast_(t, src):
+        return t
+
+
+def device_samples(X, device):
+    """[N, R] fp32, contiguous, on `device`, from a torch tensor (preferred) or anything array-like."""
+    Xd = X if isinstance(X, torch.Tensor) else torch.as_tensor(np.asarray(X, dtype=np.float32))
+    return Xd.to(device=device, dtype=torch.float32).contiguous()
+
+
+def check_sample_count(n, K):
+    if n < K:
+        raise ValueError("Expected n_samples >= n_components but got n_components = %d, n_samples = %d" % (K, n))
+
+
+def kmeans_labels(X_host, K, rs):
+    from sklearn import cluster
+    return cluster.KMeans(n_clusters=K, n_init=1, random_state=rs).fit(X_host).labels_.astype(np.int32)
+
+
+def _gather_ragged(parts, x, comm):
+    for r, p_ in enumerate(parts):                                               # ranks with different sample counts: one broadcast each
+        if r == comm.rank:
+            p_.copy_(x)
+        comm.broadcast_(p_, r)
+
+
+def gather_samples(Xd, comm):
+    """-> (every rank's samples in rank order, the offset of this rank's slice)."""
+    if not comm.on:
+        return Xd, 0
+    Nl, R = Xd.shape
+    counts = torch.zeros(comm.world, dtype=torch.int64, device=Xd.device)
+    counts[comm.rank] = Nl
+    comm.allreduce_(counts)
+    cl = [int(c) for c in counts.cpu()]
+    parts = [torch.empty(c, R, device=Xd.device) for c in cl]
+    comm.dist.all_gather(parts, Xd, group=comm.group) if len(set(cl)) == 1 else _gather_ragged(parts, Xd, comm)
+    return torch.cat(parts, 0), sum(cl[:comm.rank])
+
+
+def initial_labels(Xd, comm, K, rs, label_broadcast=None, labeller=kmeans_labels):
+    """The hard labels of THIS rank's samples for a cold start: k-means needs every sample -- gathered once (rank order), labelled on
+    rank 0, this rank keeps its slice.  `label_broadcast`: the hook of replicated fits inside a data-parallel job (rank 0's labels)."""
+    allx, off = gather_samples(Xd, comm)
+    lab = torch.empty(allx.shape[0], dtype=torch.int32, device=Xd.device)
+    if comm.rank == 0:
+        lab.copy_(torch.as_tensor(labeller(allx.cpu().numpy().astype(np.float64), K, rs)))
+    comm.broadcast_(lab, 0)
+    if label_broadcast is not None and not comm.on:
+        label_broadcast(lab)
+    return lab[off:off + Xd.shape[0]].contiguous()
+
+
+def iterate_until_done(estep, mstep, exchange, stats, flag, first_it, max_iter, check_every, what):
+    """Enqueues estep(it) / exchange(stats) / mstep(it) for it = first_it, first_it + 1, ... and reads the device-side `done` flag
+    every `check_every` iterations; the kernels are no-ops once it is set, so the result does not depend on `check_every`."""
+    from .. import _lib as L
+    it, done = first_it, False
+    while not done:
+        for _i in range(check_every):
+            rc = estep(it)
+            if exchange is not None:
+                exchange(stats)
+            rc = rc or mstep(it)
+            if rc != 0:
+                raise L.LadderHipError("%s failed: %s (%d)" % (what, L.ERRORS.get(rc, "?"), rc))
+            it += 1
+            if it > max_iter:
+                break
+        done = bool(flag.item() != 0) or it > max_iter                         # (identical on every rank: same all-reduced statistics)
+
+
+def read_tail(state):
+    """(lower_bound_, n_iter_, converged_) of a finished fit -- one host synchronisation; raises sklearn's error on status -1."""
+    tail = state[-4:-1].cpu().numpy()
+    if tail[2] < 0:
+        raise ValueError(ILL_DEFINED)
+    return float(tail[0]), int(tail[1]), bool(tail[2] > 0)
+
+
+def best_of_restarts(n_restarts, run_one):
+    """run_one() -> (state, *payload) of one finished fit; keeps the restart with the largest lower bound.
+    -> (lower_bound_, n_iter_, converged_, state, *payload)."""
+    best = None
+    for _ in range(n_restarts):
+        res = run_one()
+        tail = read_tail(res[0])
+        if best is None or tail[0] > best[0]:
+            best = tail + tuple(res)
+    return best
+
+
+def warn_if_not_converged(converged, max_iter):
+    if not converged and max_iter > 0:
+        from sklearn.exceptions import ConvergenceWarning
+        warnings.warn(NOT_CONVERGED, ConvergenceWarning)

@@ -53,10 +53,19 @@ class BaseModel:
             else:
                 from sklearn.mixture import BayesianGaussianMixture
                 self.GM_prior_training = BayesianGaussianMixture(**kw)
-        elif self.config["prior"] == "GMM":          # base.py:101-106: plain EM mixture on z (R = code_size), host fit
-            from sklearn.mixture import GaussianMixture
-            self.GM_prior_training = GaussianMixture(n_components=int(self.config["n_mixtures"]), covariance_type="full",
-                                                     max_iter=1000, n_init=1, warm_start=True)
+        elif self.config["prior"] == "GMM":          # base.py:101-106: plain EM mixture on z (R = code_size)
+            # The host fit unless the config EXPLICITLY asks for the device one (codes/emgmm.py -> csrc/emgmm.hip): an absent key keeps sklearn here,
+            # unlike "ours" above.
+            kw = dict(n_components=int(self.config["n_mixtures"]), covariance_type="full", max_iter=1000, n_init=1, warm_start=True)
+            if self.config.get("gm_fit_backend") == "hip":
+                from .emgmm import DeviceGaussianMixture
+                comm = self.engine.ctx.comm
+                self.GM_prior_training = DeviceGaussianMixture(
+                    device=self.engine.ctx.device, label_broadcast=(lambda t: comm.broadcast_(t, 0)) if comm.on else None,
+                    random_state=self.config.get("gm_random_state"), **kw)
+            else:
+                from sklearn.mixture import GaussianMixture
+                self.GM_prior_training = GaussianMixture(**kw)
 
     # codes/base.py:37-85 -- two savers: vae-model (encoder+decoder+sigma), prior-model (prior/* + inner sigma).
     # Adam slots / epoch counter are not saved by the reference either.  Format: the reference's own -- a TensorFlow

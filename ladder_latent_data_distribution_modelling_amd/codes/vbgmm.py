@@ -8,25 +8,12 @@ uses (covariance_type='full'; dirichlet_distribution for the per-epoch "fast" fi
 the host (sklearn.cluster.KMeans, exactly the call BaseMixture._initialize_parameters makes), so with the same `random_state`
 a fit reproduces sklearn's to float64 round-off (tests/test_gpu_vbgmm.py).
 """
-import warnings
-
 import numpy as np
 import torch
 
 from .. import _lib as L
-
-
-class _OneRank:
-    """The communicator of a single-process fit: every exchange is the identity."""
-    on, rank, world = False, 0, 1
-
-    @staticmethod
-    def allreduce_(t):
-        return t
-
-    @staticmethod
-    def broadcast_(t, src):
-        return t
+from . import mixture_fit as MF
+from .mixture_fit import OneRank as _OneRank
 
 
 # from this many samples on, fit() runs one E-step launch over 256-sample slices (one workgroup each) + one M-step launch per variational
@@ -53,18 +40,15 @@ class DeviceBayesianGaussianMixture:
 
     # -------------------------------------------------------------------------------------------------------------
     def _kmeans_labels(self, X_host, rs):
-        from sklearn import cluster
-        return cluster.KMeans(n_clusters=self.n_components, n_init=1, random_state=rs).fit(X_host).labels_.astype(np.int32)
+        return MF.kmeans_labels(X_host, self.n_components, rs)
 
     def fit(self, X, y=None):
         """X: [N,R] torch tensor on the device (preferred) or array-like."""
         from sklearn.utils import check_random_state
         K = self.n_components
-        Xd = X if isinstance(X, torch.Tensor) else torch.as_tensor(np.asarray(X, dtype=np.float32))
-        Xd = Xd.to(device=self.device, dtype=torch.float32).contiguous()
+        Xd = MF.device_samples(X, self.device)
         N, R = Xd.shape
-        if N < K:
-            raise ValueError("Expected n_samples >= n_components but got n_components = %d, n_samples = %d" % (K, N))
+        MF.check_sample_count(N, K)
         if N >= SLICED_FIT_MIN_SAMPLES:
             return self.fit_sharded(Xd, _OneRank(), check_every=16)
         wc = 1.0 / K if self.weight_concentration_prior is None else float(self.weight_concentration_prior)
@@ -75,31 +59,24 @@ class DeviceBayesianGaussianMixture:
         st = torch.cuda.current_stream(self.device).cuda_stream
         do_init = not (self.warm_start and self._state is not None and hasattr(self, "converged_"))
         rs = check_random_state(self.random_state)
-        best = None
-        for _ in range(self.n_init if do_init else 1):
+
+        def one_fit():
             state = torch.zeros(nstate, dtype=torch.float64, device=self.device) if do_init else self._state
-            labels = None
-            if do_init:
-                lab = self._kmeans_labels(Xd.cpu().numpy().astype(np.float64), rs)
-                labels = torch.as_tensor(lab).to(self.device)
-                if self._label_broadcast is not None:
-                    self._label_broadcast(labels)
+            labels = self._initial_labels(Xd, _OneRank(), rs) if do_init else None
             w, m, c = (torch.empty(K, device=self.device), torch.empty(K, R, device=self.device), torch.empty(K, R, R, device=self.device))
             L.call("ladder_vbgmm_fit", Xd.data_ptr(), N, K, R, labels.data_ptr() if labels is not None else None, state.data_ptr(),
                    ptype, wc, mp, float(self.reg_covar), float(self.tol), self.max_iter, w.data_ptr(), m.data_ptr(), c.data_ptr(),
                    ws.data_ptr(), ws.numel(), st)
-            tail = state[-4:-1].cpu().numpy()              # the one host sync of the fit: lower_bound_, n_iter_, converged_
-            if tail[2] < 0:
-                raise ValueError("Fitting the mixture model failed because some components have ill-defined empirical covariance "
-                                 "(for instance caused by singleton or collapsed samples). Try to decrease the number of "
-                                 "components, increase reg_covar, or scale the input data.")
-            if best is None or tail[0] > best[0]:
-                best = (float(tail[0]), int(tail[1]), bool(tail[2] > 0), state, w, m, c)
+            return state, w, m, c                          # (the one host sync of the fit: the tail read of best_of_restarts)
+
+        return self._keep(MF.best_of_restarts(self.n_init if do_init else 1, one_fit))
+
+    def _initial_labels(self, Xd, comm, rs):
+        return MF.initial_labels(Xd, comm, self.n_components, rs, self._label_broadcast, labeller=lambda Xh, K, r: self._kmeans_labels(Xh, r))
+
+    def _keep(self, best):
         self.lower_bound_, self.n_iter_, self.converged_, self._state, self.weights_dev, self.means_dev, self.covariances_dev = best
-        if not self.converged_ and self.max_iter > 0:
-            from sklearn.exceptions import ConvergenceWarning
-            warnings.warn("Best performing initialization did not converge. Try different init parameters, or increase max_iter, "
-                          "tol, or check for degenerate data.", ConvergenceWarning)
+        MF.warn_if_not_converged(self.converged_, self.max_iter)
         return self
 
     # -------------------------------------------------------------------------------------------------------------
@@ -113,8 +90,7 @@ class DeviceBayesianGaussianMixture:
         samples, as BaseMixture._initialize_parameters does) -- once; warm starts exchange statistics only."""
         from sklearn.utils import check_random_state
         K = self.n_components
-        Xd = X_local if isinstance(X_local, torch.Tensor) else torch.as_tensor(np.asarray(X_local, dtype=np.float32))
-        Xd = Xd.to(device=self.device, dtype=torch.float32).contiguous()
+        Xd = MF.device_samples(X_local, self.device)
         Nl, R = Xd.shape
         wc = 1.0 / K if self.weight_concentration_prior is None else float(self.weight_concentration_prior)
         mp = 1.0 if self.mean_precision_prior is None else float(self.mean_precision_prior)
@@ -126,78 +102,30 @@ class DeviceBayesianGaussianMixture:
         comm.allreduce_(mom)
         n_glob = torch.full((1,), float(Nl), dtype=torch.float64, device=self.device)
         comm.allreduce_(n_glob)
-        if int(n_glob.item()) < K:                                             # sklearn's check, on the GLOBAL sample count
-            raise ValueError("Expected n_samples >= n_components but got n_components = %d, n_samples = %d" % (K, int(n_glob.item())))
+        MF.check_sample_count(int(n_glob.item()), K)                           # sklearn's check, on the GLOBAL sample count
         stats = f64(L.query("ladder_vbgmm_shard_stats_doubles", K, R))
         ws = torch.empty(L.query("ladder_vbgmm_shard_workspace_bytes", Nl, K, R), dtype=torch.uint8, device=self.device)
         do_init = not (self.warm_start and self._state is not None and hasattr(self, "converged_"))
         rs = check_random_state(self.random_state)
-        best = None
-        for _ in range(self.n_init if do_init else 1):
+        lib = L.load()
+        estep_fn, mstep_fn = lib.ladder_vbgmm_shard_estep, lib.ladder_vbgmm_shard_mstep
+
+        def one_fit():
             state = f64(L.query("ladder_vbgmm_state_doubles", K, R)) if do_init else self._state
             state[-2:] = 0.0                                                   # converged_, done
-            labels = None
-            if do_init:
-                # k-means needs every sample: gathered once (rank order), labelled on rank 0, this rank keeps its slice
-                if comm.on:
-                    counts = torch.zeros(comm.world, dtype=torch.int64, device=self.device)
-                    counts[comm.rank] = Nl
-                    comm.allreduce_(counts)
-                    cl = [int(c) for c in counts.cpu()]
-                    parts = [torch.empty(c, R, device=self.device) for c in cl]
-                    comm.dist.all_gather(parts, Xd, group=comm.group) if len(set(cl)) == 1 else self._gather_ragged(parts, Xd, comm)
-                    allx, off = torch.cat(parts, 0), sum(cl[:comm.rank])
-                else:
-                    allx, off = Xd, 0
-                lab = torch.empty(allx.shape[0], dtype=torch.int32, device=self.device)
-                if comm.rank == 0:
-                    lab.copy_(torch.as_tensor(self._kmeans_labels(allx.cpu().numpy().astype(np.float64), rs)))
-                comm.broadcast_(lab, 0)
-                if self._label_broadcast is not None and not comm.on:          # replicated fits of a data-parallel job: rank 0's labels
-                    self._label_broadcast(lab)
-                labels = lab[off:off + Nl].contiguous()
+            labels = self._initial_labels(Xd, comm, rs) if do_init else None   # rank 0's k-means, once; warm starts exchange statistics only
             w, m, c = (torch.empty(K, device=self.device), torch.empty(K, R, device=self.device), torch.empty(K, R, R, device=self.device))
-            it, done = (0 if do_init else 1), False
             # (the argument lists are constant over the iterations but for `labels` / `it`: bound once, the loop is two foreign calls)
-            lib = L.load()
-            estep, mstep = lib.ladder_vbgmm_shard_estep, lib.ladder_vbgmm_shard_mstep
             e_tail = (state.data_ptr(), ptype, stats.data_ptr(), ws.data_ptr(), ws.numel(), st)
             m_head = (stats.data_ptr(), mom.data_ptr(), K, R, state.data_ptr(), ptype, wc, mp, float(self.reg_covar), float(self.tol), self.max_iter)
             m_tail = (w.data_ptr(), m.data_ptr(), c.data_ptr(), st)
-            xp, exchange = Xd.data_ptr(), (comm.allreduce_ if comm.on else None)
-            flag = state[-1:]
-            while not done:
-                for _i in range(check_every):
-                    rc = estep(xp, Nl, K, R, labels.data_ptr() if (labels is not None and it == 0) else None, *e_tail)
-                    if exchange is not None:
-                        exchange(stats)
-                    rc = rc or mstep(*m_head, it, *m_tail)
-                    if rc != 0:
-                        raise L.LadderHipError("sharded mixture fit failed: %s (%d)" % (L.ERRORS.get(rc, "?"), rc))
-                    it += 1
-                    if it > self.max_iter:
-                        break
-                done = bool(flag.item() != 0) or it > self.max_iter          # (identical on every rank: same all-reduced statistics)
-            tail = state[-4:-1].cpu().numpy()
-            if tail[2] < 0:
-                raise ValueError("Fitting the mixture model failed because some components have ill-defined empirical covariance "
-                                 "(for instance caused by singleton or collapsed samples). Try to decrease the number of "
-                                 "components, increase reg_covar, or scale the input data.")
-            if best is None or tail[0] > best[0]:
-                best = (float(tail[0]), int(tail[1]), bool(tail[2] > 0), state, w, m, c)
-        self.lower_bound_, self.n_iter_, self.converged_, self._state, self.weights_dev, self.means_dev, self.covariances_dev = best
-        if not self.converged_ and self.max_iter > 0:
-            from sklearn.exceptions import ConvergenceWarning
-            warnings.warn("Best performing initialization did not converge. Try different init parameters, or increase max_iter, "
-                          "tol, or check for degenerate data.", ConvergenceWarning)
-        return self
+            xp = Xd.data_ptr()
+            MF.iterate_until_done(lambda it: estep_fn(xp, Nl, K, R, labels.data_ptr() if (labels is not None and it == 0) else None, *e_tail),
+                                  lambda it: mstep_fn(*m_head, it, *m_tail), comm.allreduce_ if comm.on else None, stats, state[-1:],
+                                  0 if do_init else 1, self.max_iter, check_every, "sharded mixture fit")
+            return state, w, m, c
 
-    @staticmethod
-    def _gather_ragged(parts, x, comm):
-        for r, p_ in enumerate(parts):                                           # ranks with different sample counts: one broadcast each
-            if r == comm.rank:
-                p_.copy_(x)
-            comm.broadcast_(p_, r)
+        return self._keep(MF.best_of_restarts(self.n_init if do_init else 1, one_fit))
 
     # float64 views of the fitted parameters, as sklearn exposes them
     def _unpack(self):

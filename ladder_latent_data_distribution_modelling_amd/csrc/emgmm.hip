@@ -1,0 +1,469 @@
+// EM fit of the baseline "GMM" prior on the device (reference codes/base.py:101-106, 699-710, 749-767):
+// sklearn.mixture.GaussianMixture(covariance_type="full", init_params="kmeans") restated in float64 for 1 <= R <= 64, 1 <= K <= 64 -- the functions
+// _estimate_gaussian_parameters, _compute_precision_cholesky, _estimate_log_gaussian_prob, _m_step and the loop of BaseMixture.fit_predict.
+//
+// One EM iteration `it` (0 = the M-step on the hard k-means labels, then 1 .. max_iter) is
+//   emgmm_estep_kernel     a workgroup owns 64 samples; per component k it stages the upper-triangular P_k = precisions_cholesky_[k] in LDS, forms
+//                          y = (x - mu_k) P_k on v_mfma_f64_16x16x4_f64 (the all-zero 16 x 16 blocks below the diagonal are skipped) and reduces |y|^2 per
+//                          row; after the last k: logsumexp per row, responsibilities [N, K] float64, the slice's sum of log_prob_norm.
+//                          it = 0: the responsibilities are the one-hot labels.
+//   emgmm_stats_kernel     grid (component, row split): n_k, sum r x~ and the 16 x 16 blocks on and above the diagonal of sum r x~ x~^T on the same MFMA,
+//                          x~ = x - c with ONE shift vector c for all components (the fp32-rounded global mean: x - c is exact in float64 and the raw
+//                          second moments carry no uncentred cancellation); partials go to the workspace
+//   emgmm_reduce_kernel    adds the partials in the order split 0, 1, ... (and the slices' log_prob_norm sums in slice order) into
+//                          stats = [ sum log_prob_norm | n_k [K] | sum r x~ [K,R] | sum r x~ x~^T [K,R,R] ]; the lower triangle mirrors the upper one
+//   (all-reduce of stats over the data-parallel ranks, by the caller: the lower bound is a GLOBAL mean, so its sum travels with the rest)
+//   emgmm_mstep_kernel     one workgroup per component: weight, mean, covariance centred from the shifted raw moments + reg_covar, Cholesky factor,
+//                          its triangular inverse (precisions_cholesky_), log-determinant, fp32 copies for the engine's feed
+//   emgmm_finish_kernel    lower_bound = sum log_prob_norm / N of THIS iteration's E-step, |change| < tol, n_iter_, converged_ and the `done` flag
+// Every kernel returns at once when `done` is set, so the host may enqueue iterations ahead and read the flag every few iterations (the contract of
+// ladder_vbgmm_shard_*).  No atomics: every sum has one fixed order, so a fit gives the same bits on every run and for every `check_every`.
+//
+// state (doubles): weights [K] | means [K,R] | covariances [K,R,R] | precisions_cholesky [K,R,R] | log_det [K] | component status [K] |
+//                  lower_bound_, n_iter_, converged_ (-1: a non-positive Cholesky pivot, sklearn raises ValueError there), done
+//
+// Operand lane maps of v_mfma_f64_16x16x4_f64: head of csrc/fid.hip (A [m = lane & 15][k = lane >> 4], B [k][n = lane & 15],
+// C/D reg r: row (lane >> 4) + 4 r, col lane & 15).
+#include "common.h"
+
+namespace {
+
+typedef double double4_t __attribute__((ext_vector_type(4)));
+
+constexpr int EM_MAXR = 64, EM_MAXK = 64;
+constexpr int EM_SLICE = 64;            // samples per E-step workgroup: 4 wavefronts x 16 MFMA rows
+constexpr int EM_LDP = 80;              // LDS row pitch of the staged P_k in doubles: the four k-rows of one B operand fall into different bank halves
+constexpr int EM_LDC = 65;              // LDS row pitch of the M-step's factorisation (odd: a thread per row or per column walks distinct banks)
+constexpr int EM_MAX_SPLITS = 32, EM_MIN_SPLIT_ROWS = 128;
+constexpr double EM_EPS10 = 10.0 * 2.220446049250313e-16;        // 10 * np.finfo(float64).eps
+constexpr double EM_LOG_2PI = 1.8378770664093453;
+
+struct EmState {
+  double *w, *means, *cov, *pchol, *logdet, *cstat, *tail;
+  __host__ __device__ EmState(double* s, int K, int R) {
+    w = s;
+    means = w + K;
+    cov = means + (size_t)K * R;
+    pchol = cov + (size_t)K * R * R;
+    logdet = pchol + (size_t)K * R * R;
+    cstat = logdet + K;
+    tail = cstat + K;
+  }
+};
+
+__host__ __device__ inline size_t em_state_doubles(int K, int R) { return (size_t)K * (3 + R + 2 * (size_t)R * R) + 4; }
+__host__ __device__ inline size_t em_stats_doubles(int K, int R) { return 1 + (size_t)K * (1 + R + (size_t)R * R); }
+inline int em_slices(int N) { return (N + EM_SLICE - 1) / EM_SLICE; }
+
+struct EmSplit {
+  int rows, nsplit;                    // rows per split (a multiple of 4), row splits
+};
+inline EmSplit em_split(int N) {
+  EmSplit p;
+  int rows = (N + EM_MAX_SPLITS - 1) / EM_MAX_SPLITS;
+  rows = rows < EM_MIN_SPLIT_ROWS ? EM_MIN_SPLIT_ROWS : rows;
+  p.rows = (rows + 3) / 4 * 4;
+  p.nsplit = (N + p.rows - 1) / p.rows;
+  return p;
+}
+
+// moments = [ sum_n x_n [R] | N ], all-reduced by the caller: the shift is the GLOBAL mean rounded to fp32, the same on every rank
+__device__ __forceinline__ double em_shift(const double* mom, int R, int j) { return (double)(float)(mom[j] / mom[R]); }
+
+// ------------------------------------------------------------------------------------------------ column sums for the shift
+// One workgroup per column: thread-strided partial sums, the shuffle tree, then the four wavefronts in order.
+__global__ __launch_bounds__(256) void emgmm_shift_kernel(const float* __restrict__ X, int N, int R, double* __restrict__ mom) {
+  const int j = blockIdx.x, tid = threadIdx.x;
+  __shared__ double s_red[4];
+  double a = 0.0;
+  for (int n = tid; n < N; n += 256) a += (double)X[(size_t)n * R + j];
+  a = wave_sum_d(a);
+  if ((tid & 63) == 0) s_red[tid >> 6] = a;
+  __syncthreads();
+  if (tid == 0) {
+    mom[j] = ((s_red[0] + s_red[1]) + s_red[2]) + s_red[3];
+    if (j == 0) mom[R] = (double)N;
+  }
+}
+
+// ------------------------------------------------------------------------------------------------ E-step
+__global__ __launch_bounds__(256) void emgmm_estep_kernel(const float* __restrict__ X, const int* __restrict__ labels, const double* state, int N, int K,
+                                                          int R, double* resp, double* __restrict__ lpn_part) {
+  EmState S(const_cast<double*>(state), K, R);
+  if (S.tail[3] != 0.0) return;                                    // the fit is over: iterations enqueued past the end are no-ops
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, m = lane & 15, kq = lane >> 4;
+  const int n0 = blockIdx.x * EM_SLICE, rows = min(EM_SLICE, N - n0);
+  if (labels != nullptr) {                                         // iteration 0: hard labels, through the same statistics kernels
+    for (int i = tid; i < rows * K; i += 256) {
+      const int r = i / K, k = i - r * K;
+      resp[(size_t)(n0 + r) * K + k] = (labels[n0 + r] == k) ? 1.0 : 0.0;
+    }
+    if (tid == 0) lpn_part[blockIdx.x] = 0.0;
+    return;
+  }
+  __shared__ double s_P[EM_MAXR * EM_LDP], s_mu[EM_MAXR], s_ld[EM_MAXK], s_lw[EM_MAXK];
+  const int nb = (R + 15) / 16, Rp = nb * 16, nsteps = (R + 3) / 4;
+  const int row = wave * 16 + m;
+  const bool rv = row < rows;
+  const float* xr = X + (size_t)(n0 + (rv ? row : 0)) * R;         // (row n0 exists: never dereferenced unless rv)
+  double xa[16];                                                   // this lane's A operands: x[row][4 s + kq], zero past R
+#pragma unroll
+  for (int s = 0; s < 16; ++s) {
+    const int i = 4 * s + kq;
+    xa[s] = (rv && i < R) ? (double)xr[i] : 0.0;
+  }
+  if (tid < K) {
+    s_ld[tid] = S.logdet[tid];
+    s_lw[tid] = log(S.w[tid]);
+  }
+  for (int k = 0; k < K; ++k) {
+    __syncthreads();                                               // (the previous component's operands are no longer read)
+    const double* P = S.pchol + (size_t)k * R * R;
+    for (int idx = tid; idx < Rp * Rp; idx += 256) {
+      const int i = idx / Rp, j = idx - i * Rp;
+      s_P[i * EM_LDP + j] = (i < R && j < R) ? P[i * R + j] : 0.0;
+    }
+    if (tid < EM_MAXR) s_mu[tid] = tid < R ? S.means[k * R + tid] : 0.0;
+    __syncthreads();
+    double q4[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int jb = 0; jb < 4; ++jb) {
+      if (jb < nb) {                                               // (uniform: every lane reaches every MFMA)
+        double4_t acc = double4_t{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+        for (int s = 0; s < 4 * (jb + 1); ++s) {                   // P is upper triangular: rows past 16 jb + 15 of this column block are zero
+          if (s < nsteps) {
+            const int i = 4 * s + kq;
+            acc = __builtin_amdgcn_mfma_f64_16x16x4f64(xa[s] - s_mu[i], s_P[i * EM_LDP + 16 * jb + m], acc, 0, 0, 0);
+          }
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) q4[r] += acc[r] * acc[r];
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+#pragma unroll
+      for (int o = 1; o < 16; o <<= 1) q4[r] += __shfl_xor(q4[r], o, 64);    // over the 16 columns of the lane group: the same bits in every lane
+    if (m == 0) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int rr = wave * 16 + kq + 4 * r;
+        if (rr < rows) resp[(size_t)(n0 + rr) * K + k] = (-0.5 * (R * EM_LOG_2PI + q4[r]) + s_ld[k]) + s_lw[k];
+      }
+    }
+  }
+  __syncthreads();
+  double lpn = 0.0;
+  if (tid < rows) {
+    double* wr = resp + (size_t)(n0 + tid) * K;
+    double mx = -INFINITY;
+    for (int k = 0; k < K; ++k) mx = fmax(mx, wr[k]);
+    double se = 0.0;
+    for (int k = 0; k < K; ++k) se += exp(wr[k] - mx);
+    lpn = log(se) + mx;
+    for (int k = 0; k < K; ++k) wr[k] = exp(wr[k] - lpn);
+  }
+  if (wave == 0) {
+    lpn = wave_sum_d(lpn);
+    if (lane == 0) lpn_part[blockIdx.x] = lpn;
+  }
+}
+
+// ------------------------------------------------------------------------------------------------ statistics
+// blockIdx.x = component, blockIdx.y = row split.  Wavefront w owns rows 16 w .. 16 w + 15 of the R x R moment: the column blocks q >= w as MFMA
+// accumulators, plus one block whose B operand is the unit column e_0, which collects sum r x~ in its column 0.  Operands come straight from global memory.
+__global__ __launch_bounds__(256) void emgmm_stats_kernel(const float* __restrict__ X, const double* __restrict__ resp, const double* __restrict__ state,
+                                                          const double* __restrict__ mom, int N, int K, int R, int rows, double* __restrict__ part) {
+  EmState S(const_cast<double*>(state), K, R);
+  if (S.tail[3] != 0.0) return;
+  const int k = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, m = lane & 15, kq = lane >> 4;
+  const int nb = (R + 15) / 16;
+  if (wave >= nb) return;                                          // (whole wavefronts; no barrier in this kernel)
+  const int ia = wave * 16 + m;
+  const bool va = ia < R;
+  const double ca = va ? em_shift(mom, R, ia) : 0.0;
+  int jb[4];
+  bool vb[4];
+  double cb[4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    jb[q] = 16 * q + m;
+    vb[q] = jb[q] < R;
+    cb[q] = vb[q] ? em_shift(mom, R, jb[q]) : 0.0;
+  }
+  const double e0 = (m == 0) ? 1.0 : 0.0;
+  const int r0 = blockIdx.y * rows, r1 = min(N, r0 + rows);
+  double4_t acc[4], acc1 = double4_t{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+  for (int q = 0; q < 4; ++q) acc[q] = double4_t{0.0, 0.0, 0.0, 0.0};
+  double nk = 0.0;
+  for (int r = r0; r < r1; r += 4) {                               // (uniform trip count)
+    const int row = r + kq;
+    const bool ok = row < r1;
+    const float* xr = X + (size_t)(ok ? row : r0) * R;
+    const double rr = ok ? resp[(size_t)row * K + k] : 0.0;
+    nk += rr;
+    const double a = (ok && va) ? rr * ((double)xr[ia] - ca) : 0.0;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      if (q >= wave && q < nb) {
+        const double b = (ok && vb[q]) ? (double)xr[jb[q]] - cb[q] : 0.0;
+        acc[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc[q], 0, 0, 0);
+      }
+    }
+    acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(a, e0, acc1, 0, 0, 0);
+  }
+  double* out = part + (size_t)blockIdx.y * em_stats_doubles(K, R);
+  double* p_nk = out + 1;
+  double* p_x = p_nk + K + (size_t)k * R;
+  double* p_xx = out + 1 + K + (size_t)K * R + (size_t)k * R * R;
+  if (wave == 0) {                                                 // n_k: the rows r0 + kq + 4 t of lane group kq, then the four groups in order
+    const double g0 = __shfl(nk, 0, 64), g1 = __shfl(nk, 16, 64), g2 = __shfl(nk, 32, 64), g3 = __shfl(nk, 48, 64);
+    if (lane == 0) p_nk[k] = ((g0 + g1) + g2) + g3;
+  }
+#pragma unroll
+  for (int rg = 0; rg < 4; ++rg) {
+    const int i = wave * 16 + kq + 4 * rg;
+    if (i >= R) continue;
+    if (m == 0) p_x[i] = acc1[rg];
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+      if (q >= wave && q < nb && vb[q]) p_xx[(size_t)i * R + jb[q]] = acc[q][rg];
+  }
+}
+
+// stats[e] = sum over the splits in index order; of the second moments only [i][j], i <= j, was computed: the lower triangle reads its mirror, so the
+// moment is exactly symmetric.  Element 0 = the slices' log_prob_norm sums in slice order.
+__global__ __launch_bounds__(256) void emgmm_reduce_kernel(const double* __restrict__ part, const double* __restrict__ lpn_part, const double* __restrict__ state,
+                                                           int K, int R, int nsplit, int nslices, double* __restrict__ stats) {
+  EmState S(const_cast<double*>(state), K, R);
+  if (S.tail[3] != 0.0) return;
+  const size_t n = em_stats_doubles(K, R), e = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= n) return;
+  double a = 0.0;
+  if (e == 0) {
+    for (int g = 0; g < nslices; ++g) a += lpn_part[g];
+  } else {
+    size_t src = e;
+    const size_t xx0 = 1 + (size_t)K + (size_t)K * R;
+    if (e >= xx0) {
+      const size_t q = e - xx0, kk = q / ((size_t)R * R), ij = q - kk * R * R, i = ij / R, j = ij - i * R;
+      if (j < i) src = xx0 + kk * R * R + j * R + i;
+    }
+    for (int s = 0; s < nsplit; ++s) a += part[(size_t)s * n + src];
+  }
+  stats[e] = a;
+}
+
+// ------------------------------------------------------------------------------------------------ M-step
+// _compute_precision_cholesky for one component, by ONE wavefront (64 threads): A [R][EM_LDC] in LDS holds the covariance on entry.  Left-looking
+// Cholesky, thread i = row i; then the triangular inverse, thread c = column c of L^-1, kept in the strict upper triangle of A (A[c][i] = L^-1[i][c]) beside L.
+// Writes precisions_cholesky_[k] (upper triangular), its log-determinant and the component status (-1: a non-positive pivot).
+__device__ void em_prepare_component(double* A, int R, int k, EmState& S, int tid) {
+  __shared__ double s_d;
+  __shared__ int s_bad;
+  if (tid == 0) s_bad = 0;
+  for (int j = 0; j < R; ++j) {
+    double v = 0.0;
+    if (tid >= j && tid < R) {
+      v = A[tid * EM_LDC + j];
+      for (int p = 0; p < j; ++p) v -= A[tid * EM_LDC + p] * A[j * EM_LDC + p];
+      if (tid == j) s_d = v;
+    }
+    __syncthreads();
+    double d = s_d;
+    if (!(d > 0.0)) {                                              // sklearn: LinAlgError -> ValueError("... ill-defined empirical covariance ...")
+      if (tid == j) s_bad = 1;
+      d = 1.0;
+    }
+    const double ljj = sqrt(d);
+    if (tid == j) A[j * EM_LDC + j] = ljj;
+    else if (tid > j && tid < R) A[tid * EM_LDC + j] = v / ljj;
+    __syncthreads();
+  }
+  double* Pk = S.pchol + (size_t)k * R * R;
+  if (tid < R) {
+    const int c = tid;
+    const double xc = 1.0 / A[c * EM_LDC + c];
+    for (int i = c + 1; i < R; ++i) {
+      double v = -A[i * EM_LDC + c] * xc;
+      for (int p = c + 1; p < i; ++p) v -= A[i * EM_LDC + p] * A[c * EM_LDC + p];
+      A[c * EM_LDC + i] = v / A[i * EM_LDC + i];
+    }
+    for (int i = 0; i < R; ++i) Pk[c * R + i] = (i < c) ? 0.0 : (i == c ? xc : A[c * EM_LDC + i]);
+  }
+  __syncthreads();
+  if (tid == 0) {
+    double ld = 0.0;
+    for (int j = 0; j < R; ++j) ld += log(1.0 / A[j * EM_LDC + j]);
+    S.logdet[k] = ld;
+    S.cstat[k] = s_bad ? -1.0 : 0.0;
+  }
+}
+
+__global__ __launch_bounds__(64) void emgmm_mstep_kernel(const double* __restrict__ stats, const double* __restrict__ mom, double* state, int K, int R,
+                                                         double reg_covar, int it, float* __restrict__ w_out, float* __restrict__ m_out,
+                                                         float* __restrict__ c_out) {
+  EmState S(state, K, R);
+  if (S.tail[3] != 0.0) return;
+  const int k = blockIdx.x, tid = threadIdx.x;
+  __shared__ double s_A[EM_MAXR * EM_LDC], s_s1[EM_MAXR], s_dm[EM_MAXR];
+  const double* st_nk = stats + 1;
+  const double* st_x = st_nk + K + (size_t)k * R;
+  const double* st_xx = stats + 1 + K + (size_t)K * R + (size_t)k * R * R;
+  const double nk_raw = st_nk[k], nk = nk_raw + EM_EPS10;          // nk = resp.sum(axis=0) + 10 * eps
+  if (tid == 0) {
+    double w;
+    if (it == 0) {
+      w = nk / mom[R];                                             // _initialize: weights = nk / n_samples
+    } else {
+      double tot = 0.0;                                            // _m_step: weights_ = nk; weights_ /= weights_.sum()
+      for (int j = 0; j < K; ++j) tot += st_nk[j] + EM_EPS10;
+      w = nk / tot;
+    }
+    S.w[k] = w;
+    w_out[k] = (float)w;
+  }
+  if (tid < R) {
+    const double c = em_shift(mom, R, tid), s1 = st_x[tid];
+    const double mean = (s1 + c * nk_raw) / nk;                    // = sum r x / nk
+    s_s1[tid] = s1;
+    s_dm[tid] = mean - c;
+    S.means[k * R + tid] = mean;
+    m_out[k * R + tid] = (float)mean;
+  }
+  __syncthreads();
+  // sum r (x - mean)(x - mean)^T = S2 - s1 d^T - d s1^T + n_k d d^T with d = mean - c; [i][j] for i <= j, mirrored
+  double* C = S.cov + (size_t)k * R * R;
+  float* Cf = c_out + (size_t)k * R * R;
+  for (int e = tid; e < R * R; e += 64) {
+    const int i = e / R, j = e - i * R;
+    if (j < i) continue;
+    double v = st_xx[e] - (s_s1[i] * s_dm[j] + s_dm[i] * s_s1[j]) + nk_raw * s_dm[i] * s_dm[j];
+    v = v / nk + (i == j ? reg_covar : 0.0);
+    s_A[i * EM_LDC + j] = v;
+    s_A[j * EM_LDC + i] = v;
+    C[i * R + j] = v;
+    C[j * R + i] = v;
+    Cf[i * R + j] = (float)v;
+    Cf[j * R + i] = (float)v;
+  }
+  __syncthreads();
+  em_prepare_component(s_A, R, k, S, tid);
+}
+
+// precisions_cholesky_ / log-determinant / status of the covariances already IN the state (parameters set from outside)
+__global__ __launch_bounds__(64) void emgmm_prepare_kernel(double* state, int K, int R) {
+  EmState S(state, K, R);
+  const int k = blockIdx.x, tid = threadIdx.x;
+  __shared__ double s_A[EM_MAXR * EM_LDC];
+  const double* C = S.cov + (size_t)k * R * R;
+  for (int e = tid; e < R * R; e += 64) s_A[(e / R) * EM_LDC + (e % R)] = C[e];
+  __syncthreads();
+  em_prepare_component(s_A, R, k, S, tid);
+}
+
+// The end of iteration `it`, one thread: component status, lower bound of this iteration's E-step, convergence test, n_iter_.
+// it < 0: after emgmm_prepare_kernel -- only the status is folded into the tail.
+__global__ void emgmm_finish_kernel(const double* __restrict__ stats, const double* __restrict__ mom, double* state, int K, int R, double tol, int max_iter,
+                                    int it) {
+  EmState S(state, K, R);
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  if (it >= 0 && S.tail[3] != 0.0) return;
+  bool bad = false;
+  for (int k = 0; k < K; ++k) bad = bad || (S.cstat[k] < 0.0);
+  if (bad) {
+    S.tail[2] = -1.0;
+    S.tail[3] = 1.0;
+    return;
+  }
+  if (it < 0) return;
+  if (it == 0) {
+    S.tail[0] = -INFINITY;                                         // a cold start has no lower bound yet
+    S.tail[1] = 0.0;
+    if (max_iter == 0) S.tail[3] = 1.0;
+    return;
+  }
+  const double lb = stats[0] / mom[R];                             // np.mean(log_prob_norm) over ALL samples
+  const bool conv = fabs(lb - S.tail[0]) < tol;
+  S.tail[0] = lb;
+  S.tail[1] = (double)it;
+  if (conv) {
+    S.tail[2] = 1.0;
+    S.tail[3] = 1.0;
+  } else if (it >= max_iter) {
+    S.tail[3] = 1.0;
+  }
+}
+
+inline bool em_misaligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7u) != 0; }
+
+}  // namespace
+
+extern "C" {
+
+size_t ladder_emgmm_state_doubles(int K, int R) { return (K < 1 || R < 1) ? 0 : em_state_doubles(K, R); }
+size_t ladder_emgmm_stats_doubles(int K, int R) { return (K < 1 || R < 1) ? 0 : em_stats_doubles(K, R); }
+size_t ladder_emgmm_shift_doubles(int R) { return R < 1 ? 0 : (size_t)R + 1; }
+
+size_t ladder_emgmm_workspace_bytes(int N, int K, int R) {
+  if (N < 1 || K < 1 || R < 1) return 0;
+  // responsibilities [N, K] | per-slice log_prob_norm sums | per-split partial statistics
+  return ((size_t)N * K + (size_t)em_slices(N) + (size_t)em_split(N).nsplit * em_stats_doubles(K, R)) * sizeof(double);
+}
+
+int ladder_emgmm_shift(const float* X, int N, int R, double* moments, ladder_stream_t stream) {
+  if (X == nullptr || moments == nullptr || N < 1 || R < 1 || R > EM_MAXR) return LADDER_E_SHAPE;
+  if (em_misaligned(moments)) return LADDER_E_ALIGN;
+  hipLaunchKernelGGL(emgmm_shift_kernel, dim3(R), dim3(256), 0, stream, X, N, R, moments);
+  LADDER_CHECK_LAUNCH();
+  return LADDER_OK;
+}
+
+int ladder_emgmm_estep(const float* X, int N, int K, int R, const int* labels, const double* state, const double* moments, double* stats, void* ws,
+                       size_t ws_bytes, ladder_stream_t stream) {
+  if (X == nullptr || state == nullptr || moments == nullptr || stats == nullptr || N < 1 || K < 1 || K > EM_MAXK || R < 1 || R > EM_MAXR)
+    return LADDER_E_SHAPE;
+  if (em_misaligned(state) || em_misaligned(moments) || em_misaligned(stats) || em_misaligned(ws)) return LADDER_E_ALIGN;
+  if (ws == nullptr || ws_bytes < ladder_emgmm_workspace_bytes(N, K, R)) return LADDER_E_WORKSPACE;
+  const EmSplit sp = em_split(N);
+  const int G = em_slices(N);
+  const size_t n = em_stats_doubles(K, R);
+  double* resp = static_cast<double*>(ws);
+  double* lpn_part = resp + (size_t)N * K;
+  double* part = lpn_part + G;
+  hipLaunchKernelGGL(emgmm_estep_kernel, dim3(G), dim3(256), 0, stream, X, labels, state, N, K, R, resp, lpn_part);
+  LADDER_CHECK_LAUNCH();
+  hipLaunchKernelGGL(emgmm_stats_kernel, dim3(K, sp.nsplit), dim3(256), 0, stream, X, (const double*)resp, state, moments, N, K, R, sp.rows, part);
+  LADDER_CHECK_LAUNCH();
+  hipLaunchKernelGGL(emgmm_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, (const double*)part, (const double*)lpn_part, state, K, R,
+                     sp.nsplit, G, stats);
+  LADDER_CHECK_LAUNCH();
+  return LADDER_OK;
+}
+
+int ladder_emgmm_mstep(const double* stats, const double* moments, int K, int R, double* state, double reg_covar, double tol, int max_iter, int it,
+                       float* weights, float* means, float* covs, ladder_stream_t stream) {
+  if (stats == nullptr || moments == nullptr || state == nullptr || weights == nullptr || means == nullptr || covs == nullptr || K < 1 || K > EM_MAXK ||
+      R < 1 || R > EM_MAXR || max_iter < 0 || it < 0)
+    return LADDER_E_SHAPE;
+  if (em_misaligned(stats) || em_misaligned(moments) || em_misaligned(state)) return LADDER_E_ALIGN;
+  hipLaunchKernelGGL(emgmm_mstep_kernel, dim3(K), dim3(64), 0, stream, stats, moments, state, K, R, reg_covar, it, weights, means, covs);
+  LADDER_CHECK_LAUNCH();
+  hipLaunchKernelGGL(emgmm_finish_kernel, dim3(1), dim3(64), 0, stream, stats, moments, state, K, R, tol, max_iter, it);
+  LADDER_CHECK_LAUNCH();
+  return LADDER_OK;
+}
+
+int ladder_emgmm_prepare(double* state, int K, int R, ladder_stream_t stream) {
+  if (state == nullptr || K < 1 || K > EM_MAXK || R < 1 || R > EM_MAXR) return LADDER_E_SHAPE;
+  if (em_misaligned(state)) return LADDER_E_ALIGN;
+  hipLaunchKernelGGL(emgmm_prepare_kernel, dim3(K), dim3(64), 0, stream, state, K, R);
+  LADDER_CHECK_LAUNCH();
+  hipLaunchKernelGGL(emgmm_finish_kernel, dim3(1), dim3(64), 0, stream, (const double*)nullptr, (const double*)nullptr, state, K, R, 0.0, 0, -1);
+  LADDER_CHECK_LAUNCH();
+  return LADDER_OK;
+}
+
+}  // extern "C"
