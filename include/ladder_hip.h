@@ -855,6 +855,36 @@ int ladder_emgmm_mstep(const double* stats, const double* moments, int K, int R,
                        float* weights, float* means, float* covs, ladder_stream_t stream);
 int ladder_emgmm_prepare(double* state, int K, int R, ladder_stream_t stream);
 
+/* ---------------------------------------------------------------- N19: k-means, the labels of a cold mixture fit (csrc/kmeans.hip)
+ * cluster.KMeans(n_clusters=K, n_init=1, random_state=rs).fit(samples).labels_ -- the call BaseMixture._initialize_parameters makes for the mixture
+ * objects of codes/base.py:93-106 on every cold fit -- in float64 on fp32 samples X [N,R] for 1 <= R <= 64, 1 <= K <= 64, N >= K: _kmeans_plusplus,
+ * Lloyd's iteration, _relocate_empty_clusters_dense and the convergence test of _kmeans_single_lloyd.  The samples are shifted by the fp32-rounded
+ * global mean; no floating-point atomics, every sum has one fixed order: same bits on every run.
+ *   ladder_kmeans_seed         k-means++.  draws (DEVICE, ladder_kmeans_draws_doubles(K) doubles) = index of the first centre | uniforms in [0,1)
+ *                              [K-1, n_trials], n_trials = 2 + int(ln K), from the host's generator.  2 K + 3 launches, no host synchronisation.
+ *   ladder_kmeans_set_centres  explicit initial centres [K,R] (DEVICE doubles): sklearn's init = array.
+ *   then for it = 1, 2, ...:   ladder_kmeans_assign(it) (labels, squared distances, counts; |c|^2 - 2 x.c on v_mfma_f64_16x16x4_f64, lowest index wins) and
+ *                              ladder_kmeans_update(it) (cluster sums on the same MFMA, relocation of empty clusters, new centres, the test: labels unchanged
+ *                              -> done; shift <= tol * mean(var(X, axis=0)) or it == max_iter -> the NEXT pair is the final assignment and sets `done`, so
+ *                              up to max_iter + 1 pairs are enqueued).  state[-1] != 0 ends the fit; all kernels are no-ops from then on.
+ *   Several empty clusters in one iteration: ascending cluster index receives the farthest samples in descending distance (lowest index among equals);
+ *   sklearn's own order there comes from numpy.argpartition and is unspecified.  One empty cluster: sklearn's result.
+ *   state: ladder_kmeans_state_doubles doubles = centres [K,R] | inertia_, n_iter_, status (1 shift <= tol_, 2 labels unchanged, 3 max_iter), done;
+ *   written by seed / set_centres.  labels [N] int32: read as the previous labels when it > 1.  ws >= ladder_kmeans_workspace_bytes(N, K, R), the SAME
+ *   buffer from seed / set_centres to the last update.
+ * Size queries return 0 for an unsupported shape.  LADDER_E_SHAPE (nothing launched) for R > 64, K > 64, K < 1, N < K, it < 1, max_iter < 1, a NULL array
+ * or a workspace shorter than the query's answer; LADDER_E_ALIGN for double arrays off 8 bytes. */
+size_t ladder_kmeans_state_doubles(int K, int R);
+size_t ladder_kmeans_draws_doubles(int K);
+size_t ladder_kmeans_workspace_bytes(int N, int K, int R);
+int ladder_kmeans_seed(const float* X, int N, int K, int R, const double* draws, double* state, void* ws, size_t ws_bytes, ladder_stream_t stream);
+int ladder_kmeans_set_centres(const float* X, int N, int K, int R, const double* centres, double* state, void* ws, size_t ws_bytes,
+                              ladder_stream_t stream);
+int ladder_kmeans_assign(const float* X, int N, int K, int R, int it, const double* state, int* labels, void* ws, size_t ws_bytes,
+                         ladder_stream_t stream);
+int ladder_kmeans_update(const float* X, int N, int K, int R, const int* labels, double* state, double tol, int max_iter, int it, void* ws,
+                         size_t ws_bytes, ladder_stream_t stream);
+
 /* ---------------------------------------------------------------- helpers */
 /* HOST function (no device work): CRC-32C (Castagnoli) of host memory, crc = 0 to start, chainable.  Used by the
  * tf.train.Saver checkpoint-v2 reader/writer (codes/base.py:37-85: saver_ae / saver_prior) for block and tensor checksums. */

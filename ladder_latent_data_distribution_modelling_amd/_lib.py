@@ -120,6 +120,13 @@ PROTOTYPES = {
     "ladder_emgmm_estep": (_i, [_p, _i, _i, _i, _p, _p, _p, _p, _p, _z, _p]),
     "ladder_emgmm_mstep": (_i, [_p, _p, _i, _i, _p, _d, _d, _i, _i, _p, _p, _p, _p]),
     "ladder_emgmm_prepare": (_i, [_p, _i, _i, _p]),
+    "ladder_kmeans_state_doubles": (_z, [_i, _i]),
+    "ladder_kmeans_draws_doubles": (_z, [_i]),
+    "ladder_kmeans_workspace_bytes": (_z, [_i, _i, _i]),
+    "ladder_kmeans_seed": (_i, [_p, _i, _i, _i, _p, _p, _p, _z, _p]),
+    "ladder_kmeans_set_centres": (_i, [_p, _i, _i, _i, _p, _p, _p, _z, _p]),
+    "ladder_kmeans_assign": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _z, _p]),
+    "ladder_kmeans_update": (_i, [_p, _i, _i, _i, _p, _p, _d, _i, _i, _p, _z, _p]),
     "ladder_axpy": (_i, [_p, _p, _z, _f, _i, _p]),
     "ladder_filter_pack_split_bytes": (_z, [_i, _i, _i, _i]),
     "ladder_filter_pack_split": (_i, [_p, _p, _i, _i, _i, _i, _i, _p]),

@@ -281,7 +281,8 @@ class BaseTrain:
             if self.config.get("gm_fit_backend", "hip") == "hip":
                 from .vbgmm import DeviceBayesianGaussianMixture
                 self.GM_prior_final = DeviceBayesianGaussianMixture(
-                    device=self.engine.ctx.device, label_broadcast=(lambda t: comm.broadcast_(t, 0)) if comm.on else None, **kw)
+                    device=self.engine.ctx.device, label_broadcast=(lambda t: comm.broadcast_(t, 0)) if comm.on else None,
+                    kmeans_backend=self.config.get("kmeans_backend", "sklearn"), **kw)
             else:
                 from sklearn.mixture import BayesianGaussianMixture
                 self.GM_prior_final = BayesianGaussianMixture(**kw)
@@ -322,7 +323,8 @@ class BaseTrain:
             gm = self.GM_prior_final = DeviceGaussianMixture(
                 n_components=int(self.config["n_mixtures"]), covariance_type="full", max_iter=2000, n_init=1, warm_start=False,
                 random_state=self.config.get("gm_random_state"), device=self.engine.ctx.device,
-                label_broadcast=(lambda t: comm.broadcast_(t, 0)) if comm.on else None)
+                label_broadcast=(lambda t: comm.broadcast_(t, 0)) if comm.on else None,
+                kmeans_backend=self.config.get("kmeans_backend", "sklearn"))
         else:
             from sklearn.mixture import GaussianMixture
             gm = self.GM_prior_final = GaussianMixture(n_components=int(self.config["n_mixtures"]), covariance_type="full",

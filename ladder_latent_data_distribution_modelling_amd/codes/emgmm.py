@@ -3,9 +3,10 @@
 `DeviceGaussianMixture` keeps sklearn.mixture.GaussianMixture's constructor arguments and fitted attributes (`weights_`, `means_`,
 `covariances_`, `precisions_cholesky_`, `n_iter_`, `lower_bound_`, `converged_`) for the options the reference uses
 (covariance_type='full', init_params='kmeans'; warm_start; n_init restarts), but runs the EM loop in float64 on samples that never
-leave the GPU (csrc/emgmm.hip: 1 <= R <= 64, 1 <= K <= 64), on one GPU or with the samples sharded over the data-parallel ranks.  Only the
-k-means initialisation of a cold fit runs on the host (codes/mixture_fit.py, shared with codes/vbgmm.py), so with the same `random_state` a fit
-reproduces sklearn's to float64 round-off (tests/test_gpu_emgmm.py).
+leave the GPU (csrc/emgmm.hip: 1 <= R <= 64, 1 <= K <= 64), on one GPU or with the samples sharded over the data-parallel ranks.  The k-means
+initialisation of a cold fit (codes/mixture_fit.py, shared with codes/vbgmm.py) is sklearn's on the host with kmeans_backend="sklearn" (the
+default) and the same algorithm on the device with kmeans_backend="hip" (codes/kmeans.py: the same labels, tests/test_gpu_kmeans.py); either way a
+fit with the same `random_state` reproduces sklearn's to float64 round-off (tests/test_gpu_emgmm.py).
 """
 import numpy as np
 import torch
@@ -17,7 +18,7 @@ from . import mixture_fit as MF
 class DeviceGaussianMixture:
     def __init__(self, n_components=1, covariance_type="full", tol=1e-3, reg_covar=1e-6, max_iter=100, n_init=1, init_params="kmeans",
                  weights_init=None, means_init=None, precisions_init=None, warm_start=False, random_state=None, device="cuda:0",
-                 label_broadcast=None):
+                 label_broadcast=None, kmeans_backend="sklearn"):
         if covariance_type != "full" or init_params != "kmeans":
             raise NotImplementedError("the HIP fit covers covariance_type='full', init_params='kmeans' (what the reference uses)")
         if weights_init is not None or means_init is not None or precisions_init is not None:
@@ -27,12 +28,18 @@ class DeviceGaussianMixture:
         self.warm_start, self.random_state = warm_start, random_state
         self.device = torch.device(device)
         self._label_broadcast = label_broadcast       # data-parallel hook: rank 0's k-means labels -> every rank
+        self.kmeans_backend = MF.check_kmeans_backend(kmeans_backend)
         self._state = None
 
     # -------------------------------------------------------------------------------------------------------------
     def fit(self, X, y=None):
         """X: [N,R] torch tensor on the device (preferred) or array-like."""
         return self.fit_sharded(X, MF.OneRank(), check_every=16)
+
+    def _initial_labels(self, Xd, comm, rs):
+        if self.kmeans_backend == "hip":
+            return MF.initial_labels(Xd, comm, self.n_components, rs, self._label_broadcast, labeller=MF.device_kmeans_labels, on_device=True)
+        return MF.initial_labels(Xd, comm, self.n_components, rs, self._label_broadcast)
 
     def fit_sharded(self, X_local, comm, check_every=8):
         """The fit with the samples SHARDED over the data-parallel ranks: `X_local` [N_local, R] are THIS rank's samples, `comm` the engine's
@@ -60,7 +67,7 @@ class DeviceGaussianMixture:
         def one_fit():
             state = f64(L.query("ladder_emgmm_state_doubles", K, R)) if do_init else self._state
             state[-2:] = 0.0                                                   # converged_, done
-            labels = MF.initial_labels(Xd, comm, K, rs, self._label_broadcast) if do_init else None
+            labels = self._initial_labels(Xd, comm, rs) if do_init else None
             w, m, c = (torch.empty(K, device=self.device), torch.empty(K, R, device=self.device), torch.empty(K, R, R, device=self.device))
             e_head = (Xd.data_ptr(), Nl, K, R)
             e_tail = (state.data_ptr(), mom.data_ptr(), stats.data_ptr(), ws.data_ptr(), ws.numel(), st)

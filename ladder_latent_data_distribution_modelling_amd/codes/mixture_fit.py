@@ -1,6 +1,6 @@
 """What the two device mixture fits share (codes/vbgmm.py: variational Bayes on t, codes/emgmm.py: EM on z): the single-process
-communicator, the k-means labels of a cold start (sklearn.cluster.KMeans on the gathered samples of rank 0, exactly the call
-BaseMixture._initialize_parameters makes), the loop that drives the E-step / all-reduce / M-step launches against the device-side
+communicator, the k-means labels of a cold start (on the gathered samples of rank 0: sklearn.cluster.KMeans on the host, exactly the call
+BaseMixture._initialize_parameters makes, or with kmeans_backend="hip" the same algorithm on the device, codes/kmeans.py), the loop that drives the E-step / all-reduce / M-step launches against the device-side
 `done` flag, the choice among `n_init` restarts and sklearn's messages.  Both state vectors end with the same four doubles:
 lower_bound_, n_iter_, converged_ (-1 = ill-defined covariance), done.
 """
@@ -45,6 +45,33 @@ def kmeans_labels(X_host, K, rs):
     return cluster.KMeans(n_clusters=K, n_init=1, random_state=rs).fit(X_host).labels_.astype(np.int32)
 
 
+def kmeans_draws(rs, N, K):
+    """The random numbers of ONE k-means++ seeding, taken from `rs` exactly as sklearn's _kmeans_plusplus takes them (tests/test_kmeans_cpu.py
+    compares the generator's state with the one a sklearn fit leaves behind): the index of the first centre from rs.choice with uniform weights,
+    then per further centre one rs.uniform(size=n_trials), n_trials = 2 + int(ln K).  -> (first index, uniforms [K-1, n_trials])."""
+    n_trials = 2 + int(np.log(K))
+    first = int(rs.choice(N, p=np.ones(N) / N))
+    u = np.empty((K - 1, n_trials))
+    for c in range(K - 1):
+        u[c] = rs.uniform(size=n_trials)
+    return first, u
+
+
+def device_kmeans_labels(X_dev, K, rs):
+    """kmeans_labels on the device: X_dev [N,R] stays where it is, -> int32 device tensor [N] (csrc/kmeans.hip)."""
+    from .kmeans import DeviceKMeans
+    return DeviceKMeans(n_clusters=K, n_init=1, random_state=rs, device=X_dev.device).fit(X_dev).labels_dev
+
+
+KMEANS_BACKENDS = ("sklearn", "hip")
+
+
+def check_kmeans_backend(backend):
+    if backend not in KMEANS_BACKENDS:
+        raise ValueError("kmeans_backend must be one of %r, got %r" % (KMEANS_BACKENDS, backend))
+    return backend
+
+
 def _gather_ragged(parts, x, comm):
     for r, p_ in enumerate(parts):                                               # ranks with different sample counts: one broadcast each
         if r == comm.rank:
@@ -66,12 +93,15 @@ def gather_samples(Xd, comm):
     return torch.cat(parts, 0), sum(cl[:comm.rank])
 
 
-def initial_labels(Xd, comm, K, rs, label_broadcast=None, labeller=kmeans_labels):
+def initial_labels(Xd, comm, K, rs, label_broadcast=None, labeller=kmeans_labels, on_device=False):
     """The hard labels of THIS rank's samples for a cold start: k-means needs every sample -- gathered once (rank order), labelled on
-    rank 0, this rank keeps its slice.  `label_broadcast`: the hook of replicated fits inside a data-parallel job (rank 0's labels)."""
+    rank 0, this rank keeps its slice.  `label_broadcast`: the hook of replicated fits inside a data-parallel job (rank 0's labels).
+    `on_device`: the labeller takes the gathered DEVICE tensor and returns a device tensor (device_kmeans_labels): no copy to the host."""
     allx, off = gather_samples(Xd, comm)
     lab = torch.empty(allx.shape[0], dtype=torch.int32, device=Xd.device)
-    if comm.rank == 0:
+    if comm.rank == 0 and on_device:
+        lab.copy_(labeller(allx, K, rs))
+    elif comm.rank == 0:
         lab.copy_(torch.as_tensor(labeller(allx.cpu().numpy().astype(np.float64), K, rs)))
     comm.broadcast_(lab, 0)
     if label_broadcast is not None and not comm.on:

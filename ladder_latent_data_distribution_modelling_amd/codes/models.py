@@ -37,7 +37,8 @@ class BaseModel:
 
     # codes/base.py:88-106 -- the producer of (prior_weight, prior_mean, prior_cov).  config["gm_fit_backend"]: "hip" (default)
     # runs the variational fit on the device (codes/vbgmm.py -> csrc/vbgmm.hip, sklearn-parity tested); "sklearn" keeps the
-    # reference's host object.
+    # reference's host object.  config["kmeans_backend"]: "sklearn" (default) labels a cold device fit with sklearn's k-means on the host, "hip" with
+    # the same algorithm on the device (codes/kmeans.py); it has no effect on the host objects.
     def define_GM_prior(self):
         self.GM_prior_training = None
         if self.config["prior"] == "ours":
@@ -49,7 +50,8 @@ class BaseModel:
                 from .vbgmm import DeviceBayesianGaussianMixture
                 comm = self.engine.ctx.comm
                 self.GM_prior_training = DeviceBayesianGaussianMixture(
-                    device=self.engine.ctx.device, label_broadcast=(lambda t: comm.broadcast_(t, 0)) if comm.on else None, **kw)
+                    device=self.engine.ctx.device, label_broadcast=(lambda t: comm.broadcast_(t, 0)) if comm.on else None,
+                    kmeans_backend=self.config.get("kmeans_backend", "sklearn"), **kw)
             else:
                 from sklearn.mixture import BayesianGaussianMixture
                 self.GM_prior_training = BayesianGaussianMixture(**kw)
@@ -62,7 +64,7 @@ class BaseModel:
                 comm = self.engine.ctx.comm
                 self.GM_prior_training = DeviceGaussianMixture(
                     device=self.engine.ctx.device, label_broadcast=(lambda t: comm.broadcast_(t, 0)) if comm.on else None,
-                    random_state=self.config.get("gm_random_state"), **kw)
+                    random_state=self.config.get("gm_random_state"), kmeans_backend=self.config.get("kmeans_backend", "sklearn"), **kw)
             else:
                 from sklearn.mixture import GaussianMixture
                 self.GM_prior_training = GaussianMixture(**kw)

@@ -4,9 +4,10 @@
 attributes (`weights_`, `means_`, `covariances_`, `n_iter_`, `lower_bound_`, `converged_`) for the options the reference
 uses (covariance_type='full'; dirichlet_distribution for the per-epoch "fast" fit, dirichlet_process for the final
 "accurate" fit; warm_start; n_init restarts), but runs the variational loop as one persistent-workgroup HIP launch
-(`ladder_vbgmm_fit`, csrc/vbgmm.hip) on samples that never leave the GPU.  Only the k-means initialisation of a cold fit runs on
-the host (sklearn.cluster.KMeans, exactly the call BaseMixture._initialize_parameters makes), so with the same `random_state`
-a fit reproduces sklearn's to float64 round-off (tests/test_gpu_vbgmm.py).
+(`ladder_vbgmm_fit`, csrc/vbgmm.hip) on samples that never leave the GPU.  The k-means initialisation of a cold fit is
+sklearn.cluster.KMeans on the host (exactly the call BaseMixture._initialize_parameters makes) with kmeans_backend="sklearn", the
+default, and the same algorithm on the device with kmeans_backend="hip" (codes/kmeans.py: the same labels); either way a fit with the
+same `random_state` reproduces sklearn's to float64 round-off (tests/test_gpu_vbgmm.py, tests/test_gpu_kmeans.py).
 """
 import numpy as np
 import torch
@@ -24,7 +25,8 @@ SLICED_FIT_MIN_SAMPLES = 1024
 class DeviceBayesianGaussianMixture:
     def __init__(self, n_components=1, covariance_type="full", tol=1e-3, reg_covar=1e-6, max_iter=100, n_init=1,
                  init_params="kmeans", weight_concentration_prior_type="dirichlet_process", weight_concentration_prior=None,
-                 mean_precision_prior=None, warm_start=False, random_state=None, device="cuda:0", label_broadcast=None):
+                 mean_precision_prior=None, warm_start=False, random_state=None, device="cuda:0", label_broadcast=None,
+                 kmeans_backend="sklearn"):
         if covariance_type != "full" or init_params != "kmeans":
             raise NotImplementedError("the HIP fit covers covariance_type='full', init_params='kmeans' (what the reference uses)")
         if weight_concentration_prior_type not in ("dirichlet_distribution", "dirichlet_process"):
@@ -36,6 +38,7 @@ class DeviceBayesianGaussianMixture:
         self.warm_start, self.random_state = warm_start, random_state
         self.device = torch.device(device)
         self._label_broadcast = label_broadcast       # data-parallel hook: rank 0's k-means labels -> every rank
+        self.kmeans_backend = MF.check_kmeans_backend(kmeans_backend)
         self._state = None
 
     # -------------------------------------------------------------------------------------------------------------
@@ -72,6 +75,8 @@ class DeviceBayesianGaussianMixture:
         return self._keep(MF.best_of_restarts(self.n_init if do_init else 1, one_fit))
 
     def _initial_labels(self, Xd, comm, rs):
+        if self.kmeans_backend == "hip":
+            return MF.initial_labels(Xd, comm, self.n_components, rs, self._label_broadcast, labeller=MF.device_kmeans_labels, on_device=True)
         return MF.initial_labels(Xd, comm, self.n_components, rs, self._label_broadcast, labeller=lambda Xh, K, r: self._kmeans_labels(Xh, r))
 
     def _keep(self, best):
