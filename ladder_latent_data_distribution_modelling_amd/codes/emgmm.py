@@ -37,9 +37,7 @@ class DeviceGaussianMixture:
         return self.fit_sharded(X, MF.OneRank(), check_every=16)
 
     def _initial_labels(self, Xd, comm, rs):
-        if self.kmeans_backend == "hip":
-            return MF.initial_labels(Xd, comm, self.n_components, rs, self._label_broadcast, labeller=MF.device_kmeans_labels, on_device=True)
-        return MF.initial_labels(Xd, comm, self.n_components, rs, self._label_broadcast)
+        return MF.initial_labels_for(self.kmeans_backend, Xd, comm, self.n_components, rs, self._label_broadcast)
 
     def fit_sharded(self, X_local, comm, check_every=8):
         """The fit with the samples SHARDED over the data-parallel ranks: `X_local` [N_local, R] are THIS rank's samples, `comm` the engine's
@@ -47,7 +45,6 @@ class DeviceGaussianMixture:
         travels with the moments: the lower bound is a global mean), M-step + convergence test, identical on every rank.  The `done` flag
         lives in device memory and is read every `check_every` iterations; iterations enqueued past the end are no-ops, so the result does
         not depend on `check_every`.  A cold start takes its k-means labels from rank 0, once; warm starts exchange statistics only."""
-        from sklearn.utils import check_random_state
         K = self.n_components
         Xd = MF.device_samples(X_local, self.device)
         Nl, R = Xd.shape
@@ -59,30 +56,27 @@ class DeviceGaussianMixture:
         MF.check_sample_count(int(mom[-1].item()), K)                          # sklearn's check, on the GLOBAL sample count
         stats = f64(L.query("ladder_emgmm_stats_doubles", K, R))
         ws = torch.empty(L.query("ladder_emgmm_workspace_bytes", Nl, K, R), dtype=torch.uint8, device=self.device)
-        do_init = not (self.warm_start and self._state is not None and hasattr(self, "converged_"))
-        rs = check_random_state(self.random_state)
+        do_init, rs, n_fits = MF.fit_plan(self)
         lib = L.load()
         estep_fn, mstep_fn = lib.ladder_emgmm_estep, lib.ladder_emgmm_mstep
 
         def one_fit():
             state = f64(L.query("ladder_emgmm_state_doubles", K, R)) if do_init else self._state
-            state[-2:] = 0.0                                                   # converged_, done
+            state[MF.FIT_CONVERGED:] = 0.0
             labels = self._initial_labels(Xd, comm, rs) if do_init else None
-            w, m, c = (torch.empty(K, device=self.device), torch.empty(K, R, device=self.device), torch.empty(K, R, R, device=self.device))
+            w, m, c = MF.feed_tensors(K, R, self.device)
             e_head = (Xd.data_ptr(), Nl, K, R)
             e_tail = (state.data_ptr(), mom.data_ptr(), stats.data_ptr(), ws.data_ptr(), ws.numel(), st)
             m_head = (stats.data_ptr(), mom.data_ptr(), K, R, state.data_ptr(), float(self.reg_covar), float(self.tol), self.max_iter)
             m_tail = (w.data_ptr(), m.data_ptr(), c.data_ptr(), st)
             MF.iterate_until_done(lambda it: estep_fn(*e_head, labels.data_ptr() if (labels is not None and it == 0) else None, *e_tail),
-                                  lambda it: mstep_fn(*m_head, it, *m_tail), comm.allreduce_ if comm.on else None, stats, state[-1:],
+                                  lambda it: mstep_fn(*m_head, it, *m_tail), comm.allreduce_ if comm.on else None, stats, state[MF.FIT_DONE:],
                                   0 if do_init else 1, self.max_iter, check_every, "EM mixture fit")
             return state, w, m, c
 
         self.converged_ = False                                                # (sklearn sets it before the first restart: a failed fit leaves it)
-        best = MF.best_of_restarts(self.n_init if do_init else 1, one_fit)
-        self.lower_bound_, self.n_iter_, self.converged_, self._state, self.weights_dev, self.means_dev, self.covariances_dev = best
+        MF.keep_best(self, MF.best_of_restarts(n_fits, one_fit))
         self._R = R
-        MF.warn_if_not_converged(self.converged_, self.max_iter)
         return self
 
     def _prepare_state(self, state, R):

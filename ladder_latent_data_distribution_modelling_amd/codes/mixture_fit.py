@@ -1,8 +1,7 @@
 """What the two device mixture fits share (codes/vbgmm.py: variational Bayes on t, codes/emgmm.py: EM on z): the single-process
 communicator, the k-means labels of a cold start (on the gathered samples of rank 0: sklearn.cluster.KMeans on the host, exactly the call
 BaseMixture._initialize_parameters makes, or with kmeans_backend="hip" the same algorithm on the device, codes/kmeans.py), the loop that drives the E-step / all-reduce / M-step launches against the device-side
-`done` flag, the choice among `n_init` restarts and sklearn's messages.  Both state vectors end with the same four doubles:
-lower_bound_, n_iter_, converged_ (-1 = ill-defined covariance), done.
+`done` flag, the choice among `n_init` restarts and sklearn's messages.
 """
 import warnings
 
@@ -14,6 +13,11 @@ ILL_DEFINED = ("Fitting the mixture model failed because some components have il
                "components, increase reg_covar, or scale the input data.")
 NOT_CONVERGED = ("Best performing initialization did not converge. Try different init parameters, or increase max_iter, "
                  "tol, or check for degenerate data.")
+
+
+# Both state vectors end with the same four doubles (csrc/fit_util.h): lower_bound_, n_iter_, converged_ (-1 = ill-defined covariance), done;
+# as indices from the end, so that state[FIT_CONVERGED:] = converged_ and done, state[FIT_DONE:] = the one-element view of the flag
+FIT_LB, FIT_NITER, FIT_CONVERGED, FIT_DONE = -4, -3, -2, -1
 
 
 class OneRank:
@@ -93,20 +97,33 @@ def gather_samples(Xd, comm):
     return torch.cat(parts, 0), sum(cl[:comm.rank])
 
 
-def initial_labels(Xd, comm, K, rs, label_broadcast=None, labeller=kmeans_labels, on_device=False):
+def initial_labels_for(backend, Xd, comm, K, rs, label_broadcast=None):
     """The hard labels of THIS rank's samples for a cold start: k-means needs every sample -- gathered once (rank order), labelled on
     rank 0, this rank keeps its slice.  `label_broadcast`: the hook of replicated fits inside a data-parallel job (rank 0's labels).
-    `on_device`: the labeller takes the gathered DEVICE tensor and returns a device tensor (device_kmeans_labels): no copy to the host."""
+    `backend` = kmeans_backend: "hip" labels the gathered DEVICE tensor (device_kmeans_labels, no copy to the host), "sklearn" a host copy."""
     allx, off = gather_samples(Xd, comm)
     lab = torch.empty(allx.shape[0], dtype=torch.int32, device=Xd.device)
-    if comm.rank == 0 and on_device:
-        lab.copy_(labeller(allx, K, rs))
+    if comm.rank == 0 and backend == "hip":
+        lab.copy_(device_kmeans_labels(allx, K, rs))
     elif comm.rank == 0:
-        lab.copy_(torch.as_tensor(labeller(allx.cpu().numpy().astype(np.float64), K, rs)))
+        lab.copy_(torch.as_tensor(kmeans_labels(allx.cpu().numpy().astype(np.float64), K, rs)))
     comm.broadcast_(lab, 0)
     if label_broadcast is not None and not comm.on:
         label_broadcast(lab)
     return lab[off:off + Xd.shape[0]].contiguous()
+
+
+def fit_plan(gm):
+    """-> (cold start?, the random state of its k-means, fits to run): a fit starts from k-means labels, `n_init` times over, unless
+    `warm_start` is set and an earlier fit left its state behind."""
+    from sklearn.utils import check_random_state
+    cold = not (gm.warm_start and gm._state is not None and hasattr(gm, "converged_"))
+    return cold, check_random_state(gm.random_state), gm.n_init if cold else 1
+
+
+def feed_tensors(K, R, device):
+    """The fp32 copies (weights [K], means [K,R], covariances [K,R,R]) that a fit writes for the engine's mixture feed."""
+    return torch.empty(K, device=device), torch.empty(K, R, device=device), torch.empty(K, R, R, device=device)
 
 
 def iterate_until_done(estep, mstep, exchange, stats, flag, first_it, max_iter, check_every, what):
@@ -130,10 +147,10 @@ def iterate_until_done(estep, mstep, exchange, stats, flag, first_it, max_iter, 
 
 def read_tail(state):
     """(lower_bound_, n_iter_, converged_) of a finished fit -- one host synchronisation; raises sklearn's error on status -1."""
-    tail = state[-4:-1].cpu().numpy()
-    if tail[2] < 0:
+    tail = state[FIT_LB:].cpu().numpy()
+    if tail[FIT_CONVERGED] < 0:
         raise ValueError(ILL_DEFINED)
-    return float(tail[0]), int(tail[1]), bool(tail[2] > 0)
+    return float(tail[FIT_LB]), int(tail[FIT_NITER]), bool(tail[FIT_CONVERGED] > 0)
 
 
 def best_of_restarts(n_restarts, run_one):
@@ -148,7 +165,10 @@ def best_of_restarts(n_restarts, run_one):
     return best
 
 
-def warn_if_not_converged(converged, max_iter):
-    if not converged and max_iter > 0:
+def keep_best(gm, best):
+    """Stores what best_of_restarts returns on the mixture object `gm`, with sklearn's warning if that fit did not converge; -> gm."""
+    gm.lower_bound_, gm.n_iter_, gm.converged_, gm._state, gm.weights_dev, gm.means_dev, gm.covariances_dev = best
+    if not gm.converged_ and gm.max_iter > 0:
         from sklearn.exceptions import ConvergenceWarning
         warnings.warn(NOT_CONVERGED, ConvergenceWarning)
+    return gm

@@ -14,7 +14,6 @@ import torch
 
 from .. import _lib as L
 from . import mixture_fit as MF
-from .mixture_fit import OneRank as _OneRank
 
 
 # from this many samples on, fit() runs one E-step launch over 256-sample slices (one workgroup each) + one M-step launch per variational
@@ -42,47 +41,38 @@ class DeviceBayesianGaussianMixture:
         self._state = None
 
     # -------------------------------------------------------------------------------------------------------------
-    def _kmeans_labels(self, X_host, rs):
-        return MF.kmeans_labels(X_host, self.n_components, rs)
+    def _prior_args(self):
+        """(prior type, weight concentration prior, mean precision prior) as the kernels take them, with sklearn's defaults 1 / K and 1."""
+        return (0 if self.weight_concentration_prior_type == "dirichlet_distribution" else 1,
+                1.0 / self.n_components if self.weight_concentration_prior is None else float(self.weight_concentration_prior),
+                1.0 if self.mean_precision_prior is None else float(self.mean_precision_prior))
 
     def fit(self, X, y=None):
         """X: [N,R] torch tensor on the device (preferred) or array-like."""
-        from sklearn.utils import check_random_state
         K = self.n_components
         Xd = MF.device_samples(X, self.device)
         N, R = Xd.shape
         MF.check_sample_count(N, K)
         if N >= SLICED_FIT_MIN_SAMPLES:
-            return self.fit_sharded(Xd, _OneRank(), check_every=16)
-        wc = 1.0 / K if self.weight_concentration_prior is None else float(self.weight_concentration_prior)
-        mp = 1.0 if self.mean_precision_prior is None else float(self.mean_precision_prior)
-        ptype = 0 if self.weight_concentration_prior_type == "dirichlet_distribution" else 1
-        nstate = L.query("ladder_vbgmm_state_doubles", K, R)
+            return self.fit_sharded(Xd, MF.OneRank(), check_every=16)
+        ptype, wc, mp = self._prior_args()
         ws = torch.empty(L.query("ladder_vbgmm_workspace_bytes", N, K), dtype=torch.uint8, device=self.device)
         st = torch.cuda.current_stream(self.device).cuda_stream
-        do_init = not (self.warm_start and self._state is not None and hasattr(self, "converged_"))
-        rs = check_random_state(self.random_state)
+        do_init, rs, n_fits = MF.fit_plan(self)
 
         def one_fit():
-            state = torch.zeros(nstate, dtype=torch.float64, device=self.device) if do_init else self._state
-            labels = self._initial_labels(Xd, _OneRank(), rs) if do_init else None
-            w, m, c = (torch.empty(K, device=self.device), torch.empty(K, R, device=self.device), torch.empty(K, R, R, device=self.device))
+            state = torch.zeros(L.query("ladder_vbgmm_state_doubles", K, R), dtype=torch.float64, device=self.device) if do_init else self._state
+            labels = self._initial_labels(Xd, MF.OneRank(), rs) if do_init else None
+            w, m, c = MF.feed_tensors(K, R, self.device)
             L.call("ladder_vbgmm_fit", Xd.data_ptr(), N, K, R, labels.data_ptr() if labels is not None else None, state.data_ptr(),
                    ptype, wc, mp, float(self.reg_covar), float(self.tol), self.max_iter, w.data_ptr(), m.data_ptr(), c.data_ptr(),
                    ws.data_ptr(), ws.numel(), st)
             return state, w, m, c                          # (the one host sync of the fit: the tail read of best_of_restarts)
 
-        return self._keep(MF.best_of_restarts(self.n_init if do_init else 1, one_fit))
+        return MF.keep_best(self, MF.best_of_restarts(n_fits, one_fit))
 
     def _initial_labels(self, Xd, comm, rs):
-        if self.kmeans_backend == "hip":
-            return MF.initial_labels(Xd, comm, self.n_components, rs, self._label_broadcast, labeller=MF.device_kmeans_labels, on_device=True)
-        return MF.initial_labels(Xd, comm, self.n_components, rs, self._label_broadcast, labeller=lambda Xh, K, r: self._kmeans_labels(Xh, r))
-
-    def _keep(self, best):
-        self.lower_bound_, self.n_iter_, self.converged_, self._state, self.weights_dev, self.means_dev, self.covariances_dev = best
-        MF.warn_if_not_converged(self.converged_, self.max_iter)
-        return self
+        return MF.initial_labels_for(self.kmeans_backend, Xd, comm, self.n_components, rs, self._label_broadcast)
 
     # -------------------------------------------------------------------------------------------------------------
     def fit_sharded(self, X_local, comm, check_every=8):
@@ -93,13 +83,10 @@ class DeviceBayesianGaussianMixture:
         lives in device memory and is read every `check_every` iterations; iterations enqueued past the end are no-ops, so the result
         does not depend on `check_every`.  A cold start takes its k-means labels from rank 0 (sklearn.cluster.KMeans on the gathered
         samples, as BaseMixture._initialize_parameters does) -- once; warm starts exchange statistics only."""
-        from sklearn.utils import check_random_state
         K = self.n_components
         Xd = MF.device_samples(X_local, self.device)
         Nl, R = Xd.shape
-        wc = 1.0 / K if self.weight_concentration_prior is None else float(self.weight_concentration_prior)
-        mp = 1.0 if self.mean_precision_prior is None else float(self.mean_precision_prior)
-        ptype = 0 if self.weight_concentration_prior_type == "dirichlet_distribution" else 1
+        ptype, wc, mp = self._prior_args()
         st = torch.cuda.current_stream(self.device).cuda_stream
         f64 = lambda n: torch.zeros(n, dtype=torch.float64, device=self.device)
         mom = f64(L.query("ladder_vbgmm_shard_moments_doubles", R))
@@ -110,27 +97,26 @@ class DeviceBayesianGaussianMixture:
         MF.check_sample_count(int(n_glob.item()), K)                           # sklearn's check, on the GLOBAL sample count
         stats = f64(L.query("ladder_vbgmm_shard_stats_doubles", K, R))
         ws = torch.empty(L.query("ladder_vbgmm_shard_workspace_bytes", Nl, K, R), dtype=torch.uint8, device=self.device)
-        do_init = not (self.warm_start and self._state is not None and hasattr(self, "converged_"))
-        rs = check_random_state(self.random_state)
+        do_init, rs, n_fits = MF.fit_plan(self)
         lib = L.load()
         estep_fn, mstep_fn = lib.ladder_vbgmm_shard_estep, lib.ladder_vbgmm_shard_mstep
 
         def one_fit():
             state = f64(L.query("ladder_vbgmm_state_doubles", K, R)) if do_init else self._state
-            state[-2:] = 0.0                                                   # converged_, done
+            state[MF.FIT_CONVERGED:] = 0.0
             labels = self._initial_labels(Xd, comm, rs) if do_init else None   # rank 0's k-means, once; warm starts exchange statistics only
-            w, m, c = (torch.empty(K, device=self.device), torch.empty(K, R, device=self.device), torch.empty(K, R, R, device=self.device))
+            w, m, c = MF.feed_tensors(K, R, self.device)
             # (the argument lists are constant over the iterations but for `labels` / `it`: bound once, the loop is two foreign calls)
             e_tail = (state.data_ptr(), ptype, stats.data_ptr(), ws.data_ptr(), ws.numel(), st)
             m_head = (stats.data_ptr(), mom.data_ptr(), K, R, state.data_ptr(), ptype, wc, mp, float(self.reg_covar), float(self.tol), self.max_iter)
             m_tail = (w.data_ptr(), m.data_ptr(), c.data_ptr(), st)
             xp = Xd.data_ptr()
             MF.iterate_until_done(lambda it: estep_fn(xp, Nl, K, R, labels.data_ptr() if (labels is not None and it == 0) else None, *e_tail),
-                                  lambda it: mstep_fn(*m_head, it, *m_tail), comm.allreduce_ if comm.on else None, stats, state[-1:],
+                                  lambda it: mstep_fn(*m_head, it, *m_tail), comm.allreduce_ if comm.on else None, stats, state[MF.FIT_DONE:],
                                   0 if do_init else 1, self.max_iter, check_every, "sharded mixture fit")
             return state, w, m, c
 
-        return self._keep(MF.best_of_restarts(self.n_init if do_init else 1, one_fit))
+        return MF.keep_best(self, MF.best_of_restarts(n_fits, one_fit))
 
     # float64 views of the fitted parameters, as sklearn exposes them
     def _unpack(self):

@@ -20,11 +20,11 @@
 // ladder_vbgmm_shard_*).  No atomics: every sum has one fixed order, so a fit gives the same bits on every run and for every `check_every`.
 //
 // state (doubles): weights [K] | means [K,R] | covariances [K,R,R] | precisions_cholesky [K,R,R] | log_det [K] | component status [K] |
-//                  lower_bound_, n_iter_, converged_ (-1: a non-positive Cholesky pivot, sklearn raises ValueError there), done
+//                  the tail of csrc/fit_util.h: lower_bound_, n_iter_, converged_, done
 //
 // Operand lane maps of v_mfma_f64_16x16x4_f64: head of csrc/fid.hip (A [m = lane & 15][k = lane >> 4], B [k][n = lane & 15],
 // C/D reg r: row (lane >> 4) + 4 r, col lane & 15).
-#include "common.h"
+#include "fit_util.h"
 
 namespace {
 
@@ -34,9 +34,6 @@ constexpr int EM_MAXR = 64, EM_MAXK = 64;
 constexpr int EM_SLICE = 64;            // samples per E-step workgroup: 4 wavefronts x 16 MFMA rows
 constexpr int EM_LDP = 80;              // LDS row pitch of the staged P_k in doubles: the four k-rows of one B operand fall into different bank halves
 constexpr int EM_LDC = 65;              // LDS row pitch of the M-step's factorisation (odd: a thread per row or per column walks distinct banks)
-constexpr int EM_MAX_SPLITS = 32, EM_MIN_SPLIT_ROWS = 128;
-constexpr double EM_EPS10 = 10.0 * 2.220446049250313e-16;        // 10 * np.finfo(float64).eps
-constexpr double EM_LOG_2PI = 1.8378770664093453;
 
 struct EmState {
   double *w, *means, *cov, *pchol, *logdet, *cstat, *tail;
@@ -55,33 +52,17 @@ __host__ __device__ inline size_t em_state_doubles(int K, int R) { return (size_
 __host__ __device__ inline size_t em_stats_doubles(int K, int R) { return 1 + (size_t)K * (1 + R + (size_t)R * R); }
 inline int em_slices(int N) { return (N + EM_SLICE - 1) / EM_SLICE; }
 
-struct EmSplit {
-  int rows, nsplit;                    // rows per split (a multiple of 4), row splits
-};
-inline EmSplit em_split(int N) {
-  EmSplit p;
-  int rows = (N + EM_MAX_SPLITS - 1) / EM_MAX_SPLITS;
-  rows = rows < EM_MIN_SPLIT_ROWS ? EM_MIN_SPLIT_ROWS : rows;
-  p.rows = (rows + 3) / 4 * 4;
-  p.nsplit = (N + p.rows - 1) / p.rows;
-  return p;
-}
-
 // moments = [ sum_n x_n [R] | N ], all-reduced by the caller: the shift is the GLOBAL mean rounded to fp32, the same on every rank
 __device__ __forceinline__ double em_shift(const double* mom, int R, int j) { return (double)(float)(mom[j] / mom[R]); }
 
 // ------------------------------------------------------------------------------------------------ column sums for the shift
-// One workgroup per column: thread-strided partial sums, the shuffle tree, then the four wavefronts in order.
+// One workgroup per column (column_sum_256: thread-strided partial sums, the shuffle tree, then the four wavefronts in order).
 __global__ __launch_bounds__(256) void emgmm_shift_kernel(const float* __restrict__ X, int N, int R, double* __restrict__ mom) {
   const int j = blockIdx.x, tid = threadIdx.x;
   __shared__ double s_red[4];
-  double a = 0.0;
-  for (int n = tid; n < N; n += 256) a += (double)X[(size_t)n * R + j];
-  a = wave_sum_d(a);
-  if ((tid & 63) == 0) s_red[tid >> 6] = a;
-  __syncthreads();
+  const double a = column_sum_256(X, N, R, j, s_red, tid);
   if (tid == 0) {
-    mom[j] = ((s_red[0] + s_red[1]) + s_red[2]) + s_red[3];
+    mom[j] = a;
     if (j == 0) mom[R] = (double)N;
   }
 }
@@ -90,7 +71,7 @@ __global__ __launch_bounds__(256) void emgmm_shift_kernel(const float* __restric
 __global__ __launch_bounds__(256) void emgmm_estep_kernel(const float* __restrict__ X, const int* __restrict__ labels, const double* state, int N, int K,
                                                           int R, double* resp, double* __restrict__ lpn_part) {
   EmState S(const_cast<double*>(state), K, R);
-  if (S.tail[3] != 0.0) return;                                    // the fit is over: iterations enqueued past the end are no-ops
+  if (S.tail[FIT_DONE] != 0.0) return;                             // the fit is over: iterations enqueued past the end are no-ops
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, m = lane & 15, kq = lane >> 4;
   const int n0 = blockIdx.x * EM_SLICE, rows = min(EM_SLICE, N - n0);
   if (labels != nullptr) {                                         // iteration 0: hard labels, through the same statistics kernels
@@ -149,7 +130,7 @@ __global__ __launch_bounds__(256) void emgmm_estep_kernel(const float* __restric
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int rr = wave * 16 + kq + 4 * r;
-        if (rr < rows) resp[(size_t)(n0 + rr) * K + k] = (-0.5 * (R * EM_LOG_2PI + q4[r]) + s_ld[k]) + s_lw[k];
+        if (rr < rows) resp[(size_t)(n0 + rr) * K + k] = (-0.5 * (R * kLog2Pi + q4[r]) + s_ld[k]) + s_lw[k];
       }
     }
   }
@@ -176,7 +157,7 @@ __global__ __launch_bounds__(256) void emgmm_estep_kernel(const float* __restric
 __global__ __launch_bounds__(256) void emgmm_stats_kernel(const float* __restrict__ X, const double* __restrict__ resp, const double* __restrict__ state,
                                                           const double* __restrict__ mom, int N, int K, int R, int rows, double* __restrict__ part) {
   EmState S(const_cast<double*>(state), K, R);
-  if (S.tail[3] != 0.0) return;
+  if (S.tail[FIT_DONE] != 0.0) return;
   const int k = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, m = lane & 15, kq = lane >> 4;
   const int nb = (R + 15) / 16;
   if (wave >= nb) return;                                          // (whole wavefronts; no barrier in this kernel)
@@ -238,7 +219,7 @@ __global__ __launch_bounds__(256) void emgmm_stats_kernel(const float* __restric
 __global__ __launch_bounds__(256) void emgmm_reduce_kernel(const double* __restrict__ part, const double* __restrict__ lpn_part, const double* __restrict__ state,
                                                            int K, int R, int nsplit, int nslices, double* __restrict__ stats) {
   EmState S(const_cast<double*>(state), K, R);
-  if (S.tail[3] != 0.0) return;
+  if (S.tail[FIT_DONE] != 0.0) return;
   const size_t n = em_stats_doubles(K, R), e = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (e >= n) return;
   double a = 0.0;
@@ -306,20 +287,20 @@ __global__ __launch_bounds__(64) void emgmm_mstep_kernel(const double* __restric
                                                          double reg_covar, int it, float* __restrict__ w_out, float* __restrict__ m_out,
                                                          float* __restrict__ c_out) {
   EmState S(state, K, R);
-  if (S.tail[3] != 0.0) return;
+  if (S.tail[FIT_DONE] != 0.0) return;
   const int k = blockIdx.x, tid = threadIdx.x;
   __shared__ double s_A[EM_MAXR * EM_LDC], s_s1[EM_MAXR], s_dm[EM_MAXR];
   const double* st_nk = stats + 1;
   const double* st_x = st_nk + K + (size_t)k * R;
   const double* st_xx = stats + 1 + K + (size_t)K * R + (size_t)k * R * R;
-  const double nk_raw = st_nk[k], nk = nk_raw + EM_EPS10;          // nk = resp.sum(axis=0) + 10 * eps
+  const double nk_raw = st_nk[k], nk = nk_raw + kEps10;            // nk = resp.sum(axis=0) + 10 * eps
   if (tid == 0) {
     double w;
     if (it == 0) {
       w = nk / mom[R];                                             // _initialize: weights = nk / n_samples
     } else {
       double tot = 0.0;                                            // _m_step: weights_ = nk; weights_ /= weights_.sum()
-      for (int j = 0; j < K; ++j) tot += st_nk[j] + EM_EPS10;
+      for (int j = 0; j < K; ++j) tot += st_nk[j] + kEps10;
       w = nk / tot;
     }
     S.w[k] = w;
@@ -370,34 +351,32 @@ __global__ void emgmm_finish_kernel(const double* __restrict__ stats, const doub
                                     int it) {
   EmState S(state, K, R);
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  if (it >= 0 && S.tail[3] != 0.0) return;
+  if (it >= 0 && S.tail[FIT_DONE] != 0.0) return;
   bool bad = false;
   for (int k = 0; k < K; ++k) bad = bad || (S.cstat[k] < 0.0);
   if (bad) {
-    S.tail[2] = -1.0;
-    S.tail[3] = 1.0;
+    S.tail[FIT_CONVERGED] = -1.0;
+    S.tail[FIT_DONE] = 1.0;
     return;
   }
   if (it < 0) return;
   if (it == 0) {
-    S.tail[0] = -INFINITY;                                         // a cold start has no lower bound yet
-    S.tail[1] = 0.0;
-    if (max_iter == 0) S.tail[3] = 1.0;
+    S.tail[FIT_LB] = -INFINITY;                                    // a cold start has no lower bound yet
+    S.tail[FIT_NITER] = 0.0;
+    if (max_iter == 0) S.tail[FIT_DONE] = 1.0;
     return;
   }
   const double lb = stats[0] / mom[R];                             // np.mean(log_prob_norm) over ALL samples
-  const bool conv = fabs(lb - S.tail[0]) < tol;
-  S.tail[0] = lb;
-  S.tail[1] = (double)it;
+  const bool conv = fabs(lb - S.tail[FIT_LB]) < tol;
+  S.tail[FIT_LB] = lb;
+  S.tail[FIT_NITER] = (double)it;
   if (conv) {
-    S.tail[2] = 1.0;
-    S.tail[3] = 1.0;
+    S.tail[FIT_CONVERGED] = 1.0;
+    S.tail[FIT_DONE] = 1.0;
   } else if (it >= max_iter) {
-    S.tail[3] = 1.0;
+    S.tail[FIT_DONE] = 1.0;
   }
 }
-
-inline bool em_misaligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7u) != 0; }
 
 }  // namespace
 
@@ -410,12 +389,12 @@ size_t ladder_emgmm_shift_doubles(int R) { return R < 1 ? 0 : (size_t)R + 1; }
 size_t ladder_emgmm_workspace_bytes(int N, int K, int R) {
   if (N < 1 || K < 1 || R < 1) return 0;
   // responsibilities [N, K] | per-slice log_prob_norm sums | per-split partial statistics
-  return ((size_t)N * K + (size_t)em_slices(N) + (size_t)em_split(N).nsplit * em_stats_doubles(K, R)) * sizeof(double);
+  return ((size_t)N * K + (size_t)em_slices(N) + (size_t)fit_split(N).nsplit * em_stats_doubles(K, R)) * sizeof(double);
 }
 
 int ladder_emgmm_shift(const float* X, int N, int R, double* moments, ladder_stream_t stream) {
   if (X == nullptr || moments == nullptr || N < 1 || R < 1 || R > EM_MAXR) return LADDER_E_SHAPE;
-  if (em_misaligned(moments)) return LADDER_E_ALIGN;
+  if (fit_misaligned(moments)) return LADDER_E_ALIGN;
   hipLaunchKernelGGL(emgmm_shift_kernel, dim3(R), dim3(256), 0, stream, X, N, R, moments);
   LADDER_CHECK_LAUNCH();
   return LADDER_OK;
@@ -425,9 +404,9 @@ int ladder_emgmm_estep(const float* X, int N, int K, int R, const int* labels, c
                        size_t ws_bytes, ladder_stream_t stream) {
   if (X == nullptr || state == nullptr || moments == nullptr || stats == nullptr || N < 1 || K < 1 || K > EM_MAXK || R < 1 || R > EM_MAXR)
     return LADDER_E_SHAPE;
-  if (em_misaligned(state) || em_misaligned(moments) || em_misaligned(stats) || em_misaligned(ws)) return LADDER_E_ALIGN;
+  if (fit_misaligned(state) || fit_misaligned(moments) || fit_misaligned(stats) || fit_misaligned(ws)) return LADDER_E_ALIGN;
   if (ws == nullptr || ws_bytes < ladder_emgmm_workspace_bytes(N, K, R)) return LADDER_E_WORKSPACE;
-  const EmSplit sp = em_split(N);
+  const FitSplit sp = fit_split(N);
   const int G = em_slices(N);
   const size_t n = em_stats_doubles(K, R);
   double* resp = static_cast<double*>(ws);
@@ -448,7 +427,7 @@ int ladder_emgmm_mstep(const double* stats, const double* moments, int K, int R,
   if (stats == nullptr || moments == nullptr || state == nullptr || weights == nullptr || means == nullptr || covs == nullptr || K < 1 || K > EM_MAXK ||
       R < 1 || R > EM_MAXR || max_iter < 0 || it < 0)
     return LADDER_E_SHAPE;
-  if (em_misaligned(stats) || em_misaligned(moments) || em_misaligned(state)) return LADDER_E_ALIGN;
+  if (fit_misaligned(stats) || fit_misaligned(moments) || fit_misaligned(state)) return LADDER_E_ALIGN;
   hipLaunchKernelGGL(emgmm_mstep_kernel, dim3(K), dim3(64), 0, stream, stats, moments, state, K, R, reg_covar, it, weights, means, covs);
   LADDER_CHECK_LAUNCH();
   hipLaunchKernelGGL(emgmm_finish_kernel, dim3(1), dim3(64), 0, stream, stats, moments, state, K, R, tol, max_iter, it);
@@ -458,7 +437,7 @@ int ladder_emgmm_mstep(const double* stats, const double* moments, int K, int R,
 
 int ladder_emgmm_prepare(double* state, int K, int R, ladder_stream_t stream) {
   if (state == nullptr || K < 1 || K > EM_MAXK || R < 1 || R > EM_MAXR) return LADDER_E_SHAPE;
-  if (em_misaligned(state)) return LADDER_E_ALIGN;
+  if (fit_misaligned(state)) return LADDER_E_ALIGN;
   hipLaunchKernelGGL(emgmm_prepare_kernel, dim3(K), dim3(64), 0, stream, state, K, R);
   LADDER_CHECK_LAUNCH();
   hipLaunchKernelGGL(emgmm_finish_kernel, dim3(1), dim3(64), 0, stream, (const double*)nullptr, (const double*)nullptr, state, K, R, 0.0, 0, -1);

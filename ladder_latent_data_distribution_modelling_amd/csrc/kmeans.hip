@@ -34,7 +34,7 @@
 //
 // Operand lane maps of v_mfma_f64_16x16x4_f64: head of csrc/fid.hip (A [m = lane & 15][k = lane >> 4], B [k][n = lane & 15],
 // C/D reg r: row (lane >> 4) + 4 r, col lane & 15).
-#include "common.h"
+#include "fit_util.h"
 
 #include <limits.h>
 
@@ -50,25 +50,12 @@ constexpr int KM_SLICE = 64;            // samples per assignment workgroup: 4 w
 constexpr int KM_LDC = 66;
 constexpr int KM_BLOCK = 256;           // samples per block of the seeding's scan
 constexpr int KM_MAXTRIALS = 6;         // 2 + int(ln 64)
-constexpr int KM_MAX_SPLITS = 32, KM_MIN_SPLIT_ROWS = 128;
 // integer part of the workspace
 constexpr int KI_CNT = 0, KI_CHANGED = 64, KI_PENDING = 65, KI_SEL = 66, KI_CAND = 68, KI_CHOSEN = 80, KI_TOTAL = 144;
 
 inline int km_trials(int K) { return 2 + (int)log((double)K); }
 inline int km_blocks(int N) { return (N + KM_BLOCK - 1) / KM_BLOCK; }
 inline int km_slices(int N) { return (N + KM_SLICE - 1) / KM_SLICE; }
-
-struct KmSplit {
-  int rows, nsplit;                    // rows per split (a multiple of 4), row splits
-};
-inline KmSplit km_split(int N) {
-  KmSplit p;
-  int rows = (N + KM_MAX_SPLITS - 1) / KM_MAX_SPLITS;
-  rows = rows < KM_MIN_SPLIT_ROWS ? KM_MIN_SPLIT_ROWS : rows;
-  p.rows = (rows + 3) / 4 * 4;
-  p.nsplit = (N + p.rows - 1) / p.rows;
-  return p;
-}
 
 // workspace: colsum [R] | sum x~ [R] | sum x~^2 [R] | potential, 3 spare | shifted centres [K,R] | per-split cluster sums [nsplit,K,R] | squared distance
 // to the own centre [N] | candidates' closest distances [6,N] | their block sums [6,nb] | offsets [nb+1] | integers [KI_TOTAL]
@@ -78,7 +65,7 @@ struct KmWs {
 };
 inline size_t km_ws_doubles(int N, int K, int R) {
   const size_t nb = km_blocks(N);
-  return 3 * (size_t)R + 4 + (size_t)K * R * (1 + km_split(N).nsplit) + (size_t)N * (1 + KM_MAXTRIALS) + KM_MAXTRIALS * nb + nb + 1;
+  return 3 * (size_t)R + 4 + (size_t)K * R * (1 + fit_split(N).nsplit) + (size_t)N * (1 + KM_MAXTRIALS) + KM_MAXTRIALS * nb + nb + 1;
 }
 inline KmWs km_ws(void* ws, int N, int K, int R) {
   const size_t nb = km_blocks(N);
@@ -89,7 +76,7 @@ inline KmWs km_ws(void* ws, int N, int K, int R) {
   W.scal = W.s2 + R;
   W.cs = W.scal + 4;
   W.part = W.cs + (size_t)K * R;
-  W.dist = W.part + (size_t)K * R * km_split(N).nsplit;
+  W.dist = W.part + (size_t)K * R * fit_split(N).nsplit;
   W.cc = W.dist + N;
   W.cblk = W.cc + (size_t)KM_MAXTRIALS * N;
   W.offs = W.cblk + KM_MAXTRIALS * nb;
@@ -116,23 +103,11 @@ __device__ __forceinline__ double km_block_scan(double v, double* s_w, int tid) 
   return off + v;
 }
 
-// Sum over the 256 threads: the shuffle tree, then the four wavefronts in order.  EVERY thread must call it; the result is valid in thread 0.
-__device__ __forceinline__ double km_block_sum(double a, double* s_w, int tid) {
-  a = wave_sum_d(a);
-  if ((tid & 63) == 0) s_w[tid >> 6] = a;
-  __syncthreads();
-  const double r = ((s_w[0] + s_w[1]) + s_w[2]) + s_w[3];
-  __syncthreads();
-  return r;
-}
-
 // ------------------------------------------------------------------------------------------------ preparation
 __global__ __launch_bounds__(256) void kmeans_colsum_kernel(const float* __restrict__ X, int N, int R, KmWs W) {
   const int j = blockIdx.x, tid = threadIdx.x;
   __shared__ double s_w[4];
-  double a = 0.0;
-  for (int n = tid; n < N; n += 256) a += (double)X[(size_t)n * R + j];
-  a = km_block_sum(a, s_w, tid);
+  const double a = column_sum_256(X, N, R, j, s_w, tid);
   if (tid == 0) W.colsum[j] = a;
 }
 
@@ -146,8 +121,8 @@ __global__ __launch_bounds__(256) void kmeans_moments_kernel(const float* __rest
     a1 += d;
     a2 += d * d;
   }
-  a1 = km_block_sum(a1, s_w, tid);
-  a2 = km_block_sum(a2, s_w, tid);
+  a1 = block_sum_256(a1, s_w, tid);
+  a2 = block_sum_256(a2, s_w, tid);
   if (tid == 0) {
     W.s1[j] = a1;
     W.s2[j] = a2;
@@ -288,7 +263,7 @@ __global__ __launch_bounds__(256) void kmeans_cand_kernel(const float* __restric
 // ------------------------------------------------------------------------------------------------ assignment
 __global__ __launch_bounds__(256) void kmeans_assign_kernel(const float* __restrict__ X, int N, int K, int R, int it, const double* __restrict__ state,
                                                             int* __restrict__ labels, KmWs W) {
-  if (state[(size_t)K * R + 3] != 0.0) return;                     // the fit is over: iterations enqueued past the end are no-ops
+  if (state[(size_t)K * R + FIT_DONE] != 0.0) return;              // the fit is over: iterations enqueued past the end are no-ops
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, m = lane & 15, kq = lane >> 4;
   const int n0 = blockIdx.x * KM_SLICE, rows = min(KM_SLICE, N - n0);
   __shared__ double s_C[KM_MAXK * KM_LDC], s_cn[KM_MAXK], s_sh[KM_MAXR];
@@ -385,7 +360,7 @@ __global__ __launch_bounds__(256) void kmeans_assign_kernel(const float* __restr
 // blockIdx.x = row split.  Wavefront w owns the clusters 16 w .. 16 w + 15: A = the one-hot labels, B = x~, four column blocks as MFMA accumulators.
 __global__ __launch_bounds__(256) void kmeans_sums_kernel(const float* __restrict__ X, const int* __restrict__ labels, const double* __restrict__ state, int N,
                                                           int K, int R, int rows, KmWs W) {
-  if (state[(size_t)K * R + 3] != 0.0 || W.ints[KI_PENDING] != 0) return;       // over, or only the final assignment is left
+  if (state[(size_t)K * R + FIT_DONE] != 0.0 || W.ints[KI_PENDING] != 0) return;       // over, or only the final assignment is left
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, m = lane & 15, kq = lane >> 4;
   const int nkb = (K + 15) / 16, nb = (R + 15) / 16;
   if (wave >= nkb) return;                                         // (whole wavefronts; no barrier in this kernel)
@@ -431,7 +406,7 @@ __global__ __launch_bounds__(256) void kmeans_sums_kernel(const float* __restric
 __global__ __launch_bounds__(256) void kmeans_update_kernel(const float* __restrict__ X, const int* __restrict__ labels, int N, int K, int R, int nsplit,
                                                             double tol, int max_iter, int it, double* __restrict__ state, KmWs W) {
   double* tail = state + (size_t)K * R;
-  if (tail[3] != 0.0) return;
+  if (tail[FIT_DONE] != 0.0) return;
   const int tid = threadIdx.x;
   __shared__ double s_sum[KM_MAXK * KM_MAXR], s_sh[KM_MAXR], s_sq[KM_MAXK], s_rd[256], s_w[4];
   __shared__ int s_cnt[KM_MAXK], s_el[KM_MAXK], s_taken[KM_MAXK], s_rn[256], s_ne, s_far, s_old, s_fin;
@@ -532,11 +507,11 @@ __global__ __launch_bounds__(256) void kmeans_update_kernel(const float* __restr
       W.scal[1] = shift;
       W.scal[2] = tol_;
       if (changed == 0) {                                           // strict convergence: the labels stand
-        tail[1] = (double)it;
+        tail[FIT_NITER] = (double)it;
         tail[2] = 2.0;
         s_fin = 1;
       } else if (shift <= tol_ || it >= max_iter) {                 // one more assignment against the final centres
-        tail[1] = (double)it;
+        tail[FIT_NITER] = (double)it;
         tail[2] = shift <= tol_ ? 1.0 : 3.0;
         W.ints[KI_PENDING] = 1;
       }
@@ -549,15 +524,14 @@ __global__ __launch_bounds__(256) void kmeans_update_kernel(const float* __restr
   if (finish) {                                                     // (uniform) inertia_ = sum of the squared distances to the own centres
     double a = 0.0;
     for (int n = tid; n < N; n += 256) a += W.dist[n];
-    a = km_block_sum(a, s_w, tid);
+    a = block_sum_256(a, s_w, tid);
     if (tid == 0) {
       tail[0] = a;
-      tail[3] = 1.0;
+      tail[FIT_DONE] = 1.0;
     }
   }
 }
 
-inline bool km_misaligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7u) != 0; }
 inline bool km_bad_shape(int N, int K, int R) { return K < 1 || K > KM_MAXK || R < 1 || R > KM_MAXR || N < K; }
 
 int km_prepare(const float* X, int N, int K, int R, double* state, const KmWs& W, hipStream_t stream) {
@@ -583,7 +557,7 @@ size_t ladder_kmeans_workspace_bytes(int N, int K, int R) {
 
 int ladder_kmeans_seed(const float* X, int N, int K, int R, const double* draws, double* state, void* ws, size_t ws_bytes, ladder_stream_t stream) {
   if (X == nullptr || draws == nullptr || state == nullptr || km_bad_shape(N, K, R)) return LADDER_E_SHAPE;
-  if (km_misaligned(draws) || km_misaligned(state) || km_misaligned(ws)) return LADDER_E_ALIGN;
+  if (fit_misaligned(draws) || fit_misaligned(state) || fit_misaligned(ws)) return LADDER_E_ALIGN;
   if (ws == nullptr || ws_bytes < ladder_kmeans_workspace_bytes(N, K, R)) return LADDER_E_SHAPE;                // (a workspace too short for the shape)
   const KmWs W = km_ws(ws, N, K, R);
   hipStream_t s = static_cast<hipStream_t>(stream);
@@ -603,7 +577,7 @@ int ladder_kmeans_seed(const float* X, int N, int K, int R, const double* draws,
 int ladder_kmeans_set_centres(const float* X, int N, int K, int R, const double* centres, double* state, void* ws, size_t ws_bytes,
                               ladder_stream_t stream) {
   if (X == nullptr || centres == nullptr || state == nullptr || km_bad_shape(N, K, R)) return LADDER_E_SHAPE;
-  if (km_misaligned(centres) || km_misaligned(state) || km_misaligned(ws)) return LADDER_E_ALIGN;
+  if (fit_misaligned(centres) || fit_misaligned(state) || fit_misaligned(ws)) return LADDER_E_ALIGN;
   if (ws == nullptr || ws_bytes < ladder_kmeans_workspace_bytes(N, K, R)) return LADDER_E_SHAPE;                // (a workspace too short for the shape)
   const KmWs W = km_ws(ws, N, K, R);
   hipStream_t s = static_cast<hipStream_t>(stream);
@@ -617,7 +591,7 @@ int ladder_kmeans_set_centres(const float* X, int N, int K, int R, const double*
 int ladder_kmeans_assign(const float* X, int N, int K, int R, int it, const double* state, int* labels, void* ws, size_t ws_bytes,
                          ladder_stream_t stream) {
   if (X == nullptr || state == nullptr || labels == nullptr || km_bad_shape(N, K, R) || it < 1) return LADDER_E_SHAPE;
-  if (km_misaligned(state) || km_misaligned(ws)) return LADDER_E_ALIGN;
+  if (fit_misaligned(state) || fit_misaligned(ws)) return LADDER_E_ALIGN;
   if (ws == nullptr || ws_bytes < ladder_kmeans_workspace_bytes(N, K, R)) return LADDER_E_SHAPE;                // (a workspace too short for the shape)
   const KmWs W = km_ws(ws, N, K, R);
   hipLaunchKernelGGL(kmeans_assign_kernel, dim3(km_slices(N)), dim3(256), 0, static_cast<hipStream_t>(stream), X, N, K, R, it, state, labels, W);
@@ -628,10 +602,10 @@ int ladder_kmeans_assign(const float* X, int N, int K, int R, int it, const doub
 int ladder_kmeans_update(const float* X, int N, int K, int R, const int* labels, double* state, double tol, int max_iter, int it, void* ws,
                          size_t ws_bytes, ladder_stream_t stream) {
   if (X == nullptr || state == nullptr || labels == nullptr || km_bad_shape(N, K, R) || max_iter < 1 || it < 1) return LADDER_E_SHAPE;
-  if (km_misaligned(state) || km_misaligned(ws)) return LADDER_E_ALIGN;
+  if (fit_misaligned(state) || fit_misaligned(ws)) return LADDER_E_ALIGN;
   if (ws == nullptr || ws_bytes < ladder_kmeans_workspace_bytes(N, K, R)) return LADDER_E_SHAPE;                // (a workspace too short for the shape)
   const KmWs W = km_ws(ws, N, K, R);
-  const KmSplit sp = km_split(N);
+  const FitSplit sp = fit_split(N);
   hipStream_t s = static_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(kmeans_sums_kernel, dim3(sp.nsplit), dim3(256), 0, s, X, labels, (const double*)state, N, K, R, sp.rows, W);
   LADDER_CHECK_LAUNCH();

@@ -3,28 +3,23 @@
 // n_components=K, covariance_type='full', weight_concentration_prior_type='dirichlet_distribution' | 'dirichlet_process',
 // weight_concentration_prior=0.1, warm_start=True).fit(t_samples)  (codes/base.py:93-99, 681-789).
 //
-// The problem is tiny and strictly sequential (N ~ 2e3..2e4 samples of R <= 8 dims, K <= 64 components, 10..1000 dependent
-// E/M iterations), so the MI355X-shaped answer is ONE persistent workgroup of 16 wavefronts that keeps the whole VB loop --
-// E-step, sufficient statistics, Wishart/Dirichlet updates, lower bound, convergence test -- inside a single launch: no host
-// round trip per iteration (or per epoch), no launch latency on the critical path, and the fitted mixture stays in HBM for
-// ladder_gmm_prepare.  Arithmetic is float64 like sklearn's; reductions run in a fixed order (deterministic, so every
-// data-parallel rank that runs the fit on the same gathered samples gets bit-identical parameters without a broadcast).
-//
-// The update equations restate sklearn 1.7's _bayesian_mixture.py / _gaussian_mixture.py (BSD-3, third-party dependency of the
-// reference, requirements.txt:4): _estimate_gaussian_parameters, _estimate_weights/_means/_wishart_full,
-// _compute_precision_cholesky, _estimate_log_prob, _estimate_log_weights, _compute_lower_bound and the loop of
-// BaseMixture.fit_predict.  tests/test_gpu_vbgmm.py compares against sklearn itself through its public API.
-#include <hip/hip_runtime.h>
-
-#include "common.h"
-#include "ladder_hip.h"
+// The problem is tiny and strictly sequential (N ~ 2e3..2e4 samples of R <= 8 dims, K <= 64 components, 10..1000 dependent E/M
+// iterations).  Arithmetic is float64 like sklearn's; every reduction has one fixed order, so a fit gives the same bits on every run
+// and on every rank.  Two paths call the SAME device functions (vb_*) for all that sklearn defines -- the one-hot start, the E-step, the
+// Dirichlet / Wishart update with its Cholesky and inverse, the lower bound, _set_parameters:
+//   vbgmm_fit_kernel                   below 1 024 samples: ONE persistent workgroup of 16 wavefronts keeps the whole VB loop in one launch
+//   vbgmm_shard_{estep,mstep}_kernel   every other fit: an E-step launch over 256-sample slices + an M-step launch per iteration, the samples
+//                                      possibly sharded over the data-parallel ranks
+// They differ in ONE thing, the statistics pass: the persistent kernel centres the second moments before summing, as sklearn does; the
+// sharded path sums raw moments (additive over slices and ranks) and centres them in the M-step (the two forms agree to ~1e-13).
+// The functions are forced-inline and restate sklearn 1.7's _bayesian_mixture.py / _gaussian_mixture.py (BSD-3) in sklearn's evaluation
+// order -- do not reorder a sum or merge (x - mu) P: -ffp-contract=fast fuses by what surrounds a statement.  tests/test_gpu_vbgmm.py
+// compares against sklearn itself through its public API.
+#include "fit_util.h"
 
 namespace {
 
-constexpr int VB_THREADS = 1024;
-constexpr int VB_WAVES = VB_THREADS / 64;
-constexpr int VB_MAXK = 64;
-constexpr int VB_MAXR = 8;
+constexpr int VB_THREADS = 1024, VB_WAVES = VB_THREADS / 64, VB_MAXK = 64, VB_MAXR = 8;
 
 struct VbCfg {
   int N, K, R, prior_type, max_iter, init_from_labels;
@@ -44,13 +39,7 @@ __device__ double vb_digamma(double x) {
   return r + log(x) - 0.5 / x + t;
 }
 
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-// state layout (doubles): wa[K] wb[K] mean_prec[K] dof[K] means[K*R] cov[K*R*R] prec_chol[K*R*R] | lower_bound n_iter converged
+// state layout (doubles): wa[K] wb[K] mean_prec[K] dof[K] means[K*R] cov[K*R*R] prec_chol[K*R*R] | the four tail doubles of fit_util.h
 struct VbState {
   double *wa, *wb, *mprec, *dof, *means, *cov, *pchol, *tail;
   __device__ VbState(double* s, int K, int R) {
@@ -59,240 +48,168 @@ struct VbState {
   }
 };
 
-__global__ __launch_bounds__(VB_THREADS) void vbgmm_fit_kernel(const float* __restrict__ X, const int* __restrict__ labels,
-                                                               double* __restrict__ state, VbCfg c, double* __restrict__ resp,
-                                                               float* __restrict__ w_out, float* __restrict__ m_out,
-                                                               float* __restrict__ c_out) {
-  const int N = c.N, K = c.K, R = c.R, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  VbState S(state, K, R);
-  __shared__ double s_nk[VB_MAXK], s_ck[VB_MAXK], s_xk[VB_MAXK * VB_MAXR], s_mu[VB_MAXK * VB_MAXR];
-  __shared__ double s_pc[VB_MAXK * VB_MAXR * VB_MAXR];          // precisions_cholesky_ (upper triangular), E-step operand
-  __shared__ double s_sk[VB_MAXK * VB_MAXR * VB_MAXR];          // empirical covariances (M-step)
-  __shared__ double s_prior_mean[VB_MAXR], s_prior_cov[VB_MAXR * VB_MAXR];
-  __shared__ double s_red[VB_WAVES], s_scal[4];
-  __shared__ int s_flag;
+// ---------------------------------------------------------------------------------------------------------------- shared by both paths
+// _initialize_parameters: one-hot responsibilities from the k-means labels
+__device__ __forceinline__ void vb_onehot(const int* __restrict__ labels, int N, int K, double* __restrict__ resp, int tid, int nthreads) {
+  for (size_t i = tid; i < (size_t)N * K; i += nthreads) resp[i] = (labels[i / K] == (int)(i % K)) ? 1.0 : 0.0;
+}
 
-  // ---- priors from the data, as _check_parameters(X) does on every fit: mean_prior_ = X.mean(0), covariance_prior_ = cov(X.T)
-  for (int r = wave; r < R; r += VB_WAVES) {
-    double a = 0.0;
-    for (int n = lane; n < N; n += 64) a += (double)X[(size_t)n * R + r];
-    a = wave_sum(a);
-    if (lane == 0) s_prior_mean[r] = a / N;
+// The E-step on the N rows of X (_estimate_log_prob_resp): resp <- responsibilities; returns sum r log r in thread 0 (0 elsewhere).
+// EVERY thread of the VB_THREADS must call it (three barriers); s_scal: 1, s_red: VB_WAVES doubles of LDS.
+__device__ __forceinline__ double vb_estep(const float* __restrict__ X, int N, const VbState& S, const VbCfg& c, double* s_mu, double* s_pc,
+                                           double* s_ck, double* s_scal, double* s_red, double* __restrict__ resp, int tid) {
+  const int K = c.K, R = c.R;
+  if (tid == 0 && c.prior_type == 0) {
+    double sw = 0.0;
+    for (int k = 0; k < K; ++k) sw += S.wa[k];
+    s_scal[0] = vb_digamma(sw);
+  }
+  for (int i = tid; i < K * R; i += VB_THREADS) s_mu[i] = S.means[i];
+  for (int i = tid; i < K * R * R; i += VB_THREADS) s_pc[i] = S.pchol[i];
+  __syncthreads();
+  if (tid < K) {                                                  // s_ck[k]: what _estimate_log_prob + _estimate_log_weights give per component
+    const int k = tid;
+    double log_det = 0.0, log_lambda = R * log(2.0);
+    for (int j = 0; j < R; ++j) {
+      log_det += log(s_pc[(k * R + j) * R + j]);
+      log_lambda += vb_digamma(0.5 * (S.dof[k] - j));
+    }
+    double lw;
+    if (c.prior_type == 0) {
+      lw = vb_digamma(S.wa[k]) - s_scal[0];
+    } else {            // stick breaking: digamma(a) - digamma(a+b) + sum_{j<k} (digamma(b_j) - digamma(a_j+b_j))
+      lw = vb_digamma(S.wa[k]) - vb_digamma(S.wa[k] + S.wb[k]);
+      for (int j = 0; j < k; ++j) lw += vb_digamma(S.wb[j]) - vb_digamma(S.wa[j] + S.wb[j]);
+    }
+    s_ck[k] = -0.5 * R * log(2.0 * M_PI) + log_det - 0.5 * R * log(S.dof[k]) + 0.5 * (log_lambda - R / S.mprec[k]) + lw;
   }
   __syncthreads();
-  for (int p = wave; p < R * R; p += VB_WAVES) {
-    const int i = p / R, j = p - i * R;
-    double a = 0.0;
-    for (int n = lane; n < N; n += 64)
-      a += ((double)X[(size_t)n * R + i] - s_prior_mean[i]) * ((double)X[(size_t)n * R + j] - s_prior_mean[j]);
-    a = wave_sum(a);
-    if (lane == 0) s_prior_cov[p] = a / (N - 1);
-  }
-  if (c.init_from_labels)
-    for (size_t i = tid; i < (size_t)N * K; i += VB_THREADS) resp[i] = (labels[i / K] == (int)(i % K)) ? 1.0 : 0.0;
-  __syncthreads();
-
-  double lower_bound = c.init_from_labels ? -INFINITY : S.tail[0];
-  int n_iter = 0, converged = 0;
-  // iteration 0 = _initialize(X, resp) (M-step on the one-hot responsibilities); a warm start skips it.
-  for (int it = c.init_from_labels ? 0 : 1; it <= c.max_iter; ++it) {
-    double entropy = 0.0;      // sum_nk resp * log_resp of this iteration's E-step (thread 0)
-    if (it > 0) {
-      // ------------------------------------------------------------------ E-step (_estimate_log_prob_resp)
-      if (tid == 0) {
-        double sw = 0.0;
-        if (c.prior_type == 0) {
-          for (int k = 0; k < K; ++k) sw += S.wa[k];
-          s_scal[0] = vb_digamma(sw);
-        }
-      }
-      for (int i = tid; i < K * R; i += VB_THREADS) s_mu[i] = S.means[i];
-      for (int i = tid; i < K * R * R; i += VB_THREADS) s_pc[i] = S.pchol[i];
-      __syncthreads();
-      if (tid < K) {
-        const int k = tid;
-        double log_det = 0.0, log_lambda = R * log(2.0);
-        for (int j = 0; j < R; ++j) {
-          log_det += log(s_pc[(k * R + j) * R + j]);
-          log_lambda += vb_digamma(0.5 * (S.dof[k] - j));
-        }
-        double lw;
-        if (c.prior_type == 0) {
-          lw = vb_digamma(S.wa[k]) - s_scal[0];
-        } else {            // stick breaking: digamma(a) - digamma(a+b) + sum_{j<k} (digamma(b_j) - digamma(a_j+b_j))
-          lw = vb_digamma(S.wa[k]) - vb_digamma(S.wa[k] + S.wb[k]);
-          for (int j = 0; j < k; ++j) lw += vb_digamma(S.wb[j]) - vb_digamma(S.wa[j] + S.wb[j]);
-        }
-        s_ck[k] = -0.5 * R * log(2.0 * M_PI) + log_det - 0.5 * R * log(S.dof[k]) + 0.5 * (log_lambda - R / S.mprec[k]) + lw;
-      }
-      __syncthreads();
-      double ent = 0.0;
-      for (int n = tid; n < N; n += VB_THREADS) {
-        double x[VB_MAXR];
-        for (int i = 0; i < R; ++i) x[i] = (double)X[(size_t)n * R + i];
-        double* wr = resp + (size_t)n * K;
-        double mx = -INFINITY;
-        for (int k = 0; k < K; ++k) {
-          const double* P = s_pc + (size_t)k * R * R;
-          const double* mu = s_mu + k * R;
-          double q = 0.0;
-          for (int j = 0; j < R; ++j) {
-            double xy = 0.0, my = 0.0;                    // y = X @ prec_chol - mu @ prec_chol, as sklearn evaluates it
-            for (int i = 0; i <= j; ++i) {
-              xy += x[i] * P[i * R + j];
-              my += mu[i] * P[i * R + j];
-            }
-            const double y = xy - my;
-            q += y * y;
-          }
-          const double w = s_ck[k] - 0.5 * q;
-          wr[k] = w;
-          mx = fmax(mx, w);
-        }
-        double se = 0.0;
-        for (int k = 0; k < K; ++k) se += exp(wr[k] - mx);
-        const double lse = mx + log(se);
-        for (int k = 0; k < K; ++k) {
-          const double lr = wr[k] - lse, r = exp(lr);
-          wr[k] = r;
-          ent += r * lr;
-        }
-      }
-      ent = wave_sum(ent);
-      if (lane == 0) s_red[wave] = ent;
-      __syncthreads();
-      if (tid == 0) {
-        for (int w = 0; w < VB_WAVES; ++w) entropy += s_red[w];
-      }
-    }
-    // -------------------------------------------------------------------- M-step (_estimate_gaussian_parameters + updates)
-    for (int k = wave; k < K; k += VB_WAVES) {
-      double a = 0.0;
-      for (int n = lane; n < N; n += 64) a += resp[(size_t)n * K + k];
-      a = wave_sum(a);
-      if (lane == 0) s_nk[k] = a + 10.0 * 2.220446049250313e-16;
-    }
-    __syncthreads();
-    for (int p = wave; p < K * R; p += VB_WAVES) {
-      const int k = p / R, r = p - k * R;
-      double a = 0.0;
-      for (int n = lane; n < N; n += 64) a += resp[(size_t)n * K + k] * (double)X[(size_t)n * R + r];
-      a = wave_sum(a);
-      if (lane == 0) s_xk[p] = a / s_nk[k];
-    }
-    __syncthreads();
-    const int npair = R * (R + 1) / 2;
-    for (int p = wave; p < K * npair; p += VB_WAVES) {
-      const int k = p / npair;
-      int q = p - k * npair, i = 0;
-      while (q >= R - i) { q -= R - i; ++i; }
-      const int j = i + q;
-      double a = 0.0;
-      for (int n = lane; n < N; n += 64)
-        a += resp[(size_t)n * K + k] * ((double)X[(size_t)n * R + i] - s_xk[k * R + i]) * ((double)X[(size_t)n * R + j] - s_xk[k * R + j]);
-      a = wave_sum(a);
-      if (lane == 0) {
-        a = a / s_nk[k] + (i == j ? c.reg_covar : 0.0);
-        s_sk[(k * R + i) * R + j] = a;
-        s_sk[(k * R + j) * R + i] = a;
-      }
-    }
-    __syncthreads();
-    if (tid == 0) s_flag = 0;
-    __syncthreads();
-    if (tid < K) {
-      const int k = tid;
-      const double nk = s_nk[k];
-      if (c.prior_type == 0) {
-        S.wa[k] = c.wc_prior + nk;                                    // dirichlet_distribution
-        S.wb[k] = 0.0;
-      } else {
-        double tail = 0.0;                                            // sum_{j>k} nk_j
-        for (int j = K - 1; j > k; --j) tail += s_nk[j];
-        S.wa[k] = 1.0 + nk;
-        S.wb[k] = c.wc_prior + tail;
-      }
-      const double mp = c.mean_prec_prior + nk;
-      S.mprec[k] = mp;
-      for (int r = 0; r < R; ++r) S.means[k * R + r] = (c.mean_prec_prior * s_prior_mean[r] + nk * s_xk[k * R + r]) / mp;
-      const double dof = (double)R + nk;                              // degrees_of_freedom_prior_ = n_features
-      S.dof[k] = dof;
-      double* C = S.cov + (size_t)k * R * R;
-      for (int i = 0; i < R; ++i)
-        for (int j = 0; j < R; ++j) {
-          const double di = s_xk[k * R + i] - s_prior_mean[i], dj = s_xk[k * R + j] - s_prior_mean[j];
-          C[i * R + j] = (s_prior_cov[i * R + j] + nk * s_sk[(k * R + i) * R + j] + nk * c.mean_prec_prior / mp * (di * dj)) / dof;
-        }
-      // precisions_cholesky_ = solve_triangular(cholesky(cov, lower), I, lower).T   (s_sk slot reused as scratch for L)
-      double* Lm = s_sk + (size_t)k * R * R;
-      bool ok = true;
+  double ent = 0.0;
+  for (int n = tid; n < N; n += VB_THREADS) {
+    double x[VB_MAXR];
+    for (int i = 0; i < R; ++i) x[i] = (double)X[(size_t)n * R + i];
+    double* wr = resp + (size_t)n * K;
+    double mx = -INFINITY;
+    for (int k = 0; k < K; ++k) {
+      const double* P = s_pc + (size_t)k * R * R;
+      const double* mu = s_mu + k * R;
+      double q = 0.0;
       for (int j = 0; j < R; ++j) {
-        double d = C[j * R + j];
-        for (int p = 0; p < j; ++p) d -= Lm[j * R + p] * Lm[j * R + p];
-        if (!(d > 0.0)) { ok = false; d = 1.0; }
-        const double ljj = sqrt(d);
-        Lm[j * R + j] = ljj;
-        for (int i = j + 1; i < R; ++i) {
-          double v = C[i * R + j];
-          for (int p = 0; p < j; ++p) v -= Lm[i * R + p] * Lm[j * R + p];
-          Lm[i * R + j] = v / ljj;
+        double xy = 0.0, my = 0.0;                    // y = X @ prec_chol - mu @ prec_chol, as sklearn evaluates it
+        for (int i = 0; i <= j; ++i) {
+          xy += x[i] * P[i * R + j];
+          my += mu[i] * P[i * R + j];
         }
+        const double y = xy - my;
+        q += y * y;
       }
-      if (!ok) atomicExch(&s_flag, 1);                                // ill-defined empirical covariance (sklearn raises)
-      double* Pk = S.pchol + (size_t)k * R * R;
-      for (int col = 0; col < R; ++col) {                             // column `col` of L^-1 by forward substitution
-        for (int i = 0; i < R; ++i) {
-          double v = (i == col) ? 1.0 : 0.0;
-          for (int p = col; p < i; ++p) v -= Lm[i * R + p] * Pk[col * R + p];   // Pk[col][p] = (L^-1)[p][col] (transposed store)
-          Pk[col * R + i] = (i < col) ? 0.0 : v / Lm[i * R + i];
-        }
-      }
+      const double w = s_ck[k] - 0.5 * q;
+      wr[k] = w;
+      mx = fmax(mx, w);
     }
-    __syncthreads();
-    if (s_flag) {
-      if (tid == 0) { S.tail[0] = lower_bound; S.tail[1] = n_iter; S.tail[2] = -1.0; }
-      return;
+    double se = 0.0;
+    for (int k = 0; k < K; ++k) se += exp(wr[k] - mx);
+    const double lse = mx + log(se);
+    for (int k = 0; k < K; ++k) {
+      const double lr = wr[k] - lse, r = exp(lr);
+      wr[k] = r;
+      ent += r * lr;
     }
-    if (it == 0) continue;
-    // -------------------------------------------------------------------- lower bound + convergence (_compute_lower_bound)
-    if (tid == 0) {
-      double log_wishart = 0.0, sum_log_mp = 0.0, log_norm_weight;
-      for (int k = 0; k < K; ++k) {
-        const double* Pk = S.pchol + (size_t)k * R * R;
-        double ld = 0.0, lg = 0.0;
-        for (int j = 0; j < R; ++j) {
-          ld += log(Pk[j * R + j]);
-          lg += lgamma(0.5 * (S.dof[k] - j));
-        }
-        ld -= 0.5 * R * log(S.dof[k]);
-        log_wishart += -(S.dof[k] * ld + S.dof[k] * R * 0.5 * log(2.0) + lg);
-        sum_log_mp += log(S.mprec[k]);
-      }
-      if (c.prior_type == 0) {
-        double sw = 0.0, sl = 0.0;
-        for (int k = 0; k < K; ++k) { sw += S.wa[k]; sl += lgamma(S.wa[k]); }
-        log_norm_weight = lgamma(sw) - sl;
-      } else {
-        double sb = 0.0;
-        for (int k = 0; k < K; ++k) sb += lgamma(S.wa[k]) + lgamma(S.wb[k]) - lgamma(S.wa[k] + S.wb[k]);   // betaln
-        log_norm_weight = -sb;
-      }
-      const double lb = -entropy - log_wishart - log_norm_weight - 0.5 * R * sum_log_mp;
-      s_scal[1] = lb;
-      s_flag = fabs(lb - lower_bound) < c.tol ? 2 : 0;
-    }
-    __syncthreads();
-    lower_bound = s_scal[1];
-    n_iter = it;
-    if (s_flag == 2) { converged = 1; break; }
-    __syncthreads();
   }
+  ent = wave_sum_d(ent);                                          // the shuffle tree, then the wavefronts in the order 0, 1, ...
+  if ((tid & 63) == 0) s_red[tid >> 6] = ent;
   __syncthreads();
-  // ---- _set_parameters: weights_, means_, covariances_ (float64 in `state`, float32 copies for the mixture feed)
+  double entropy = 0.0;
+  if (tid == 0)
+    for (int w = 0; w < VB_WAVES; ++w) entropy += s_red[w];
+  return entropy;
+}
+
+// _m_step for component k from nk, xk and the CENTRED empirical covariance sk (+ reg_covar): _estimate_weights, _estimate_means,
+// _estimate_wishart_full, _compute_precision_cholesky.  One thread per component; s_sk[k] is reused as scratch for the Cholesky factor.
+// A non-positive pivot (ill-defined empirical covariance, sklearn raises) sets *s_flag, between the factorisation and the inverse.
+__device__ __forceinline__ void vb_update_component(int k, const VbState& S, const VbCfg& c, const double* s_nk, const double* s_xk, double* s_sk,
+                                                    const double* s_prior_mean, const double* s_prior_cov, int* s_flag) {
+  const int K = c.K, R = c.R;
+  const double nk = s_nk[k];
+  if (c.prior_type == 0) {
+    S.wa[k] = c.wc_prior + nk;                                    // dirichlet_distribution
+    S.wb[k] = 0.0;
+  } else {
+    double tail = 0.0;                                            // sum_{j>k} nk_j
+    for (int j = K - 1; j > k; --j) tail += s_nk[j];
+    S.wa[k] = 1.0 + nk;
+    S.wb[k] = c.wc_prior + tail;
+  }
+  const double mp = c.mean_prec_prior + nk;
+  S.mprec[k] = mp;
+  for (int r = 0; r < R; ++r) S.means[k * R + r] = (c.mean_prec_prior * s_prior_mean[r] + nk * s_xk[k * R + r]) / mp;
+  const double dof = (double)R + nk;                              // degrees_of_freedom_prior_ = n_features
+  S.dof[k] = dof;
+  double* C = S.cov + (size_t)k * R * R;
+  for (int i = 0; i < R; ++i)
+    for (int j = 0; j < R; ++j) {
+      const double di = s_xk[k * R + i] - s_prior_mean[i], dj = s_xk[k * R + j] - s_prior_mean[j];
+      C[i * R + j] = (s_prior_cov[i * R + j] + nk * s_sk[(k * R + i) * R + j] + nk * c.mean_prec_prior / mp * (di * dj)) / dof;
+    }
+  // precisions_cholesky_ = solve_triangular(cholesky(cov, lower), I, lower).T   (s_sk slot reused as scratch for L)
+  double* Lm = s_sk + (size_t)k * R * R;
+  bool ok = true;
+  for (int j = 0; j < R; ++j) {
+    double d = C[j * R + j];
+    for (int p = 0; p < j; ++p) d -= Lm[j * R + p] * Lm[j * R + p];
+    if (!(d > 0.0)) { ok = false; d = 1.0; }
+    const double ljj = sqrt(d);
+    Lm[j * R + j] = ljj;
+    for (int i = j + 1; i < R; ++i) {
+      double v = C[i * R + j];
+      for (int p = 0; p < j; ++p) v -= Lm[i * R + p] * Lm[j * R + p];
+      Lm[i * R + j] = v / ljj;
+    }
+  }
+  if (!ok) atomicExch(s_flag, 1);
+  double* Pk = S.pchol + (size_t)k * R * R;
+  for (int col = 0; col < R; ++col) {                             // column `col` of L^-1 by forward substitution
+    for (int i = 0; i < R; ++i) {
+      double v = (i == col) ? 1.0 : 0.0;
+      for (int p = col; p < i; ++p) v -= Lm[i * R + p] * Pk[col * R + p];   // Pk[col][p] = (L^-1)[p][col] (transposed store)
+      Pk[col * R + i] = (i < col) ? 0.0 : v / Lm[i * R + i];
+    }
+  }
+}
+
+// _compute_lower_bound (log-Wishart, log-norm-weight) from the updated state and this iteration's sum r log r.  One thread.
+__device__ __forceinline__ double vb_lower_bound(const VbState& S, const VbCfg& c, double entropy) {
+  const int K = c.K, R = c.R;
+  double log_wishart = 0.0, sum_log_mp = 0.0, log_norm_weight;
+  for (int k = 0; k < K; ++k) {
+    const double* Pk = S.pchol + (size_t)k * R * R;
+    double ld = 0.0, lg = 0.0;
+    for (int j = 0; j < R; ++j) {
+      ld += log(Pk[j * R + j]);
+      lg += lgamma(0.5 * (S.dof[k] - j));
+    }
+    ld -= 0.5 * R * log(S.dof[k]);
+    log_wishart += -(S.dof[k] * ld + S.dof[k] * R * 0.5 * log(2.0) + lg);
+    sum_log_mp += log(S.mprec[k]);
+  }
+  if (c.prior_type == 0) {
+    double sw = 0.0, sl = 0.0;
+    for (int k = 0; k < K; ++k) { sw += S.wa[k]; sl += lgamma(S.wa[k]); }
+    log_norm_weight = lgamma(sw) - sl;
+  } else {
+    double sb = 0.0;
+    for (int k = 0; k < K; ++k) sb += lgamma(S.wa[k]) + lgamma(S.wb[k]) - lgamma(S.wa[k] + S.wb[k]);   // betaln
+    log_norm_weight = -sb;
+  }
+  return -entropy - log_wishart - log_norm_weight - 0.5 * R * sum_log_mp;
+}
+
+// _set_parameters: the normalised weights_ (thread 0; s_ck is scratch) and the float32 copies for the mixture feed
+__device__ __forceinline__ void vb_write_feed(const VbState& S, const VbCfg& c, double* s_ck, float* __restrict__ w_out, float* __restrict__ m_out,
+                                              float* __restrict__ c_out, int tid, int nthreads) {
+  const int K = c.K, R = c.R;
   if (tid == 0) {
-    S.tail[0] = lower_bound;
-    S.tail[1] = n_iter;
-    S.tail[2] = converged;
     double tot = 0.0;
     if (c.prior_type == 0) {
       for (int k = 0; k < K; ++k) tot += S.wa[k];
@@ -308,21 +225,110 @@ __global__ __launch_bounds__(VB_THREADS) void vbgmm_fit_kernel(const float* __re
       for (int k = 0; k < K; ++k) w_out[k] = (float)(s_ck[k] / tot);
     }
   }
-  for (int i = tid; i < K * R; i += VB_THREADS) m_out[i] = (float)S.means[i];
-  for (int i = tid; i < K * R * R; i += VB_THREADS) c_out[i] = (float)S.cov[i];
+  for (int i = tid; i < K * R; i += nthreads) m_out[i] = (float)S.means[i];
+  for (int i = tid; i < K * R * R; i += nthreads) c_out[i] = (float)S.cov[i];
 }
 
-// ==================================================================================================================================
+__global__ __launch_bounds__(VB_THREADS) void vbgmm_fit_kernel(const float* __restrict__ X, const int* __restrict__ labels, double* __restrict__ state, VbCfg c,
+                                                               double* __restrict__ resp, float* __restrict__ w_out, float* __restrict__ m_out,
+                                                               float* __restrict__ c_out) {
+  const int N = c.N, K = c.K, R = c.R, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  VbState S(state, K, R);
+  __shared__ double s_nk[VB_MAXK], s_ck[VB_MAXK], s_xk[VB_MAXK * VB_MAXR], s_mu[VB_MAXK * VB_MAXR];
+  __shared__ double s_pc[VB_MAXK * VB_MAXR * VB_MAXR];          // precisions_cholesky_ (upper triangular), E-step operand
+  __shared__ double s_sk[VB_MAXK * VB_MAXR * VB_MAXR];          // empirical covariances (M-step)
+  __shared__ double s_prior_mean[VB_MAXR], s_prior_cov[VB_MAXR * VB_MAXR];
+  __shared__ double s_red[VB_WAVES], s_scal[4];
+  __shared__ int s_flag;
+  // ---- priors from the data, as _check_parameters(X) does on every fit: mean_prior_ = X.mean(0), covariance_prior_ = cov(X.T)
+  for (int r = wave; r < R; r += VB_WAVES) {
+    double a = 0.0;
+    for (int n = lane; n < N; n += 64) a += (double)X[(size_t)n * R + r];
+    a = wave_sum_d(a);
+    if (lane == 0) s_prior_mean[r] = a / N;
+  }
+  __syncthreads();
+  for (int p = wave; p < R * R; p += VB_WAVES) {
+    const int i = p / R, j = p - i * R;
+    double a = 0.0;
+    for (int n = lane; n < N; n += 64)
+      a += ((double)X[(size_t)n * R + i] - s_prior_mean[i]) * ((double)X[(size_t)n * R + j] - s_prior_mean[j]);
+    a = wave_sum_d(a);
+    if (lane == 0) s_prior_cov[p] = a / (N - 1);
+  }
+  if (c.init_from_labels) vb_onehot(labels, N, K, resp, tid, VB_THREADS);
+  __syncthreads();
+  double lower_bound = c.init_from_labels ? -INFINITY : S.tail[FIT_LB];
+  int n_iter = 0, converged = 0;
+  // iteration 0 = _initialize(X, resp) (M-step on the one-hot responsibilities); a warm start skips it.
+  for (int it = c.init_from_labels ? 0 : 1; it <= c.max_iter; ++it) {
+    double entropy = 0.0;      // sum_nk resp * log_resp of this iteration's E-step (thread 0)
+    if (it > 0) entropy = vb_estep(X, N, S, c, s_mu, s_pc, s_ck, s_scal, s_red, resp, tid);
+    // M-step: _estimate_gaussian_parameters, the second moments CENTRED before they are summed (as sklearn does)
+    for (int k = wave; k < K; k += VB_WAVES) {
+      double a = 0.0;
+      for (int n = lane; n < N; n += 64) a += resp[(size_t)n * K + k];
+      a = wave_sum_d(a);
+      if (lane == 0) s_nk[k] = a + kEps10;
+    }
+    __syncthreads();
+    for (int p = wave; p < K * R; p += VB_WAVES) {
+      const int k = p / R, r = p - k * R;
+      double a = 0.0;
+      for (int n = lane; n < N; n += 64) a += resp[(size_t)n * K + k] * (double)X[(size_t)n * R + r];
+      a = wave_sum_d(a);
+      if (lane == 0) s_xk[p] = a / s_nk[k];
+    }
+    __syncthreads();
+    const int npair = R * (R + 1) / 2;
+    for (int p = wave; p < K * npair; p += VB_WAVES) {
+      const int k = p / npair;
+      int q = p - k * npair, i = 0;
+      while (q >= R - i) { q -= R - i; ++i; }
+      const int j = i + q;
+      double a = 0.0;
+      for (int n = lane; n < N; n += 64)
+        a += resp[(size_t)n * K + k] * ((double)X[(size_t)n * R + i] - s_xk[k * R + i]) * ((double)X[(size_t)n * R + j] - s_xk[k * R + j]);
+      a = wave_sum_d(a);
+      if (lane == 0) {
+        a = a / s_nk[k] + (i == j ? c.reg_covar : 0.0);
+        s_sk[(k * R + i) * R + j] = a;
+        s_sk[(k * R + j) * R + i] = a;
+      }
+    }
+    __syncthreads();
+    if (tid == 0) s_flag = 0;
+    __syncthreads();
+    if (tid < K) vb_update_component(tid, S, c, s_nk, s_xk, s_sk, s_prior_mean, s_prior_cov, &s_flag);
+    __syncthreads();
+    if (s_flag) {
+      if (tid == 0) { S.tail[FIT_LB] = lower_bound; S.tail[FIT_NITER] = n_iter; S.tail[FIT_CONVERGED] = -1.0; }
+      return;
+    }
+    if (it == 0) continue;
+    if (tid == 0) {                                                  // lower bound + convergence
+      const double lb = vb_lower_bound(S, c, entropy);
+      s_scal[1] = lb;
+      s_flag = fabs(lb - lower_bound) < c.tol ? 2 : 0;
+    }
+    __syncthreads();
+    lower_bound = s_scal[1];
+    n_iter = it;
+    if (s_flag == 2) { converged = 1; break; }
+    __syncthreads();
+  }
+  __syncthreads();
+  if (tid == 0) { S.tail[FIT_LB] = lower_bound; S.tail[FIT_NITER] = n_iter; S.tail[FIT_CONVERGED] = converged; }
+  vb_write_feed(S, c, s_ck, w_out, m_out, c_out, tid, VB_THREADS);
+}
+
 // The SHARDED fit (data-parallel exchange step C5, round 3): every rank keeps only ITS samples.  One variational iteration =
 //   vbgmm_shard_estep_kernel   E-step on the local samples with the (replicated) current parameters + the local SUFFICIENT STATISTICS
 //                              stats = [ sum r log r | n_k | sum_n r_nk x_n | sum_n r_nk x_n x_n^T ]   (1 + K + K R + K R R doubles)
 //   all-reduce(stats)          over RCCL / xGMI by the host (torch.distributed; a few KB)
 //   vbgmm_shard_mstep_kernel   M-step from the GLOBAL statistics, lower bound, convergence test -- identical on every rank
-// The priors sklearn takes from the data (mean_prior_ = X.mean(0), covariance_prior_ = cov(X.T)) come from all-reduced raw moments
-// (vbgmm_moments_kernel).  Both kernels return at once when the state's `done` flag (tail[3]) is set, so the host may enqueue
-// iterations ahead and look at the flag only every few iterations without changing the result.  Second moments are accumulated raw
-// (sum r x x^T) and centred in the M-step, where sklearn (and the persistent kernel above) centre before summing: float64 on O(1..10)
-// latent coordinates -- the two forms agree to ~1e-13, tests/test_gpu_vbgmm.py holds the sharded fit to sklearn at 1e-7.
+// The priors sklearn takes from the data (mean_prior_ = X.mean(0), covariance_prior_ = cov(X.T)) come from all-reduced raw moments.  Both
+// kernels return at once when the state's `done` flag is set: the host may enqueue iterations ahead and read the flag every few iterations.
 __global__ __launch_bounds__(VB_THREADS) void vbgmm_moments_kernel(const float* __restrict__ X, int N, int R, double* __restrict__ out) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   if (tid == 0) out[0] = (double)N;
@@ -334,21 +340,19 @@ __global__ __launch_bounds__(VB_THREADS) void vbgmm_moments_kernel(const float* 
       const int i = (p - R) / R, j = (p - R) - i * R;
       for (int n = lane; n < N; n += 64) a += (double)X[(size_t)n * R + i] * (double)X[(size_t)n * R + j];
     }
-    a = wave_sum(a);
+    a = wave_sum_d(a);
     if (lane == 0) out[1 + p] = a;
   }
 }
 
 // One workgroup = one SLICE of `per` local samples (the statistics are additive over samples: the slices of a rank are reduced in a fixed
-// order by vbgmm_stats_reduce_kernel exactly as the ranks are by the all-reduce) -- the accurate per-epoch fit runs on 20 096 samples,
-// which one workgroup walks in 3.8 ms per iteration and 79 workgroups in microseconds.
+// order by vbgmm_stats_reduce_kernel exactly as the ranks are by the all-reduce): 79 workgroups at the 20 096 samples of the accurate fit.
 __global__ __launch_bounds__(VB_THREADS) void vbgmm_shard_estep_kernel(const float* __restrict__ X, const int* __restrict__ labels,
-                                                                       const double* __restrict__ state, VbCfg c,
-                                                                       double* __restrict__ resp, double* __restrict__ stats,
-                                                                       const int per, const size_t stats_stride) {
+                                                                       const double* __restrict__ state, VbCfg c, double* __restrict__ resp,
+                                                                       double* __restrict__ stats, const int per, const size_t stats_stride) {
   const int K = c.K, R = c.R, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   VbState S(const_cast<double*>(state), K, R);
-  if (S.tail[3] != 0.0) return;                                  // the fit is over: later (speculatively enqueued) iterations are no-ops
+  if (S.tail[FIT_DONE] != 0.0) return;                           // the fit is over: later (speculatively enqueued) iterations are no-ops
   const int n_first = blockIdx.x * per, N = min(per, c.N - n_first);
   X += (size_t)n_first * R;
   if (labels != nullptr) labels += n_first;
@@ -356,78 +360,12 @@ __global__ __launch_bounds__(VB_THREADS) void vbgmm_shard_estep_kernel(const flo
   stats += (size_t)blockIdx.x * stats_stride;
   __shared__ double s_ck[VB_MAXK], s_mu[VB_MAXK * VB_MAXR], s_pc[VB_MAXK * VB_MAXR * VB_MAXR], s_red[VB_WAVES], s_scal[1];
   double entropy = 0.0;
-  if (c.init_from_labels) {
-    for (size_t i = tid; i < (size_t)N * K; i += VB_THREADS) resp[i] = (labels[i / K] == (int)(i % K)) ? 1.0 : 0.0;
-  } else {
-    if (tid == 0 && c.prior_type == 0) {
-      double sw = 0.0;
-      for (int k = 0; k < K; ++k) sw += S.wa[k];
-      s_scal[0] = vb_digamma(sw);
-    }
-    for (int i = tid; i < K * R; i += VB_THREADS) s_mu[i] = S.means[i];
-    for (int i = tid; i < K * R * R; i += VB_THREADS) s_pc[i] = S.pchol[i];
-    __syncthreads();
-    if (tid < K) {
-      const int k = tid;
-      double log_det = 0.0, log_lambda = R * log(2.0);
-      for (int j = 0; j < R; ++j) {
-        log_det += log(s_pc[(k * R + j) * R + j]);
-        log_lambda += vb_digamma(0.5 * (S.dof[k] - j));
-      }
-      double lw;
-      if (c.prior_type == 0) {
-        lw = vb_digamma(S.wa[k]) - s_scal[0];
-      } else {
-        lw = vb_digamma(S.wa[k]) - vb_digamma(S.wa[k] + S.wb[k]);
-        for (int j = 0; j < k; ++j) lw += vb_digamma(S.wb[j]) - vb_digamma(S.wa[j] + S.wb[j]);
-      }
-      s_ck[k] = -0.5 * R * log(2.0 * M_PI) + log_det - 0.5 * R * log(S.dof[k]) + 0.5 * (log_lambda - R / S.mprec[k]) + lw;
-    }
-    __syncthreads();
-    double ent = 0.0;
-    for (int n = tid; n < N; n += VB_THREADS) {
-      double x[VB_MAXR];
-      for (int i = 0; i < R; ++i) x[i] = (double)X[(size_t)n * R + i];
-      double* wr = resp + (size_t)n * K;
-      double mx = -INFINITY;
-      for (int k = 0; k < K; ++k) {
-        const double* P = s_pc + (size_t)k * R * R;
-        const double* mu = s_mu + k * R;
-        double q = 0.0;
-        for (int j = 0; j < R; ++j) {
-          double xy = 0.0, my = 0.0;
-          for (int i = 0; i <= j; ++i) {
-            xy += x[i] * P[i * R + j];
-            my += mu[i] * P[i * R + j];
-          }
-          const double y = xy - my;
-          q += y * y;
-        }
-        const double w = s_ck[k] - 0.5 * q;
-        wr[k] = w;
-        mx = fmax(mx, w);
-      }
-      double se = 0.0;
-      for (int k = 0; k < K; ++k) se += exp(wr[k] - mx);
-      const double lse = mx + log(se);
-      for (int k = 0; k < K; ++k) {
-        const double lr = wr[k] - lse, r = exp(lr);
-        wr[k] = r;
-        ent += r * lr;
-      }
-    }
-    ent = wave_sum(ent);
-    if (lane == 0) s_red[wave] = ent;
-    __syncthreads();
-    if (tid == 0)
-      for (int w = 0; w < VB_WAVES; ++w) entropy += s_red[w];
-  }
+  if (c.init_from_labels) vb_onehot(labels, N, K, resp, tid, VB_THREADS);
+  else entropy = vb_estep(X, N, S, c, s_mu, s_pc, s_ck, s_scal, s_red, resp, tid);
   __syncthreads();
   // local sufficient statistics (fixed order: lane-strided partial sums, then the shuffle tree)
   if (tid == 0) stats[0] = entropy;
-  double* st_nk = stats + 1;
-  double* st_x = st_nk + K;
-  double* st_xx = st_x + (size_t)K * R;
+  double *st_nk = stats + 1, *st_x = st_nk + K, *st_xx = st_x + (size_t)K * R;
   for (int p = wave; p < K * (1 + R + R * R); p += VB_WAVES) {
     double a = 0.0;
     if (p < K) {
@@ -440,7 +378,7 @@ __global__ __launch_bounds__(VB_THREADS) void vbgmm_shard_estep_kernel(const flo
       if (j < i) continue;                                        // (upper triangle; mirrored below)
       for (int n = lane; n < N; n += 64) a += resp[(size_t)n * K + k] * (double)X[(size_t)n * R + i] * (double)X[(size_t)n * R + j];
     }
-    a = wave_sum(a);
+    a = wave_sum_d(a);
     if (lane == 0) {
       if (p < K) st_nk[p] = a;
       else if (p < K + K * R) st_x[p - K] = a;
@@ -456,7 +394,7 @@ __global__ __launch_bounds__(VB_THREADS) void vbgmm_shard_estep_kernel(const flo
 __global__ __launch_bounds__(256) void vbgmm_stats_reduce_kernel(const double* __restrict__ partial, const double* __restrict__ state,
                                                                  int K, int R, int G, int n, double* __restrict__ stats) {
   VbState S(const_cast<double*>(state), K, R);
-  if (S.tail[3] != 0.0) return;
+  if (S.tail[FIT_DONE] != 0.0) return;
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
   double a = 0.0;
@@ -465,12 +403,11 @@ __global__ __launch_bounds__(256) void vbgmm_stats_reduce_kernel(const double* _
 }
 
 __global__ __launch_bounds__(256) void vbgmm_shard_mstep_kernel(const double* __restrict__ stats, const double* __restrict__ moments,
-                                                                double* __restrict__ state, VbCfg c, int it,
-                                                                float* __restrict__ w_out, float* __restrict__ m_out,
-                                                                float* __restrict__ c_out) {
+                                                                double* __restrict__ state, VbCfg c, int it, float* __restrict__ w_out,
+                                                                float* __restrict__ m_out, float* __restrict__ c_out) {
   const int K = c.K, R = c.R, tid = threadIdx.x;
   VbState S(state, K, R);
-  if (S.tail[3] != 0.0) return;
+  if (S.tail[FIT_DONE] != 0.0) return;
   __shared__ double s_nk[VB_MAXK], s_xk[VB_MAXK * VB_MAXR], s_sk[VB_MAXK * VB_MAXR * VB_MAXR], s_ck[VB_MAXK];
   __shared__ double s_prior_mean[VB_MAXR], s_prior_cov[VB_MAXR * VB_MAXR];
   __shared__ int s_flag, s_done;
@@ -482,125 +419,42 @@ __global__ __launch_bounds__(256) void vbgmm_shard_mstep_kernel(const double* __
     const int i = tid / R, j = tid - i * R;
     s_prior_cov[tid] = (moments[1 + R + tid] - Ntot * s_prior_mean[i] * s_prior_mean[j]) / (Ntot - 1.0);
   }
-  const double* st_nk = stats + 1;
-  const double* st_x = st_nk + K;
-  const double* st_xx = st_x + (size_t)K * R;
-  if (tid < K) s_nk[tid] = st_nk[tid] + 10.0 * 2.220446049250313e-16;
+  const double *st_nk = stats + 1, *st_x = st_nk + K, *st_xx = st_x + (size_t)K * R;
+  if (tid < K) s_nk[tid] = st_nk[tid] + kEps10;
   __syncthreads();
   for (int p = tid; p < K * R; p += 256) s_xk[p] = st_x[p] / s_nk[p / R];
   __syncthreads();
+  // the raw second moments, centred here
   for (int p = tid; p < K * R * R; p += 256) {
     const int k = p / (R * R), ij = p - k * R * R, i = ij / R, j = ij - i * R;
     s_sk[p] = st_xx[p] / s_nk[k] - s_xk[k * R + i] * s_xk[k * R + j] + (i == j ? c.reg_covar : 0.0);
   }
   __syncthreads();
-  if (tid < K) {
-    const int k = tid;
-    const double nk = s_nk[k];
-    if (c.prior_type == 0) {
-      S.wa[k] = c.wc_prior + nk;
-      S.wb[k] = 0.0;
-    } else {
-      double tail = 0.0;
-      for (int j = K - 1; j > k; --j) tail += s_nk[j];
-      S.wa[k] = 1.0 + nk;
-      S.wb[k] = c.wc_prior + tail;
-    }
-    const double mp = c.mean_prec_prior + nk;
-    S.mprec[k] = mp;
-    for (int r = 0; r < R; ++r) S.means[k * R + r] = (c.mean_prec_prior * s_prior_mean[r] + nk * s_xk[k * R + r]) / mp;
-    const double dof = (double)R + nk;
-    S.dof[k] = dof;
-    double* C = S.cov + (size_t)k * R * R;
-    for (int i = 0; i < R; ++i)
-      for (int j = 0; j < R; ++j) {
-        const double di = s_xk[k * R + i] - s_prior_mean[i], dj = s_xk[k * R + j] - s_prior_mean[j];
-        C[i * R + j] = (s_prior_cov[i * R + j] + nk * s_sk[(k * R + i) * R + j] + nk * c.mean_prec_prior / mp * (di * dj)) / dof;
-      }
-    double* Lm = s_sk + (size_t)k * R * R;
-    bool ok = true;
-    for (int j = 0; j < R; ++j) {
-      double d = C[j * R + j];
-      for (int p = 0; p < j; ++p) d -= Lm[j * R + p] * Lm[j * R + p];
-      if (!(d > 0.0)) { ok = false; d = 1.0; }
-      const double ljj = sqrt(d);
-      Lm[j * R + j] = ljj;
-      for (int i = j + 1; i < R; ++i) {
-        double v = C[i * R + j];
-        for (int p = 0; p < j; ++p) v -= Lm[i * R + p] * Lm[j * R + p];
-        Lm[i * R + j] = v / ljj;
-      }
-    }
-    if (!ok) atomicExch(&s_flag, 1);
-    double* Pk = S.pchol + (size_t)k * R * R;
-    for (int col = 0; col < R; ++col)
-      for (int i = 0; i < R; ++i) {
-        double v = (i == col) ? 1.0 : 0.0;
-        for (int p = col; p < i; ++p) v -= Lm[i * R + p] * Pk[col * R + p];
-        Pk[col * R + i] = (i < col) ? 0.0 : v / Lm[i * R + i];
-      }
-  }
+  if (tid < K) vb_update_component(tid, S, c, s_nk, s_xk, s_sk, s_prior_mean, s_prior_cov, &s_flag);
   __syncthreads();
   if (tid == 0) {
     if (s_flag) {                                                  // ill-defined empirical covariance (sklearn raises)
-      S.tail[2] = -1.0;
-      S.tail[3] = 1.0;
-      s_done = 2;
+      S.tail[FIT_CONVERGED] = -1.0; S.tail[FIT_DONE] = 1.0; s_done = 2;
     } else if (it == 0) {
-      S.tail[0] = -INFINITY;                                       // _initialize: no lower bound yet
-      S.tail[1] = 0.0;
-      if (c.max_iter == 0) { S.tail[3] = 1.0; s_done = 1; }
+      S.tail[FIT_LB] = -INFINITY; S.tail[FIT_NITER] = 0.0;         // _initialize: no lower bound yet
+      if (c.max_iter == 0) { S.tail[FIT_DONE] = 1.0; s_done = 1; }
     } else {
-      double log_wishart = 0.0, sum_log_mp = 0.0, log_norm_weight;
-      for (int k = 0; k < K; ++k) {
-        const double* Pk = S.pchol + (size_t)k * R * R;
-        double ld = 0.0, lg = 0.0;
-        for (int j = 0; j < R; ++j) {
-          ld += log(Pk[j * R + j]);
-          lg += lgamma(0.5 * (S.dof[k] - j));
-        }
-        ld -= 0.5 * R * log(S.dof[k]);
-        log_wishart += -(S.dof[k] * ld + S.dof[k] * R * 0.5 * log(2.0) + lg);
-        sum_log_mp += log(S.mprec[k]);
-      }
-      if (c.prior_type == 0) {
-        double sw = 0.0, sl = 0.0;
-        for (int k = 0; k < K; ++k) { sw += S.wa[k]; sl += lgamma(S.wa[k]); }
-        log_norm_weight = lgamma(sw) - sl;
-      } else {
-        double sb = 0.0;
-        for (int k = 0; k < K; ++k) sb += lgamma(S.wa[k]) + lgamma(S.wb[k]) - lgamma(S.wa[k] + S.wb[k]);
-        log_norm_weight = -sb;
-      }
-      const double lb = -stats[0] - log_wishart - log_norm_weight - 0.5 * R * sum_log_mp;
-      const bool conv = fabs(lb - S.tail[0]) < c.tol;
-      S.tail[0] = lb;
-      S.tail[1] = (double)it;
-      if (conv) { S.tail[2] = 1.0; S.tail[3] = 1.0; s_done = 1; }
-      else if (it >= c.max_iter) { S.tail[3] = 1.0; s_done = 1; }
+      const double lb = vb_lower_bound(S, c, stats[0]);
+      const bool conv = fabs(lb - S.tail[FIT_LB]) < c.tol;
+      S.tail[FIT_LB] = lb; S.tail[FIT_NITER] = (double)it;
+      if (conv) { S.tail[FIT_CONVERGED] = 1.0; S.tail[FIT_DONE] = 1.0; s_done = 1; }
+      else if (it >= c.max_iter) { S.tail[FIT_DONE] = 1.0; s_done = 1; }
     }
   }
   __syncthreads();
   if (s_done != 1) return;
-  // _set_parameters: the float32 copies for the mixture feed
-  if (tid == 0) {
-    double tot = 0.0;
-    if (c.prior_type == 0) {
-      for (int k = 0; k < K; ++k) tot += S.wa[k];
-      for (int k = 0; k < K; ++k) w_out[k] = (float)(S.wa[k] / tot);
-    } else {
-      double prod = 1.0;
-      for (int k = 0; k < K; ++k) {
-        const double sm = S.wa[k] + S.wb[k];
-        s_ck[k] = S.wa[k] / sm * prod;
-        prod *= S.wb[k] / sm;
-        tot += s_ck[k];
-      }
-      for (int k = 0; k < K; ++k) w_out[k] = (float)(s_ck[k] / tot);
-    }
-  }
-  for (int i = tid; i < K * R; i += 256) m_out[i] = (float)S.means[i];
-  for (int i = tid; i < K * R * R; i += 256) c_out[i] = (float)S.cov[i];
+  vb_write_feed(S, c, s_ck, w_out, m_out, c_out, tid, 256);
+}
+
+inline bool vb_bad_shape(int K, int R, int prior_type) { return K < 1 || K > VB_MAXK || R < 1 || R > VB_MAXR || (prior_type != 0 && prior_type != 1); }
+inline VbCfg vb_cfg(int N, int K, int R, int prior_type, const int* labels, int max_iter = 0, double wc_prior = 0.0, double mean_prec_prior = 0.0,
+                    double reg_covar = 0.0, double tol = 0.0) {
+  return VbCfg{N, K, R, prior_type, max_iter, labels != nullptr ? 1 : 0, wc_prior, mean_prec_prior, reg_covar, tol};
 }
 
 }  // namespace
@@ -608,16 +462,14 @@ __global__ __launch_bounds__(256) void vbgmm_shard_mstep_kernel(const double* __
 extern "C" {
 
 size_t ladder_vbgmm_state_doubles(int K, int R) { return (size_t)K * (4 + R + 2 * R * R) + 4; }
-
 size_t ladder_vbgmm_workspace_bytes(int N, int K) { return (size_t)N * K * sizeof(double); }
 
 int ladder_vbgmm_fit(const float* X, int N, int K, int R, const int* labels, double* state, int prior_type, double wc_prior,
                      double mean_prec_prior, double reg_covar, double tol, int max_iter, float* weights, float* means,
                      float* covs, void* ws, size_t ws_bytes, ladder_stream_t stream) {
-  if (N < 2 || K < 1 || K > VB_MAXK || R < 1 || R > VB_MAXR || N < K || max_iter < 0 || (prior_type != 0 && prior_type != 1))
-    return LADDER_E_SHAPE;
+  if (N < 2 || N < K || max_iter < 0 || vb_bad_shape(K, R, prior_type)) return LADDER_E_SHAPE;
   if (ws == nullptr || ws_bytes < ladder_vbgmm_workspace_bytes(N, K)) return LADDER_E_WORKSPACE;
-  VbCfg c{N, K, R, prior_type, max_iter, labels != nullptr ? 1 : 0, wc_prior, mean_prec_prior, reg_covar, tol};
+  const VbCfg c = vb_cfg(N, K, R, prior_type, labels, max_iter, wc_prior, mean_prec_prior, reg_covar, tol);
   hipLaunchKernelGGL(vbgmm_fit_kernel, dim3(1), dim3(VB_THREADS), 0, stream, X, labels, state, c, (double*)ws, weights, means, covs);
   LADDER_CHECK_LAUNCH();
   return LADDER_OK;
@@ -646,18 +498,16 @@ size_t ladder_vbgmm_shard_workspace_bytes(int N, int K, int R) {
 
 int ladder_vbgmm_shard_estep(const float* X, int N, int K, int R, const int* labels, const double* state, int prior_type, double* stats,
                              void* ws, size_t ws_bytes, ladder_stream_t stream) {
-  if (N < 1 || K < 1 || K > VB_MAXK || R < 1 || R > VB_MAXR || (prior_type != 0 && prior_type != 1)) return LADDER_E_SHAPE;
+  if (N < 1 || vb_bad_shape(K, R, prior_type)) return LADDER_E_SHAPE;
   if (ws == nullptr || ws_bytes < ladder_vbgmm_shard_workspace_bytes(N, K, R)) return LADDER_E_WORKSPACE;
-  VbCfg c{N, K, R, prior_type, 0, labels != nullptr ? 1 : 0, 0.0, 0.0, 0.0, 0.0};
+  const VbCfg c = vb_cfg(N, K, R, prior_type, labels);
   const int G = vb_slices(N), n = (int)ladder_vbgmm_shard_stats_doubles(K, R);
   double* resp = (double*)ws;
   double* partial = resp + (size_t)N * K;
-  if (G == 1) {
-    hipLaunchKernelGGL(vbgmm_shard_estep_kernel, dim3(1), dim3(VB_THREADS), 0, stream, X, labels, state, c, resp, stats, VB_SLICE, (size_t)0);
-  } else {
-    hipLaunchKernelGGL(vbgmm_shard_estep_kernel, dim3(G), dim3(VB_THREADS), 0, stream, X, labels, state, c, resp, partial, VB_SLICE, (size_t)n);
-    hipLaunchKernelGGL(vbgmm_stats_reduce_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, (const double*)partial, state, K, R, G, n, stats);
-  }
+  // one slice writes `stats` itself; several write per-slice partials, reduced in slice order
+  hipLaunchKernelGGL(vbgmm_shard_estep_kernel, dim3(G), dim3(VB_THREADS), 0, stream, X, labels, state, c, resp, G == 1 ? stats : partial, VB_SLICE,
+                     (size_t)(G == 1 ? 0 : n));
+  if (G > 1) hipLaunchKernelGGL(vbgmm_stats_reduce_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, (const double*)partial, state, K, R, G, n, stats);
   LADDER_CHECK_LAUNCH();
   return LADDER_OK;
 }
@@ -665,8 +515,8 @@ int ladder_vbgmm_shard_estep(const float* X, int N, int K, int R, const int* lab
 int ladder_vbgmm_shard_mstep(const double* stats, const double* moments, int K, int R, double* state, int prior_type, double wc_prior,
                              double mean_prec_prior, double reg_covar, double tol, int max_iter, int it, float* weights, float* means,
                              float* covs, ladder_stream_t stream) {
-  if (K < 1 || K > VB_MAXK || R < 1 || R > VB_MAXR || max_iter < 0 || it < 0 || (prior_type != 0 && prior_type != 1)) return LADDER_E_SHAPE;
-  VbCfg c{0, K, R, prior_type, max_iter, 0, wc_prior, mean_prec_prior, reg_covar, tol};
+  if (max_iter < 0 || it < 0 || vb_bad_shape(K, R, prior_type)) return LADDER_E_SHAPE;
+  const VbCfg c = vb_cfg(0, K, R, prior_type, nullptr, max_iter, wc_prior, mean_prec_prior, reg_covar, tol);
   hipLaunchKernelGGL(vbgmm_shard_mstep_kernel, dim3(1), dim3(256), 0, stream, stats, moments, state, c, it, weights, means, covs);
   LADDER_CHECK_LAUNCH();
   return LADDER_OK;

@@ -65,7 +65,7 @@ def kmeans_rows(Xd, reps):
     from sklearn.cluster import KMeans
     from ladder_latent_data_distribution_modelling_amd.codes.kmeans import DeviceKMeans
 
-    def host():                                                                      # what mixture_fit.initial_labels does around the labeller
+    def host():                                                                      # what mixture_fit.initial_labels_for does around the labeller
         lab = KMeans(n_clusters=K, n_init=1, random_state=np.random.RandomState(SEED)).fit(Xd.cpu().numpy().astype(np.float64)).labels_
         return torch.as_tensor(lab.astype(np.int32)).to(Xd.device)
 

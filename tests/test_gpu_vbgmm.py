@@ -272,3 +272,54 @@ def test_persistent_kernel_still_matches_sklearn(R, K, ptype, max_iter, monkeypa
     from ladder_latent_data_distribution_modelling_amd.codes import vbgmm
     monkeypatch.setattr(vbgmm, "SLICED_FIT_MIN_SAMPLES", 1 << 30)
     test_vbgmm_matches_sklearn(R, K, ptype, max_iter)
+
+
+# the two paths of fit(): threshold 0 -> the sliced E-step / M-step launches, 1 << 30 -> the persistent one-workgroup kernel
+PATHS = [pytest.param(0, id="sliced"), pytest.param(1 << 30, id="persistent")]
+
+
+@pytest.mark.parametrize("threshold", PATHS)
+@pytest.mark.parametrize("ptype", ["dirichlet_distribution", "dirichlet_process"])
+@pytest.mark.parametrize("N,R,K", [(70, 1, 1), (70, 1, 2), (257, 1, 3), (257, 2, 1)])
+def test_vbgmm_smallest_shapes_match_sklearn(N, R, K, ptype, threshold, monkeypatch):
+    """The shapes at which the device functions both paths share (csrc/vbgmm.hip: vb_*) would go wrong with a wrong stride or loop bound:
+    K = 1 (empty stick-breaking prefix and suffix), R = 1 (1 x 1 factors), N = 70 (no multiple of the wavefront), N = 257 (one 256-sample
+    slice plus a one-sample slice).  Cold fit, then a warm-started refit, five iterations each by construction (tol = 0), against sklearn at
+    the tolerances test_vbgmm_matches_sklearn (persistent) and test_vbgmm_sharded_statistics_fit_matches_sklearn_one_rank (sliced) hold."""
+    import warnings
+    from sklearn.mixture import BayesianGaussianMixture
+    from ladder_latent_data_distribution_modelling_amd.codes import vbgmm
+    monkeypatch.setattr(vbgmm, "SLICED_FIT_MIN_SAMPLES", threshold)
+    sliced = threshold == 0
+    rng = np.random.default_rng(N * 100 + R * 10 + K)
+    X1, X2 = _samples(rng, N, R, centres=3), _samples(rng, N, R, centres=3)
+    kw = dict(n_components=K, covariance_type="full", max_iter=5, tol=0.0, n_init=1, weight_concentration_prior_type=ptype,
+              weight_concentration_prior=0.1, warm_start=True, random_state=7)
+    ref, dev = BayesianGaussianMixture(**kw), vbgmm.DeviceBayesianGaussianMixture(**kw)
+    for X in (X1, X2):
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            ref.fit(X.astype(np.float64))
+            dev.fit(torch.as_tensor(X).cuda())
+        assert dev.n_iter_ == ref.n_iter_ == 5 and dev.converged_ == ref.converged_
+        assert abs(dev.lower_bound_ - ref.lower_bound_) <= (1e-8 if sliced else 1e-9) * abs(ref.lower_bound_)
+        np.testing.assert_allclose(dev.weights_, ref.weights_, rtol=1e-7 if sliced else 1e-8, atol=1e-11 if sliced else 1e-12)
+        np.testing.assert_allclose(dev.means_, ref.means_, rtol=1e-7 if sliced else 1e-8, atol=1e-9 if sliced else 1e-10)
+        np.testing.assert_allclose(dev.covariances_, ref.covariances_, rtol=1e-6 if sliced else 1e-7, atol=1e-9 if sliced else 1e-10)
+        np.testing.assert_array_equal(dev.weights_dev.cpu().numpy(), dev.weights_.astype(np.float32))
+        if not sliced:
+            np.testing.assert_array_equal(dev.covariances_dev.cpu().numpy(), dev.covariances_.astype(np.float32))
+
+
+@pytest.mark.parametrize("threshold", PATHS)
+@pytest.mark.parametrize("ptype", ["dirichlet_distribution", "dirichlet_process"])
+def test_vbgmm_ill_defined_covariance_raises(ptype, threshold, monkeypatch):
+    """64 identical samples without reg_covar: the empirical covariance has no positive pivot, the M-step of either path leaves status -1 in
+    the state tail and fit() raises what sklearn raises.  An error return, not a device fault."""
+    from ladder_latent_data_distribution_modelling_amd.codes import vbgmm
+    monkeypatch.setattr(vbgmm, "SLICED_FIT_MIN_SAMPLES", threshold)
+    X = np.full((64, 2), 0.5, dtype=np.float32)
+    gm = vbgmm.DeviceBayesianGaussianMixture(n_components=2, covariance_type="full", reg_covar=0.0, weight_concentration_prior_type=ptype,
+                                             random_state=7)
+    with pytest.raises(ValueError, match="ill-defined empirical covariance"):
+        gm.fit(torch.as_tensor(X).cuda())
