@@ -3,113 +3,16 @@
 // resize, depth-to-space, symmetric pad, activation backward.  All tensors NHWC fp32: the channel
 // axis is contiguous, so a wavefront always touches >=256 contiguous bytes per row.
 #include "split16.h"
+#include "norm_util.h"
 
 namespace {
 
 // ----------------------------------------------------------------------------- column statistics
-// x viewed as [rows, C].  256 threads = 64 channels x 4 row-lanes; grid = (ceil(C/64), row-blocks).
-// MODE 1: (sum x, sum x^2)    MODE 2: BN backward (sum dp, sum dp*xhat)
-template <int MODE>
-__global__ __launch_bounds__(256) void colstats_stage1(const float* __restrict__ a, const float* __restrict__ b,
-                                                       const float* __restrict__ mean_rstd, const float* __restrict__ gamma,
-                                                       const float* __restrict__ beta, float* __restrict__ ws, size_t rows,
-                                                       int C, size_t rows_per_blk, int act) {
-  const int cl = threadIdx.x & 63, rl = threadIdx.x >> 6;
-  const int c = blockIdx.x * 64 + cl;
-  const size_t r0 = (size_t)blockIdx.y * rows_per_blk, r1 = min(rows, r0 + rows_per_blk);
-  float s0 = 0.f, s1 = 0.f;
-  if (c < C) {
-    if (MODE == 1) {
-      for (size_t r = r0 + rl; r < r1; r += 4) {
-        const float v = a[r * C + c];
-        s0 += v;
-        s1 += v * v;
-      }
-    } else {
-      const float mu = mean_rstd[c], rs = mean_rstd[C + c], g = gamma[c], be = beta[c];
-      for (size_t r = r0 + rl; r < r1; r += 4) {
-        const float xh = (b[r * C + c] - mu) * rs;
-        const float dp = a[r * C + c] * ladder_act_grad_from_out(g * xh + be, act);
-        s0 += dp;
-        s1 += dp * xh;
-      }
-    }
-  }
-  __shared__ float sm[2][4][64];
-  sm[0][rl][cl] = s0;
-  sm[1][rl][cl] = s1;
-  __syncthreads();
-  if (rl == 0 && c < C) {
-    ws[((size_t)blockIdx.y * 2 + 0) * C + c] = (sm[0][0][cl] + sm[0][1][cl]) + (sm[0][2][cl] + sm[0][3][cl]);
-    ws[((size_t)blockIdx.y * 2 + 1) * C + c] = (sm[1][0][cl] + sm[1][1][cl]) + (sm[1][2][cl] + sm[1][3][cl]);
-  }
-}
-template <int MODE>
-__global__ __launch_bounds__(256) void colstats_stage1_v4(const float* __restrict__ a, const float* __restrict__ b,
-                                                          const float* __restrict__ mean_rstd, const float* __restrict__ gamma,
-                                                          const float* __restrict__ beta, float* __restrict__ ws, size_t rows,
-                                                          int C, size_t rows_per_blk, int act) {
-  const int cq = threadIdx.x & 15, rl = threadIdx.x >> 4;       // 16 float4 channel groups x 16 row lanes
-  const int c = blockIdx.x * 64 + cq * 4;
-  const size_t r0 = (size_t)blockIdx.y * rows_per_blk, r1 = min(rows, r0 + rows_per_blk);
-  float4 s0 = make_float4(0.f, 0.f, 0.f, 0.f), s1 = s0;
-  if (c < C) {
-    if (MODE == 1) {
-      size_t r = r0 + rl;
-      for (; r + 7 * 16 < r1; r += 8 * 16) {        // eight loads in flight, accumulated in row order (bit-identical to the plain loop)
-        float4 v[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) v[u] = *reinterpret_cast<const float4*>(a + (r + u * 16) * C + c);
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-          s0.x += v[u].x; s0.y += v[u].y; s0.z += v[u].z; s0.w += v[u].w;
-          s1.x += v[u].x * v[u].x; s1.y += v[u].y * v[u].y; s1.z += v[u].z * v[u].z; s1.w += v[u].w * v[u].w;
-        }
-      }
-      for (; r < r1; r += 16) {
-        const float4 v = *reinterpret_cast<const float4*>(a + r * C + c);
-        s0.x += v.x; s0.y += v.y; s0.z += v.z; s0.w += v.w;
-        s1.x += v.x * v.x; s1.y += v.y * v.y; s1.z += v.z * v.z; s1.w += v.w * v.w;
-      }
-    } else {
-      const float4 mu = *reinterpret_cast<const float4*>(mean_rstd + c), rs = *reinterpret_cast<const float4*>(mean_rstd + C + c);
-      const float4 g = *reinterpret_cast<const float4*>(gamma + c), be = *reinterpret_cast<const float4*>(beta + c);
-      auto row = [&](const float4 xv, const float4 dv) {
-        float xh, dp;
-        xh = (xv.x - mu.x) * rs.x; dp = dv.x * ladder_act_grad_from_out(g.x * xh + be.x, act); s0.x += dp; s1.x += dp * xh;
-        xh = (xv.y - mu.y) * rs.y; dp = dv.y * ladder_act_grad_from_out(g.y * xh + be.y, act); s0.y += dp; s1.y += dp * xh;
-        xh = (xv.z - mu.z) * rs.z; dp = dv.z * ladder_act_grad_from_out(g.z * xh + be.z, act); s0.z += dp; s1.z += dp * xh;
-        xh = (xv.w - mu.w) * rs.w; dp = dv.w * ladder_act_grad_from_out(g.w * xh + be.w, act); s0.w += dp; s1.w += dp * xh;
-      };
-      size_t r = r0 + rl;
-      for (; r + 7 * 16 < r1; r += 8 * 16) {        // the loads of eight rows in flight, accumulated in row order (bit-identical to the plain loop)
-        float4 xv[8], dv[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-          xv[u] = *reinterpret_cast<const float4*>(b + (r + u * 16) * C + c);
-          dv[u] = *reinterpret_cast<const float4*>(a + (r + u * 16) * C + c);
-        }
-#pragma unroll
-        for (int u = 0; u < 8; ++u) row(xv[u], dv[u]);
-      }
-      for (; r < r1; r += 16) row(*reinterpret_cast<const float4*>(b + r * C + c), *reinterpret_cast<const float4*>(a + r * C + c));
-    }
-  }
-  __shared__ float4 sm[2][16][16];
-  sm[0][rl][cq] = s0;
-  sm[1][rl][cq] = s1;
-  __syncthreads();
-  if (rl < 2 && c < C) {        // rl 0 -> sums, rl 1 -> second statistic; fixed-order tree over the 16 row lanes
-    float4 t = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-    for (int k = 0; k < 16; ++k) {
-      const float4 v = sm[rl][k][cq];
-      t.x += v.x; t.y += v.y; t.z += v.z; t.w += v.w;
-    }
-    *reinterpret_cast<float4*>(ws + ((size_t)blockIdx.y * 2 + rl) * C + c) = t;
-  }
-}
-
+// x viewed as [rows, C]; grid = (ceil(C/64), row-blocks), 256 threads over 64 channels: V = 4 -> 16 float4 channel groups x 16 row lanes,
+// V = 1 -> 64 channels x 4 row lanes.  What a row contributes is the ROW functor's business; the loop keeps the loads of eight rows in
+// flight and accumulates them in row order (bit-identical to the plain loop), the row lanes are combined in a fixed order, and the two
+// sums go to ws [nblk][2][C].
+//
 // ---- batch-norm FORWARD statistics in fp64 (round 5) ------------------------------------------------------------------------------------
 // TF's fused batch norm is two-pass (reference codes/models.py:398-460: tf.layers.batch_normalization): the variance is formed about the
 // mean.  The single-pass form var = E[x^2] - mean^2 from fp32 sums loses eps_fp32 x (1 + mean^2 / var) of relative accuracy -- invisible at
@@ -119,201 +22,147 @@ __global__ __launch_bounds__(256) void colstats_stage1_v4(const float* __restric
 // operations per element against 78 TFLOP/s of fp64 vector rate): their duration does not change.
 // RECORD layout (the `sums` argument of every ladder_bn_* entry point): 2C doubles = sum x | sum x^2, i.e. the first 4C floats of the buffer;
 // the "minmax" form appends min x | max x as 2C floats (6C floats in all).
-__global__ __launch_bounds__(256) void colstats64_stage1(const float* __restrict__ a, double* __restrict__ ws, size_t rows, int C,
-                                                         size_t rows_per_blk) {
-  const int cl = threadIdx.x & 63, rl = threadIdx.x >> 6;
-  const int c = blockIdx.x * 64 + cl;
-  const size_t r0 = (size_t)blockIdx.y * rows_per_blk, r1 = min(rows, r0 + rows_per_blk);
-  double s0 = 0.0, s1 = 0.0;
-  if (c < C)
-    for (size_t r = r0 + rl; r < r1; r += 4) {
-      const double v = (double)a[r * C + c];
-      s0 += v;
-      s1 = fma(v, v, s1);
-    }
-  __shared__ double sm[2][4][64];
-  sm[0][rl][cl] = s0;
-  sm[1][rl][cl] = s1;
-  __syncthreads();
-  if (rl == 0 && c < C) {
-    ws[((size_t)blockIdx.y * 2 + 0) * C + c] = (sm[0][0][cl] + sm[0][1][cl]) + (sm[0][2][cl] + sm[0][3][cl]);
-    ws[((size_t)blockIdx.y * 2 + 1) * C + c] = (sm[1][0][cl] + sm[1][1][cl]) + (sm[1][2][cl] + sm[1][3][cl]);
-  }
-}
-
-// 16 float4 channel groups x 16 row lanes; MINMAX: also the per-channel extremes.  Partials: ws [nblk][2][C] doubles, then (MINMAX) [nblk][2][C]
-// floats behind all of them.
+// MINMAX: also the per-channel extremes, partials wsmm [nblk][2][C] floats (V = 4 only).
 template <bool MINMAX>
-__global__ __launch_bounds__(256) void colstats64_stage1_v4(const float* __restrict__ a, double* __restrict__ ws, float* __restrict__ wsmm,
-                                                            size_t rows, int C, size_t rows_per_blk) {
-  const int cq = threadIdx.x & 15, rl = threadIdx.x >> 4;
-  const int c = blockIdx.x * 64 + cq * 4;
-  const size_t r0 = (size_t)blockIdx.y * rows_per_blk, r1 = min(rows, r0 + rows_per_blk);
-  double s0[4] = {0.0, 0.0, 0.0, 0.0}, s1[4] = {0.0, 0.0, 0.0, 0.0};
-  float4 mn = make_float4(INFINITY, INFINITY, INFINITY, INFINITY), mx = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
-  if (c < C) {
-    auto row = [&](const float4 v) {
-      const double d[4] = {(double)v.x, (double)v.y, (double)v.z, (double)v.w};
+struct MomentsRow {
+  using Sum = double;
+  static constexpr bool kMinMax = MINMAX;
+  const float* x;
+  double* ws;
+  float* wsmm;
+  template <int V> struct Coef {};
+  template <int V> using In = Lanes<float, V>;
+  template <int V> struct Acc {
+    Lanes<double, V> s0 = lanes_fill<double, V>(0.0), s1 = lanes_fill<double, V>(0.0);
+    Lanes<float, V> mn = lanes_fill<float, V>(INFINITY), mx = lanes_fill<float, V>(-INFINITY);
+  };
+  template <int V> __device__ __forceinline__ Coef<V> coef(int, int) const { return {}; }
+  template <int V> __device__ __forceinline__ In<V> load(size_t i) const { return lanes_load<V>(x + i); }
+  template <int V> __device__ __forceinline__ void add(Acc<V>& a, const In<V>& v, const Coef<V>&) const {
 #pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        s0[j] += d[j];
-        s1[j] = fma(d[j], d[j], s1[j]);
-      }
+    for (int j = 0; j < V; ++j) {
+      const double d = (double)v.v[j];
+      a.s0.v[j] += d;
+      a.s1.v[j] = fma(d, d, a.s1.v[j]);
       if (MINMAX) {
-        mn.x = fminf(mn.x, v.x); mn.y = fminf(mn.y, v.y); mn.z = fminf(mn.z, v.z); mn.w = fminf(mn.w, v.w);
-        mx.x = fmaxf(mx.x, v.x); mx.y = fmaxf(mx.y, v.y); mx.z = fmaxf(mx.z, v.z); mx.w = fmaxf(mx.w, v.w);
+        a.mn.v[j] = fminf(a.mn.v[j], v.v[j]);
+        a.mx.v[j] = fmaxf(a.mx.v[j], v.v[j]);
       }
-    };
+    }
+  }
+};
+// batch-norm BACKWARD statistics in fp32: sum dp | sum dp * xhat
+struct BnBwdRow {
+  using Sum = float;
+  static constexpr bool kMinMax = false;
+  const float *dy, *x, *mean_rstd, *gamma, *beta;
+  float* ws;
+  int act;
+  template <int V> using Coef = NormCoef<V>;
+  template <int V> struct In {
+    Lanes<float, V> x, dy;
+  };
+  template <int V> struct Acc {
+    Lanes<float, V> s0 = lanes_fill<float, V>(0.f), s1 = lanes_fill<float, V>(0.f);
+  };
+  template <int V> __device__ __forceinline__ Coef<V> coef(int C, int c) const { return bn_coef<V>(mean_rstd, gamma, beta, C, c); }
+  template <int V> __device__ __forceinline__ In<V> load(size_t i) const { return {lanes_load<V>(x + i), lanes_load<V>(dy + i)}; }
+  template <int V> __device__ __forceinline__ void add(Acc<V>& a, const In<V>& v, const Coef<V>& k) const {
+    norm_bwd_accumulate(v.x, v.dy, k, act, a.s0, a.s1);
+  }
+};
+
+template <typename Row, int V>
+__global__ __launch_bounds__(256) void colstats_stage1(const Row row, size_t rows, int C, size_t rows_per_blk) {
+  constexpr int RL = V == 4 ? 16 : 4, CG = 256 / RL;
+  using S = typename Row::Sum;
+  const int cg = threadIdx.x % CG, rl = threadIdx.x / CG;
+  const int c = blockIdx.x * 64 + cg * V;
+  const size_t r0 = (size_t)blockIdx.y * rows_per_blk, r1 = min(rows, r0 + rows_per_blk);
+  typename Row::template Acc<V> acc;
+  if (c < C) {
+    const typename Row::template Coef<V> k = row.template coef<V>(C, c);
     size_t r = r0 + rl;
-    for (; r + 7 * 16 < r1; r += 8 * 16) {          // eight loads in flight, accumulated in row order
-      float4 v[8];
+    for (; r + 7 * RL < r1; r += 8 * RL) {
+      typename Row::template In<V> in[8];
 #pragma unroll
-      for (int u = 0; u < 8; ++u) v[u] = *reinterpret_cast<const float4*>(a + (r + u * 16) * C + c);
+      for (int u = 0; u < 8; ++u) in[u] = row.template load<V>((r + u * RL) * C + c);
 #pragma unroll
-      for (int u = 0; u < 8; ++u) row(v[u]);
+      for (int u = 0; u < 8; ++u) row.template add<V>(acc, in[u], k);
     }
-    for (; r < r1; r += 16) row(*reinterpret_cast<const float4*>(a + r * C + c));
+    for (; r < r1; r += RL) row.template add<V>(acc, row.template load<V>(r * C + c), k);
   }
-  __shared__ double sm[2][16][16][4];
-  __shared__ float4 smm[2][16][16];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    sm[0][rl][cq][j] = s0[j];
-    sm[1][rl][cq][j] = s1[j];
-  }
-  if (MINMAX) {
-    smm[0][rl][cq] = mn;
-    smm[1][rl][cq] = mx;
-  }
-  __syncthreads();
-  if (rl < 2 && c < C) {          // rl = which sum; fixed-order combination of the 16 row lanes
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      double t = sm[rl][0][cq][j];
-#pragma unroll
-      for (int k = 1; k < 16; ++k) t += sm[rl][k][cq][j];
-      ws[((size_t)blockIdx.y * 2 + rl) * C + c + j] = t;
+  if constexpr (V == 4) {
+    __shared__ Lanes<S, 4> sm[2][16][16];
+    sm[0][rl][cg] = acc.s0;
+    sm[1][rl][cg] = acc.s1;
+    __syncthreads();
+    if (rl < 2 && c < C) lanes_store(row.ws + ((size_t)blockIdx.y * 2 + rl) * C + c, rowlane16_reduce<LaneAdd>(sm[rl], cg));      // rl = which sum
+    if constexpr (Row::kMinMax) {
+      __shared__ Lanes<float, 4> smm[2][16][16];
+      smm[0][rl][cg] = acc.mn;
+      smm[1][rl][cg] = acc.mx;
+      __syncthreads();
+      if (rl < 2 && c < C)
+        lanes_store(row.wsmm + ((size_t)blockIdx.y * 2 + rl) * C + c, rl == 0 ? rowlane16_reduce<LaneMin>(smm[0], cg) : rowlane16_reduce<LaneMax>(smm[1], cg));
     }
-  } else if (MINMAX && rl < 4 && c < C) {
-    const int w = rl - 2;
-    float4 t = smm[w][0][cq];
-#pragma unroll
-    for (int k = 1; k < 16; ++k) {
-      const float4 v = smm[w][k][cq];
-      if (w == 0) { t.x = fminf(t.x, v.x); t.y = fminf(t.y, v.y); t.z = fminf(t.z, v.z); t.w = fminf(t.w, v.w); }
-      else { t.x = fmaxf(t.x, v.x); t.y = fmaxf(t.y, v.y); t.z = fmaxf(t.z, v.z); t.w = fmaxf(t.w, v.w); }
+  } else {
+    __shared__ S sm[4][64];
+    const S t0 = block_rowlane_sum(acc.s0.v[0], sm, rl, cg), t1 = block_rowlane_sum(acc.s1.v[0], sm, rl, cg);
+    if (rl == 0 && c < C) {
+      row.ws[((size_t)blockIdx.y * 2 + 0) * C + c] = t0;
+      row.ws[((size_t)blockIdx.y * 2 + 1) * C + c] = t1;
     }
-    *reinterpret_cast<float4*>(wsmm + ((size_t)blockIdx.y * 2 + w) * C + c) = t;
   }
 }
 
-// second stage over fp64 partials [nblk][2][C] (+ float extremes [nblk][2][C]): the record (2C doubles, + 2C floats); fixed order
-__global__ __launch_bounds__(1024) void colstats64_stage2(const double* __restrict__ ws, const float* __restrict__ wsmm, float* __restrict__ rec,
-                                                          int nblk, int C) {
-  const int cl = threadIdx.x & 63, rl = threadIdx.x >> 6;       // rl 0 .. 15
-  const int i = blockIdx.x * 64 + cl;                             // over 2C sums, then (wsmm != NULL) 2C extremes
-  const int total = wsmm != nullptr ? 4 * C : 2 * C;
-  const bool is_sum = i < 2 * C;
-  const int which = is_sum ? i / C : (i - 2 * C) / C, c = is_sum ? i - which * C : i - 2 * C - which * C;
-  double s = is_sum ? 0.0 : (which == 0 ? (double)INFINITY : -(double)INFINITY);
-  if (i < total) {
-    for (int b = rl; b < nblk; b += 16) {
-      if (is_sum) s += ws[((size_t)b * 2 + which) * C + c];
-      else {
-        const double v = (double)wsmm[((size_t)b * 2 + which) * C + c];
-        s = which == 0 ? fmin(s, v) : fmax(s, v);
-      }
-    }
-  }
-  __shared__ double sm[16][64];
-  sm[rl][cl] = s;
-  __syncthreads();
-  if (rl == 0 && i < total) {
-    double t = sm[0][cl];
+// Second stage: one column per (which, channel) -- which 0, 1: the two sums, (MINMAX) 2, 3: min, max -- of partials [nblk][ksum][C] (sums,
+// type In) and [nblk][kmm][C] floats (extremes, rows mmoff and mmoff + 1).  CL columns x RL row lanes per workgroup; a lane strides over the
+// partials with NACC independent fp64 accumulators, combined pairwise, then the lanes in order: deterministic, ~nblk / RL dependent operations
+// instead of nblk.  Sums in fp64, extremes exactly.  Out: the sums as the fp64 record (double) or as floats; the extremes as 2C floats
+// behind 2C doubles.  The shapes in use (measured in round 4):
+//   64 x 16, one accumulator: the <= 512 partials of colstats_stage1 (4 row lanes -> 16: 11 -> 6 us, 16 calls per iteration);
+//   16 x 16, one accumulator: the per-tile column sums a convolution epilogue emits (thousands of blocks);
+//   16 x 64, four accumulators: the [nblk][4][C] partials (sum, sum of squares, min, max per tile) of a convolution epilogue -- with 16
+//     row lanes and one dependent fp64 chain per lane the 4 096 partial rows of the image-side conv took 47 us, a third of the conv itself.
+template <int CL, int RL, int NACC, bool MINMAX, typename In, typename Out>
+__global__ __launch_bounds__(CL * RL) void colstats_stage2(const In* __restrict__ wsum, int ksum, const float* __restrict__ wmm, int kmm,
+                                                             int mmoff, float* __restrict__ rec, int nblk, int C) {
+  const int cl = threadIdx.x % CL, rl = threadIdx.x / CL;
+  const int i = blockIdx.x * CL + cl;                               // over 2C sums, then (MINMAX) 2C extremes
+  const bool live = i < (MINMAX ? 4 : 2) * C;
+  const int which = live ? i / C : 0, c = live ? i - which * C : 0;
+  const bool is_sum = !MINMAX || which < 2;
+  auto op = [&](double a, double b) { return is_sum ? a + b : (which == 2 ? fmin(a, b) : fmax(a, b)); };
+  auto at = [&](int b) {
+    return is_sum ? (double)wsum[((size_t)b * ksum + which) * C + c] : (double)wmm[((size_t)b * kmm + mmoff + which - 2) * C + c];
+  };
+  double s[NACC];
 #pragma unroll
-    for (int k = 1; k < 16; ++k) t = is_sum ? t + sm[k][cl] : (which == 0 ? fmin(t, sm[k][cl]) : fmax(t, sm[k][cl]));
-    if (is_sum) reinterpret_cast<double*>(rec)[i] = t;
-    else rec[4 * C + (i - 2 * C)] = (float)t;
-  }
-}
-
-// second stage for the fp32 [nblk][4][C] partials a convolution epilogue emits (sum, sum of squares, min, max per tile): sums in fp64 (fixed
-// order), extremes exactly; out = the fp64 record (2C doubles sum | sum of squares, then min | max as 2C floats).
-// 16 columns x 64 row lanes per workgroup, four independent accumulators per lane (round 4: with 16 row lanes and one dependent fp64 chain per
-// lane the 4 096 partial rows of the image-side conv took 47 us -- a third of the conv itself)
-__global__ __launch_bounds__(1024) void colstats_minmax_stage2(const float* __restrict__ ws, float* __restrict__ out, int nblk, int C) {
-  const int cl = threadIdx.x & 15, rl = threadIdx.x >> 4;          // rl 0 .. 63
-  const int i = blockIdx.x * 16 + cl;   // over 4C
-  const int which = i < 4 * C ? i / C : 0, c = i < 4 * C ? i - which * C : 0;
-  const double init = which == 2 ? (double)INFINITY : (which == 3 ? -(double)INFINITY : 0.0);
-  double s4[4] = {init, init, init, init};
-  if (i < 4 * C) {
+  for (int u = 0; u < NACC; ++u) s[u] = is_sum ? 0.0 : (which == 2 ? (double)INFINITY : -(double)INFINITY);
+  if (live) {
     int b = rl;
-    for (; b + 3 * 64 < nblk; b += 4 * 64) {
-      double v[4];
+    for (; b + (NACC - 1) * RL < nblk; b += NACC * RL) {
+      double v[NACC];
 #pragma unroll
-      for (int u = 0; u < 4; ++u) v[u] = (double)ws[((size_t)(b + u * 64) * 4 + which) * C + c];
+      for (int u = 0; u < NACC; ++u) v[u] = at(b + u * RL);
 #pragma unroll
-      for (int u = 0; u < 4; ++u) s4[u] = which < 2 ? s4[u] + v[u] : (which == 2 ? fmin(s4[u], v[u]) : fmax(s4[u], v[u]));
+      for (int u = 0; u < NACC; ++u) s[u] = op(s[u], v[u]);
     }
-    for (int u = 0; b < nblk; b += 64, ++u) {
-      const double v = (double)ws[((size_t)b * 4 + which) * C + c];
-      s4[u] = which < 2 ? s4[u] + v : (which == 2 ? fmin(s4[u], v) : fmax(s4[u], v));
-    }
+    if constexpr (NACC > 1)
+      for (int u = 0; b < nblk; b += RL, ++u) s[u] = op(s[u], at(b));
   }
-  const double s = which < 2 ? (s4[0] + s4[1]) + (s4[2] + s4[3]) : (which == 2 ? fmin(fmin(s4[0], s4[1]), fmin(s4[2], s4[3])) : fmax(fmax(s4[0], s4[1]), fmax(s4[2], s4[3])));
-  __shared__ double sm[64][17];
-  sm[rl][cl] = s;
+  __shared__ double sm[RL][CL == 16 ? 17 : CL];
+  if constexpr (NACC == 4) sm[rl][cl] = op(op(s[0], s[1]), op(s[2], s[3]));
+  else sm[rl][cl] = s[0];
   __syncthreads();
-  if (rl == 0 && i < 4 * C) {
+  if (rl == 0 && live) {
+    constexpr int UNROLL = RL == 16 ? 16 : 8;
     double t = sm[0][cl];
-#pragma unroll 8
-    for (int k = 1; k < 64; ++k) t = which < 2 ? t + sm[k][cl] : (which == 2 ? fmin(t, sm[k][cl]) : fmax(t, sm[k][cl]));
-    // the fp64 record (see colstats64_stage1): 2C doubles = sum | sum of squares, then min | max as floats
-    if (which < 2) reinterpret_cast<double*>(out)[i] = t;
-    else out[4 * C + (i - 2 * C)] = (float)t;
-  }
-}
-
-// stage 2: one workgroup per 64 (which,channel) columns; 16 row-lanes stride over the stage-1 partials, combined in a
-// fixed order (fp64) -> deterministic and ~nblk/16 dependent adds instead of nblk (round 4: 4 row-lanes -> 16: 11 -> 6 us, 16 calls per iteration).
-__global__ __launch_bounds__(1024) void colstats_stage2(const float* __restrict__ ws, float* __restrict__ out, int nblk, int C) {
-  const int cl = threadIdx.x & 63, rl = threadIdx.x >> 6;       // rl 0 .. 15
-  const int i = blockIdx.x * 64 + cl;   // over 2C
-  double s = 0.0;
-  if (i < 2 * C) {
-    const int which = i / C, c = i - which * C;
-    for (int b = rl; b < nblk; b += 16) s += (double)ws[((size_t)b * 2 + which) * C + c];
-  }
-  __shared__ double sm[16][64];
-  sm[rl][cl] = s;
-  __syncthreads();
-  if (rl == 0 && i < 2 * C) {
-    double t = 0.0;
-#pragma unroll
-    for (int k = 0; k < 16; ++k) t += sm[k][cl];
-    out[i] = (float)t;
-  }
-}
-
-// stage 2 for MANY partials (the per-tile column sums a convolution epilogue emits: thousands of blocks): 16 columns x 16 row lanes per
-// workgroup, every lane sums each 16th partial in fp64, fixed-order LDS tree.
-__global__ __launch_bounds__(256) void colstats_stage2_wide(const float* __restrict__ ws, float* __restrict__ out, int nblk, int C) {
-  const int cl = threadIdx.x & 15, rl = threadIdx.x >> 4;
-  const int i = blockIdx.x * 16 + cl;   // over 2C
-  double s = 0.0;
-  if (i < 2 * C) {
-    const int which = i / C, c = i - which * C;
-    for (int b = rl; b < nblk; b += 16) s += (double)ws[((size_t)b * 2 + which) * C + c];
-  }
-  __shared__ double sm[16][17];
-  sm[rl][cl] = s;
-  __syncthreads();
-  if (rl == 0 && i < 2 * C) {
-    double t = 0.0;
-#pragma unroll
-    for (int k = 0; k < 16; ++k) t += sm[k][cl];
-    reinterpret_cast<double*>(out)[i] = t;          // the fp64 record (forward statistics only: ladder_bn_stats_from_partials)
+#pragma unroll UNROLL
+    for (int k = 1; k < RL; ++k) t = op(t, sm[k][cl]);
+    if (is_sum) reinterpret_cast<Out*>(rec)[i] = (Out)t;
+    else rec[4 * C + (i - 2 * C)] = (float)t;
   }
 }
 
@@ -332,88 +181,55 @@ __global__ void bn_finalize_kernel(const float* __restrict__ sums, double count,
   amax_clear_by_block0(clear_rec);
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= C) return;
-  const double* s64 = reinterpret_cast<const double*>(sums);      // the fp64 record: sum | sum of squares
-  const double mean = s64[c] / count;
-  double var = s64[C + c] / count - mean * mean;
-  if (var < 0.0) var = 0.0;
-  mean_rstd[c] = (float)mean;
-  mean_rstd[C + c] = (float)(1.0 / sqrt(var + (double)eps));
+  bn_moments(sums, C, c, count, eps, mean_rstd[c], mean_rstd[C + c]);
 }
 
+// C % 4 == 0 path: float4 per thread, grid-stride.  When the stride is a multiple of C (always for power-of-two channel counts) a thread
+// meets the same 4 channels in every iteration: their coefficients are loaded once -- per-iteration parameter gathers (24 dword loads
+// beside the two 16-byte data loads) held the backward kernel to ~2 TB/s.
 __global__ __launch_bounds__(256) void bn_apply_kernel(const float* __restrict__ x, const float* __restrict__ mean_rstd,
                                                        const float* __restrict__ gamma, const float* __restrict__ beta,
                                                        float* __restrict__ y, size_t n, int C, int act, float* __restrict__ yamax) {
-  // C % 4 == 0 path: float4 per thread, grid-stride; the 4 channels' coefficients are loaded once when the stride is a multiple of C
   const size_t stride = (size_t)gridDim.x * blockDim.x;
   const size_t i0 = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   const bool fixed = ((stride * 4) % (size_t)C) == 0;
-  int c = (int)((i0 * 4) % C);
-  float4 mu = *reinterpret_cast<const float4*>(mean_rstd + c), rs = *reinterpret_cast<const float4*>(mean_rstd + C + c);
-  float4 g = *reinterpret_cast<const float4*>(gamma + c), be = *reinterpret_cast<const float4*>(beta + c);
+  NormCoef<4> k = bn_coef<4>(mean_rstd, gamma, beta, C, (int)((i0 * 4) % C));
   float ymax = 0.f;
   for (size_t i = i0; i < n / 4; i += stride) {
-    if (!fixed) {
-      c = (int)((i * 4) % C);
-      mu = *reinterpret_cast<const float4*>(mean_rstd + c); rs = *reinterpret_cast<const float4*>(mean_rstd + C + c);
-      g = *reinterpret_cast<const float4*>(gamma + c); be = *reinterpret_cast<const float4*>(beta + c);
-    }
-    const float4 v = reinterpret_cast<const float4*>(x)[i];
-    float4 o;
-    o.x = ladder_act_fn(g.x * ((v.x - mu.x) * rs.x) + be.x, act);
-    o.y = ladder_act_fn(g.y * ((v.y - mu.y) * rs.y) + be.y, act);
-    o.z = ladder_act_fn(g.z * ((v.z - mu.z) * rs.z) + be.z, act);
-    o.w = ladder_act_fn(g.w * ((v.w - mu.w) * rs.w) + be.w, act);
-    reinterpret_cast<float4*>(y)[i] = o;
-    ymax = fmaxf(fmaxf(ymax, fmaxf(fabsf(o.x), fabsf(o.y))), fmaxf(fabsf(o.z), fabsf(o.w)));
+    if (!fixed) k = bn_coef<4>(mean_rstd, gamma, beta, C, (int)((i * 4) % C));
+    const Lanes<float, 4> o = norm_act(lanes_load<4>(x + i * 4), k, act);
+    lanes_store(y + i * 4, o);
+    ymax = lanes_absmax(ymax, o);
   }
   if (yamax != nullptr) amax_commit_block(ymax, yamax);     // max|y| for the split contraction that consumes y
 }
-// ... with the finalisation INSIDE (strict fp32, no absmax record): a thread derives the mean / 1 / sd of its four channels from the fp64 record itself -- the
-// expressions of bn_finalize_kernel, so the values are the same bits -- and workgroup 0 writes mean_rstd for the backward pass.  One launch less per batch
+// ... with the finalisation INSIDE (strict fp32, no absmax record): a thread derives the mean / 1 / sd of its four channels from the fp64 record itself
+// (bn_moments, as bn_finalize_kernel does: the same bits) and workgroup 0 writes mean_rstd for the backward pass.  One launch less per batch
 // norm (a 5 us kernel + its gap on the serial chain, twelve times an iteration).  Host side: only when the stride is a multiple of C.
 __global__ __launch_bounds__(256) void bn_apply_fin_kernel(const float* __restrict__ x, const float* __restrict__ sums, const double count, const float eps,
                                                            float* __restrict__ mean_rstd, const float* __restrict__ gamma, const float* __restrict__ beta,
                                                            float* __restrict__ y, size_t n, int C, int act) {
-  const double* s64 = reinterpret_cast<const double*>(sums);      // the fp64 record: sum | sum of squares
-  auto coef = [&](const int c, float& mu, float& rs) __attribute__((always_inline)) {
-    const double mean = s64[c] / count;
-    double var = s64[C + c] / count - mean * mean;
-    if (var < 0.0) var = 0.0;
-    mu = (float)mean;
-    rs = (float)(1.0 / sqrt(var + (double)eps));
-  };
   if (blockIdx.x == 0)
-    for (int c = threadIdx.x; c < C; c += 256) {
-      float mu, rs;
-      coef(c, mu, rs);
-      mean_rstd[c] = mu;
-      mean_rstd[C + c] = rs;
-    }
+    for (int c = threadIdx.x; c < C; c += 256) bn_moments(sums, C, c, count, eps, mean_rstd[c], mean_rstd[C + c]);
   const size_t stride = (size_t)gridDim.x * blockDim.x;
   const size_t i0 = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int c = (int)((i0 * 4) % C);
-  float mu[4], rs[4];
+  const Lanes<float, 4> g = lanes_load<4>(gamma + c), be = lanes_load<4>(beta + c);
+  NormCoef<4> k;
 #pragma unroll
-  for (int j = 0; j < 4; ++j) coef(c + j, mu[j], rs[j]);
-  const float4 g = *reinterpret_cast<const float4*>(gamma + c), be = *reinterpret_cast<const float4*>(beta + c);
-  for (size_t i = i0; i < n / 4; i += stride) {
-    const float4 v = reinterpret_cast<const float4*>(x)[i];
-    float4 o;
-    o.x = ladder_act_fn(g.x * ((v.x - mu[0]) * rs[0]) + be.x, act);
-    o.y = ladder_act_fn(g.y * ((v.y - mu[1]) * rs[1]) + be.y, act);
-    o.z = ladder_act_fn(g.z * ((v.z - mu[2]) * rs[2]) + be.z, act);
-    o.w = ladder_act_fn(g.w * ((v.w - mu[3]) * rs[3]) + be.w, act);
-    reinterpret_cast<float4*>(y)[i] = o;
+  for (int j = 0; j < 4; ++j) {
+    bn_moments(sums, C, c + j, count, eps, k.mean[j], k.rstd[j]);
+    k.scale[j] = g.v[j];
+    k.shift[j] = be.v[j];
   }
+  for (size_t i = i0; i < n / 4; i += stride) lanes_store(y + i * 4, norm_act(lanes_load<4>(x + i * 4), k, act));
 }
 __global__ void bn_apply_scalar_kernel(const float* __restrict__ x, const float* __restrict__ mean_rstd,
                                        const float* __restrict__ gamma, const float* __restrict__ beta,
                                        float* __restrict__ y, size_t n, int C, int act) {
   const size_t stride = (size_t)gridDim.x * blockDim.x;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    const int c = (int)(i % C);
-    y[i] = ladder_act_fn(gamma[c] * ((x[i] - mean_rstd[c]) * mean_rstd[C + c]) + beta[c], act);
-  }
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
+    y[i] = norm_act(x[i], bn_coef<1>(mean_rstd, gamma, beta, C, (int)(i % C)), act);
 }
 
 // ---- batch-norm apply that emits the fp16 PLANES of y (the operand images of the split gather kernels, ladder_presplit layout) ----------
@@ -425,15 +241,13 @@ __global__ __launch_bounds__(256) void bn_finalize_minmax_kernel(const float* __
                                                                  const float* __restrict__ beta, int C, int act, float* __restrict__ rec) {
   float bmax = 0.f;
   for (int c = threadIdx.x; c < C; c += blockDim.x) {
-    const double* s64 = reinterpret_cast<const double*>(sums4);   // the fp64 record: sum | sum of squares (2C doubles), then min | max (floats)
-    const double mean = s64[c] / count;
-    double var = s64[C + c] / count - mean * mean;
-    if (var < 0.0) var = 0.0;
-    const float mu = (float)mean, rs = (float)(1.0 / sqrt(var + (double)eps));
-    mean_rstd[c] = mu;
-    mean_rstd[C + c] = rs;
-    const float g = gamma[c], be = beta[c];
-    const float ylo = ladder_act_fn(g * ((sums4[4 * C + c] - mu) * rs) + be, act), yhi = ladder_act_fn(g * ((sums4[5 * C + c] - mu) * rs) + be, act);
+    NormCoef<1> k;                                     // the record in its minmax form: min | max (floats) behind the 2C doubles
+    bn_moments(sums4, C, c, count, eps, k.mean[0], k.rstd[0]);
+    mean_rstd[c] = k.mean[0];
+    mean_rstd[C + c] = k.rstd[0];
+    k.scale[0] = gamma[c];
+    k.shift[0] = beta[c];
+    const float ylo = norm_act(sums4[4 * C + c], k, act), yhi = norm_act(sums4[5 * C + c], k, act);
     bmax = fmaxf(bmax, fmaxf(fabsf(ylo), fabsf(yhi)));
   }
   __shared__ float red[4];
@@ -453,33 +267,24 @@ __global__ __launch_bounds__(256) void bn_apply_planes_kernel(const float* __res
   const size_t i0 = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   const bool fixed = ((stride * 4) % (size_t)C) == 0;
   const float cs = scale_from_absmax(amax_load(rec));
-  int c = (int)((i0 * 4) % C);
-  float4 mu = *reinterpret_cast<const float4*>(mean_rstd + c), rs = *reinterpret_cast<const float4*>(mean_rstd + C + c);
-  float4 g = *reinterpret_cast<const float4*>(gamma + c), be = *reinterpret_cast<const float4*>(beta + c);
+  NormCoef<4> k = bn_coef<4>(mean_rstd, gamma, beta, C, (int)((i0 * 4) % C));
   if (i0 == 0) {
     *reinterpret_cast<uint4*>(planes + 2 * n) = make_uint4(0u, 0u, 0u, 0u);      // the zero pad behind the last plane
     *reinterpret_cast<uint4*>(planes + 2 * n + 8) = make_uint4(0u, 0u, 0u, 0u);  // header (ladder_presplit): ONE scale for the tensor
   }
   for (size_t i = i0; i < n / 4; i += stride) {
-    if (!fixed) {
-      c = (int)((i * 4) % C);
-      mu = *reinterpret_cast<const float4*>(mean_rstd + c); rs = *reinterpret_cast<const float4*>(mean_rstd + C + c);
-      g = *reinterpret_cast<const float4*>(gamma + c); be = *reinterpret_cast<const float4*>(beta + c);
-    }
-    const float4 v = reinterpret_cast<const float4*>(x)[i];
-    float4 o;
-    o.x = ladder_act_fn(g.x * ((v.x - mu.x) * rs.x) + be.x, act);
-    o.y = ladder_act_fn(g.y * ((v.y - mu.y) * rs.y) + be.y, act);
-    o.z = ladder_act_fn(g.z * ((v.z - mu.z) * rs.z) + be.z, act);
-    o.w = ladder_act_fn(g.w * ((v.w - mu.w) * rs.w) + be.w, act);
-    if (y != nullptr) reinterpret_cast<float4*>(y)[i] = o;
+    if (!fixed) k = bn_coef<4>(mean_rstd, gamma, beta, C, (int)((i * 4) % C));
+    const Lanes<float, 4> o = norm_act(lanes_load<4>(x + i * 4), k, act);
+    if (y != nullptr) lanes_store(y + i * 4, o);
     uint2 pl[2];
-    split4<2, true>(make_float4(o.x * cs, o.y * cs, o.z * cs, o.w * cs), pl);
+    split4<2, true>(make_float4(o.v[0] * cs, o.v[1] * cs, o.v[2] * cs, o.v[3] * cs), pl);
     reinterpret_cast<uint2*>(planes)[i] = pl[0];
     reinterpret_cast<uint2*>(planes + n)[i] = pl[1];
   }
 }
 
+// (the two one-channel-per-thread backward kernels scale INSIDE the bracket, (xh * sum) * inv where norm_dx has xh * (sum * inv): they keep
+// their own last line, with the rounding they always had -- here no operation is fused)
 __global__ void bn_bwd_apply_kernel(const float* __restrict__ dy, const float* __restrict__ x,
                                     const float* __restrict__ mean_rstd, const float* __restrict__ gamma,
                                     const float* __restrict__ beta, const float* __restrict__ dsums, float inv_count,
@@ -487,12 +292,15 @@ __global__ void bn_bwd_apply_kernel(const float* __restrict__ dy, const float* _
   const size_t stride = (size_t)gridDim.x * blockDim.x;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
     const int c = (int)(i % C);
-    const float mu = mean_rstd[c], rs = mean_rstd[C + c], g = gamma[c];
-    const float xh = (x[i] - mu) * rs;
-    const float dp = dy[i] * ladder_act_grad_from_out(g * xh + beta[c], act);
-    dx[i] = g * rs * (dp - dsums[c] * inv_count - xh * dsums[C + c] * inv_count);
+    const NormCoef<1> k = bn_coef<1>(mean_rstd, gamma, beta, C, c);
+    float xh, grad;
+    norm_bwd_terms(x[i], k, act, xh, grad);
+    dx[i] = k.scale[0] * k.rstd[0] * (rounded(dy[i] * grad) - rounded(dsums[c] * inv_count) - rounded(xh * dsums[C + c] * inv_count));
   }
 }
+// NOT folded onto norm_dx: in the code the compiler makes of this kernel one of a thread's four channels rounds xh * s2 on its own (the
+// vectoriser packs that product with the g * rs products) while the other three fuse it.  No single expression reproduces that, so the
+// kernel keeps its text, and with it its bits, until a change that is allowed to move them.
 // float4 per thread, grid-stride.  When the stride is a multiple of C (always for power-of-two channel counts) a thread meets the same 4
 // channels in every iteration: their 6 coefficients are loaded once -- per-iteration parameter gathers (24 dword loads beside the two
 // 16-byte data loads) held this kernel to ~2 TB/s.
@@ -546,13 +354,6 @@ __global__ void bn_param_grad_kernel(const float* __restrict__ dsums, float* __r
 
 // ----------------------------------------------------------------------------- instance norm + style + act
 // one workgroup per (sample n, 64-channel group); 4 row-lanes stride over HW.
-__device__ __forceinline__ float block_rowlane_sum(float v, float (*sm)[64], int rl, int cl) {
-  __syncthreads();
-  sm[rl][cl] = v;
-  __syncthreads();
-  return (sm[0][cl] + sm[1][cl]) + (sm[2][cl] + sm[3][cl]);
-}
-
 __global__ __launch_bounds__(256) void in_style_fwd_kernel(const float* __restrict__ x, const float* __restrict__ style,
                                                            float* __restrict__ y, float* __restrict__ mean_rstd, int HW, int C,
                                                            float eps, int act) {
@@ -575,17 +376,18 @@ __global__ __launch_bounds__(256) void in_style_fwd_kernel(const float* __restri
   const float var = block_rowlane_sum(s, sm, rl, cl) / (float)HW;
   const float rstd = 1.0f / sqrtf(var + eps);
   if (!ok) return;
-  const float s0 = style[(size_t)n * 2 * C + c] + 1.f, s1 = style[(size_t)n * 2 * C + C + c];
+  const NormCoef<1> k = {{mean}, {rstd}, {style[(size_t)n * 2 * C + c] + 1.f}, {style[(size_t)n * 2 * C + C + c]}};
   if (rl == 0) {
     mean_rstd[(size_t)n * 2 * C + c] = mean;
     mean_rstd[(size_t)n * 2 * C + C + c] = rstd;
   }
   for (int r = rl; r < HW; r += 4) {
     const size_t i = (size_t)r * C + c;
-    yp[i] = ladder_act_fn((xp[i] - mean) * rstd * s0 + s1, act);
+    yp[i] = norm_act(xp[i], k, act);
   }
 }
 
+// dstyle[n] = sum dp * xhat | sum dp (both instance-norm backward paths)
 __global__ __launch_bounds__(256) void in_style_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ x,
                                                            const float* __restrict__ style, const float* __restrict__ mean_rstd,
                                                            float* __restrict__ dx, float* __restrict__ dstyle, int HW, int C, int act) {
@@ -594,35 +396,27 @@ __global__ __launch_bounds__(256) void in_style_bwd_kernel(const float* __restri
   const bool ok = c < C;
   const size_t base = (size_t)n * HW * C;
   __shared__ float sm[4][64];
-  float mean = 0.f, rstd = 0.f, s0 = 0.f, s1 = 0.f;
-  if (ok) {
-    mean = mean_rstd[(size_t)n * 2 * C + c];
-    rstd = mean_rstd[(size_t)n * 2 * C + C + c];
-    s0 = style[(size_t)n * 2 * C + c] + 1.f;
-    s1 = style[(size_t)n * 2 * C + C + c];
-  }
-  float a0 = 0.f, a1 = 0.f;
+  NormCoef<1> k = {{0.f}, {0.f}, {0.f}, {0.f}};
+  if (ok) k = in_coef<1>(mean_rstd, style, n, C, c);
+  Lanes<float, 1> a0 = {{0.f}}, a1 = {{0.f}};
   if (ok)
     for (int r = rl; r < HW; r += 4) {
       const size_t i = base + (size_t)r * C + c;
-      const float xh = (x[i] - mean) * rstd;
-      const float dp = dy[i] * ladder_act_grad_from_out(xh * s0 + s1, act);
-      a0 += dp * xh;
-      a1 += dp;
+      norm_bwd_accumulate<1>({{x[i]}}, {{dy[i]}}, k, act, a1, a0);
     }
-  const float ds0 = block_rowlane_sum(a0, sm, rl, cl);
-  const float ds1 = block_rowlane_sum(a1, sm, rl, cl);
+  const float ds0 = block_rowlane_sum(a0.v[0], sm, rl, cl);
+  const float ds1 = block_rowlane_sum(a1.v[0], sm, rl, cl);
   if (!ok) return;
   if (rl == 0) {
     dstyle[(size_t)n * 2 * C + c] = ds0;
     dstyle[(size_t)n * 2 * C + C + c] = ds1;
   }
   const float inv = 1.f / (float)HW;
-  for (int r = rl; r < HW; r += 4) {
+  for (int r = rl; r < HW; r += 4) {                       // (its own last line, see bn_bwd_apply_kernel: dy * grad - ds1 * inv fused, xh * ds0 rounded, then fused)
     const size_t i = base + (size_t)r * C + c;
-    const float xh = (x[i] - mean) * rstd;
-    const float dp = dy[i] * ladder_act_grad_from_out(xh * s0 + s1, act);
-    dx[i] = rstd * s0 * (dp - ds1 * inv - xh * ds0 * inv);
+    float xh, grad;
+    norm_bwd_terms(x[i], k, act, xh, grad);
+    dx[i] = (k.rstd[0] * k.scale[0]) * fmaf(-(xh * ds0), inv, fmaf(dy[i], grad, -(ds1 * inv)));
   }
 }
 
@@ -635,22 +429,32 @@ __global__ __launch_bounds__(256) void in_style_bwd_kernel(const float* __restri
 // zero-padded corner of the producing convolution, which can sit tens of standard deviations off a low-variance channel's mean -- found
 // by the full-resolution data-parallel test against the float64 oracle (batch 16: 1-3 % error on the gradients behind such a channel,
 // i.e. 40x the fp32 CPU restatement's deviation, while batch 8 happened to pass).  Partials are combined in a fixed order.
-__device__ __forceinline__ float4 f4add(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
 constexpr int IN_PIVOT_SAMPLES = 16;
 // average of pixels floor(k HW / 16), k = 0..15 (min(16, HW) of them) of channel(s) c of one instance: the same fp32 operations in the
 // same order for a scalar and for a float4 caller, so every workgroup of an instance and the finalize kernel agree bit for bit
-__device__ __forceinline__ float in_pivot(const float* __restrict__ xp, int HW, int C, int c) {
+template <int V>
+__device__ __forceinline__ Lanes<float, V> in_pivot(const float* __restrict__ xp, int HW, int C, int c) {
   const int cnt = HW < IN_PIVOT_SAMPLES ? HW : IN_PIVOT_SAMPLES;
-  float s = 0.f;
-  for (int k = 0; k < cnt; ++k) s += xp[(size_t)((long)k * HW / cnt) * C + c];
-  return s * (1.f / (float)cnt);
-}
-__device__ __forceinline__ float4 in_pivot4(const float* __restrict__ xp, int HW, int C, int c) {
-  const int cnt = HW < IN_PIVOT_SAMPLES ? HW : IN_PIVOT_SAMPLES;
-  float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
-  for (int k = 0; k < cnt; ++k) s = f4add(s, *reinterpret_cast<const float4*>(xp + (size_t)((long)k * HW / cnt) * C + c));
+  Lanes<float, V> s = lanes_fill<float, V>(0.f);
+  for (int k = 0; k < cnt; ++k) {
+    const Lanes<float, V> v = lanes_load<V>(xp + (size_t)((long)k * HW / cnt) * C + c);
+#pragma unroll
+    for (int j = 0; j < V; ++j) s.v[j] += v.v[j];
+  }
   const float r = 1.f / (float)cnt;
-  return make_float4(s.x * r, s.y * r, s.z * r, s.w * r);
+#pragma unroll
+  for (int j = 0; j < V; ++j) s.v[j] *= r;
+  return s;
+}
+
+// the two partial sums of a workgroup: its 16 row lanes in order, to part [N][split][2][C]
+__device__ __forceinline__ void in_part_store(const Lanes<float, 4>& a0, const Lanes<float, 4>& a1, float* __restrict__ part, int n, int split, int sp,
+                                              int C, int c, int cq, int rl) {
+  __shared__ Lanes<float, 4> sm[2][16][16];
+  sm[0][rl][cq] = a0;
+  sm[1][rl][cq] = a1;
+  __syncthreads();
+  if (rl < 2 && c < C) lanes_store(part + (((size_t)n * split + sp) * 2 + rl) * C + c, rowlane16_reduce<LaneAdd>(sm[rl], cq));
 }
 
 __global__ __launch_bounds__(256) void in_stats_kernel(const float* __restrict__ x, float* __restrict__ part, int HW, int C, int split) {
@@ -658,26 +462,20 @@ __global__ __launch_bounds__(256) void in_stats_kernel(const float* __restrict__
   const int n = blockIdx.y, c = blockIdx.x * 64 + cq * 4, sp = blockIdx.z;
   const float* xp = x + (size_t)n * HW * C;
   const int per = (HW + split - 1) / split, r0 = sp * per, r1 = min(HW, r0 + per);
-  float4 s0 = make_float4(0.f, 0.f, 0.f, 0.f), s1 = s0;
+  Lanes<float, 4> s0 = lanes_fill<float, 4>(0.f), s1 = s0;
   if (c < C) {
-    const float4 pv = in_pivot4(xp, HW, C, c);
+    const Lanes<float, 4> pv = in_pivot<4>(xp, HW, C, c);
     for (int r = r0 + rl; r < r1; r += 16) {
-      const float4 v = *reinterpret_cast<const float4*>(xp + (size_t)r * C + c);
-      const float dx = v.x - pv.x, dy = v.y - pv.y, dz = v.z - pv.z, dw = v.w - pv.w;
-      s0.x += dx; s0.y += dy; s0.z += dz; s0.w += dw;
-      s1.x += dx * dx; s1.y += dy * dy; s1.z += dz * dz; s1.w += dw * dw;
+      const Lanes<float, 4> v = lanes_load<4>(xp + (size_t)r * C + c);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const float d = v.v[j] - pv.v[j];
+        s0.v[j] += d;
+        s1.v[j] += d * d;
+      }
     }
   }
-  __shared__ float4 sm[2][16][16];
-  sm[0][rl][cq] = s0;
-  sm[1][rl][cq] = s1;
-  __syncthreads();
-  if (rl < 2 && c < C) {
-    float4 t = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-    for (int k = 0; k < 16; ++k) t = f4add(t, sm[rl][k][cq]);
-    *reinterpret_cast<float4*>(part + (((size_t)n * split + sp) * 2 + rl) * C + c) = t;
-  }
+  in_part_store(s0, s1, part, n, split, sp, C, c, cq, rl);
 }
 
 __global__ void in_finalize_kernel(const float* __restrict__ x, const float* __restrict__ part, float* __restrict__ mean_rstd,
@@ -691,7 +489,7 @@ __global__ void in_finalize_kernel(const float* __restrict__ x, const float* __r
     s0 += (double)part[(((size_t)n * split + sp) * 2 + 0) * C + c];
     s1 += (double)part[(((size_t)n * split + sp) * 2 + 1) * C + c];
   }
-  const double pv = (double)in_pivot(x + (size_t)n * HW * C, HW, C, c);
+  const double pv = (double)in_pivot<1>(x + (size_t)n * HW * C, HW, C, c).v[0];
   const double md = s0 / HW;
   double var = s1 / HW - md * md;
   if (var < 0.0) var = 0.0;
@@ -713,21 +511,12 @@ __global__ __launch_bounds__(256) void in_apply_kernel(const float* __restrict__
   float ymax = 0.f;
   const size_t base = (size_t)n * HW * C;
   const int per = (HW + split - 1) / split, r0 = sp * per, r1 = live ? min(HW, r0 + per) : r0;
-  const float4 mu = *reinterpret_cast<const float4*>(mean_rstd + (size_t)n * 2 * C + c);
-  const float4 rs = *reinterpret_cast<const float4*>(mean_rstd + (size_t)n * 2 * C + C + c);
-  float4 s0 = *reinterpret_cast<const float4*>(style + (size_t)n * 2 * C + c);
-  const float4 s1 = *reinterpret_cast<const float4*>(style + (size_t)n * 2 * C + C + c);
-  s0.x += 1.f; s0.y += 1.f; s0.z += 1.f; s0.w += 1.f;
+  const NormCoef<4> k = in_coef<4>(mean_rstd, style, n, C, c);
   for (int r = r0 + rl; r < r1; r += 16) {
     const size_t i = base + (size_t)r * C + c;
-    const float4 v = *reinterpret_cast<const float4*>(x + i);
-    float4 o;
-    o.x = ladder_act_fn((v.x - mu.x) * rs.x * s0.x + s1.x, act);
-    o.y = ladder_act_fn((v.y - mu.y) * rs.y * s0.y + s1.y, act);
-    o.z = ladder_act_fn((v.z - mu.z) * rs.z * s0.z + s1.z, act);
-    o.w = ladder_act_fn((v.w - mu.w) * rs.w * s0.w + s1.w, act);
-    *reinterpret_cast<float4*>(y + i) = o;
-    ymax = fmaxf(fmaxf(ymax, fmaxf(fabsf(o.x), fabsf(o.y))), fmaxf(fabsf(o.z), fabsf(o.w)));
+    const Lanes<float, 4> o = norm_act(lanes_load<4>(x + i), k, act);
+    lanes_store(y + i, o);
+    ymax = lanes_absmax(ymax, o);
   }
   if (yamax != nullptr) amax_commit_block_sample(ymax, yamax, n);      // (blockIdx.y = sample: a per-sample record)
 }
@@ -740,33 +529,15 @@ __global__ __launch_bounds__(256) void in_bwd_stats_kernel(const float* __restri
   const int n = blockIdx.y, c = blockIdx.x * 64 + cq * 4, sp = blockIdx.z;
   const size_t base = (size_t)n * HW * C;
   const int per = (HW + split - 1) / split, r0 = sp * per, r1 = min(HW, r0 + per);
-  float4 a0 = make_float4(0.f, 0.f, 0.f, 0.f), a1 = a0;
+  Lanes<float, 4> a0 = lanes_fill<float, 4>(0.f), a1 = a0;
   if (c < C) {
-    const float4 mu = *reinterpret_cast<const float4*>(mean_rstd + (size_t)n * 2 * C + c);
-    const float4 rs = *reinterpret_cast<const float4*>(mean_rstd + (size_t)n * 2 * C + C + c);
-    float4 s0 = *reinterpret_cast<const float4*>(style + (size_t)n * 2 * C + c);
-    const float4 s1 = *reinterpret_cast<const float4*>(style + (size_t)n * 2 * C + C + c);
-    s0.x += 1.f; s0.y += 1.f; s0.z += 1.f; s0.w += 1.f;
+    const NormCoef<4> k = in_coef<4>(mean_rstd, style, n, C, c);
     for (int r = r0 + rl; r < r1; r += 16) {
       const size_t i = base + (size_t)r * C + c;
-      const float4 xv = *reinterpret_cast<const float4*>(x + i), dv = *reinterpret_cast<const float4*>(dy + i);
-      float xh, dp;
-      xh = (xv.x - mu.x) * rs.x; dp = dv.x * ladder_act_grad_from_out(xh * s0.x + s1.x, act); a0.x += dp * xh; a1.x += dp;
-      xh = (xv.y - mu.y) * rs.y; dp = dv.y * ladder_act_grad_from_out(xh * s0.y + s1.y, act); a0.y += dp * xh; a1.y += dp;
-      xh = (xv.z - mu.z) * rs.z; dp = dv.z * ladder_act_grad_from_out(xh * s0.z + s1.z, act); a0.z += dp * xh; a1.z += dp;
-      xh = (xv.w - mu.w) * rs.w; dp = dv.w * ladder_act_grad_from_out(xh * s0.w + s1.w, act); a0.w += dp * xh; a1.w += dp;
+      norm_bwd_accumulate(lanes_load<4>(x + i), lanes_load<4>(dy + i), k, act, a1, a0);
     }
   }
-  __shared__ float4 sm[2][16][16];
-  sm[0][rl][cq] = a0;
-  sm[1][rl][cq] = a1;
-  __syncthreads();
-  if (rl < 2 && c < C) {
-    float4 t = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-    for (int k = 0; k < 16; ++k) t = f4add(t, sm[rl][k][cq]);
-    *reinterpret_cast<float4*>(part + (((size_t)n * split + sp) * 2 + rl) * C + c) = t;
-  }
+  in_part_store(a0, a1, part, n, split, sp, C, c, cq, rl);
 }
 __global__ void in_bwd_finalize_kernel(const float* __restrict__ part, float* __restrict__ dstyle, int N, int C, int split,
                                        float* __restrict__ clear_rec) {
@@ -798,29 +569,20 @@ __global__ __launch_bounds__(256) void in_bwd_apply_kernel(const float* __restri
   const size_t base = (size_t)n * HW * C;
   const int per = (HW + split - 1) / split, r0 = sp * per, r1 = live ? min(HW, r0 + per) : r0;
   const float inv = 1.f / (float)HW;
-  float mu[4], rs[4], s0[4], s1[4], d0[4], d1[4];
+  const NormCoef<4> k = in_coef<4>(mean_rstd, style, n, C, c);
+  Lanes<float, 4> m1, m2;
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
-    mu[j] = mean_rstd[(size_t)n * 2 * C + c + j];
-    rs[j] = mean_rstd[(size_t)n * 2 * C + C + c + j];
-    s0[j] = style[(size_t)n * 2 * C + c + j] + 1.f;
-    s1[j] = style[(size_t)n * 2 * C + C + c + j];
-    d0[j] = dstyle[(size_t)n * 2 * C + c + j] * inv;
-    d1[j] = dstyle[(size_t)n * 2 * C + C + c + j] * inv;
+    m2.v[j] = dstyle[(size_t)n * 2 * C + c + j] * inv;
+    m1.v[j] = dstyle[(size_t)n * 2 * C + C + c + j] * inv;
   }
   for (int r = r0 + rl; r < r1; r += 16) {
     const size_t i = base + (size_t)r * C + c;
-    const float4 xv = *reinterpret_cast<const float4*>(x + i), dv = *reinterpret_cast<const float4*>(dy + i);
-    const float xs[4] = {xv.x, xv.y, xv.z, xv.w}, ds[4] = {dv.x, dv.y, dv.z, dv.w};
-    float o[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const float xh = (xs[j] - mu[j]) * rs[j];
-      const float dp = ds[j] * ladder_act_grad_from_out(xh * s0[j] + s1[j], act);
-      o[j] = rs[j] * s0[j] * (dp - d1[j] - xh * d0[j]);
-    }
-    *reinterpret_cast<float4*>(dx + i) = make_float4(o[0], o[1], o[2], o[3]);
-    omax = fmaxf(fmaxf(omax, fmaxf(fabsf(o[0]), fabsf(o[1]))), fmaxf(fabsf(o[2]), fabsf(o[3])));
+    Lanes<float, 4> xh, grad;
+    norm_bwd_terms(lanes_load<4>(x + i), k, act, xh, grad);
+    const Lanes<float, 4> o = norm_dx(xh, lanes_load<4>(dy + i), grad, k, m1, m2);
+    lanes_store(dx + i, o);
+    omax = lanes_absmax(omax, o);
   }
   if (dxamax != nullptr) amax_commit_block_sample(omax, dxamax, n);
 }
@@ -899,21 +661,12 @@ __global__ __launch_bounds__(256) void in_apply_resize2x_kernel(const float* __r
     const int cv = (int)(j % CV);
     const int pix = (int)(j / CV), iy = pix / W, ix = pix - iy * W;
     const int c = cv * 4;
-    const float4 mu = *reinterpret_cast<const float4*>(mean_rstd + (size_t)n * 2 * C + c);
-    const float4 rs = *reinterpret_cast<const float4*>(mean_rstd + (size_t)n * 2 * C + C + c);
-    float4 s0 = *reinterpret_cast<const float4*>(style + (size_t)n * 2 * C + c);
-    const float4 s1 = *reinterpret_cast<const float4*>(style + (size_t)n * 2 * C + C + c);
-    s0.x += 1.f; s0.y += 1.f; s0.z += 1.f; s0.w += 1.f;
+    const NormCoef<4> k = in_coef<4>(mean_rstd, style, n, C, c);
     const int yh = min(iy + 1, H - 1), xh = min(ix + 1, W - 1);
     const float* xb = x + (size_t)n * H * W * C + c;
     auto norm = [&](int r, int q) -> float4 {
-      const float4 v = *reinterpret_cast<const float4*>(xb + ((size_t)r * W + q) * C);
-      float4 o;
-      o.x = ladder_act_fn((v.x - mu.x) * rs.x * s0.x + s1.x, act);
-      o.y = ladder_act_fn((v.y - mu.y) * rs.y * s0.y + s1.y, act);
-      o.z = ladder_act_fn((v.z - mu.z) * rs.z * s0.z + s1.z, act);
-      o.w = ladder_act_fn((v.w - mu.w) * rs.w * s0.w + s1.w, act);
-      return o;
+      const Lanes<float, 4> o = norm_act(lanes_load<4>(xb + ((size_t)r * W + q) * C), k, act);
+      return make_float4(o.v[0], o.v[1], o.v[2], o.v[3]);
     };
     const float4 tl = norm(iy, ix), tr = norm(iy, xh), bl = norm(yh, ix), br = norm(yh, xh);
     ymax = fmaxf(fmaxf(fabsf(tl.x), fabsf(tl.y)), fmaxf(fabsf(tl.z), fabsf(tl.w)));
@@ -1129,6 +882,22 @@ inline unsigned ew_grid(size_t work_items) {
 
 }  // namespace
 
+// the float4 kernels: C % 4 == 0 and every tensor they access 16 bytes at a time on a 16-byte boundary
+template <typename... P>
+static bool vec4_ok(int C, const P*... p) {
+  return C % 4 == 0 && (ladder_aligned16(p) && ...);
+}
+// ... and, for instance norm, the workspace of the split three-kernel path
+template <typename... P>
+static bool in_vec_ok(int N, int HW, int C, const void* ws, size_t ws_bytes, const P*... p) {
+  return C % 4 == 0 && ws != nullptr && ws_bytes >= ladder_in_style_workspace_bytes(N, HW, C) && vec4_ok(C, p...);
+}
+
+template <int V, typename Row>
+static void stage1_launch(const Row& row, size_t rows, int C, size_t nblk, hipStream_t stream) {
+  hipLaunchKernelGGL((colstats_stage1<Row, V>), dim3((C + 63) / 64, (unsigned)nblk), dim3(256), 0, stream, row, rows, C, (rows + nblk - 1) / nblk);
+}
+
 extern "C" {
 
 int ladder_bn_fwd_stats(const float* x, float* sums, size_t rows, int C, void* ws, size_t ws_bytes, ladder_stream_t stream) {
@@ -1136,20 +905,20 @@ int ladder_bn_fwd_stats(const float* x, float* sums, size_t rows, int C, void* w
   const size_t nblk = stats_nblk(rows);
   if (ws_bytes < nblk * 2 * (size_t)C * sizeof(double)) return LADDER_E_WORKSPACE;
   if ((reinterpret_cast<uintptr_t>(sums) & 7u) != 0 || (reinterpret_cast<uintptr_t>(ws) & 7u) != 0) return LADDER_E_ALIGN;
-  const size_t rpb = (rows + nblk - 1) / nblk;
-  if (C % 4 == 0 && ladder_aligned16(x))
-    hipLaunchKernelGGL(colstats64_stage1_v4<false>, dim3((C + 63) / 64, (unsigned)nblk), dim3(256), 0, stream, x, (double*)ws, (float*)nullptr, rows, C, rpb);
-  else
-    hipLaunchKernelGGL(colstats64_stage1, dim3((C + 63) / 64, (unsigned)nblk), dim3(256), 0, stream, x, (double*)ws, rows, C, rpb);
-  hipLaunchKernelGGL(colstats64_stage2, dim3((2 * C + 63) / 64), dim3(1024), 0, stream, (const double*)ws, (const float*)nullptr, sums, (int)nblk, C);
+  const MomentsRow<false> row = {x, (double*)ws, nullptr};
+  if (vec4_ok(C, x)) stage1_launch<4>(row, rows, C, nblk, stream);
+  else stage1_launch<1>(row, rows, C, nblk, stream);
+  hipLaunchKernelGGL((colstats_stage2<64, 16, 1, false, double, double>), dim3((2 * C + 63) / 64), dim3(1024), 0, stream, (const double*)ws, 2,
+                     (const float*)nullptr, 0, 0, sums, (int)nblk, C);
   LADDER_CHECK_LAUNCH();
   return LADDER_OK;
 }
 
-// sums[0:C] = sum over blocks of partials[b][0][:], sums[C:2C] = ... of partials[b][1][:]  (partials [nblk][2][C]; fixed order, fp64)
+// sums[0:C] = sum over blocks of partials[b][0][:], sums[C:2C] = ... of partials[b][1][:]  (partials [nblk][2][C]; fixed order, fp64; the fp64 record)
 int ladder_bn_stats_from_partials(const float* partials, int nblk, float* sums, int C, ladder_stream_t stream) {
   if (nblk <= 0 || C <= 0) return LADDER_E_SHAPE;
-  hipLaunchKernelGGL(colstats_stage2_wide, dim3((2 * C + 15) / 16), dim3(256), 0, stream, partials, sums, nblk, C);
+  hipLaunchKernelGGL((colstats_stage2<16, 16, 1, false, float, double>), dim3((2 * C + 15) / 16), dim3(256), 0, stream, partials, 2,
+                     (const float*)nullptr, 0, 0, sums, nblk, C);
   LADDER_CHECK_LAUNCH();
   return LADDER_OK;
 }
@@ -1162,20 +931,18 @@ int ladder_bn_fwd_apply(const float* x, const float* sums, double count, const f
 int ladder_bn_fwd_apply_absmax(const float* x, const float* sums, double count, const float* gamma, const float* beta, float* y,
                                float* mean_rstd, size_t rows, int C, float eps, int act, float* y_absmax, ladder_stream_t stream) {
   if (rows == 0 || C <= 0 || count <= 0) return LADDER_E_SHAPE;
-  if (y_absmax != nullptr) {                     // the record is produced by the vectorised kernel only
-    if (!(C % 4 == 0 && ladder_aligned16(x) && ladder_aligned16(y))) return LADDER_E_SHAPE;
-  }
+  const bool v4 = vec4_ok(C, x, y);
+  if (y_absmax != nullptr && !v4) return LADDER_E_SHAPE;      // the record is produced by the vectorised kernel only
   const size_t n = rows * (size_t)C;
   static const bool fold = getenv("LADDER_DISABLE_BN_FOLD") == nullptr;      // (A / B switch: the finalisation as a launch of its own)
-  if (fold && y_absmax == nullptr && C % 4 == 0 && ladder_aligned16(x) && ladder_aligned16(y) && ladder_aligned16(gamma) && ladder_aligned16(beta) &&
-      ((size_t)ew_grid(n / 4) * 256 * 4) % (size_t)C == 0) {
+  if (fold && y_absmax == nullptr && v4 && ladder_aligned16(gamma) && ladder_aligned16(beta) && ((size_t)ew_grid(n / 4) * 256 * 4) % (size_t)C == 0) {
     hipLaunchKernelGGL(bn_apply_fin_kernel, dim3(ew_grid(n / 4)), dim3(256), 0, stream, x, sums, count, eps, mean_rstd, gamma, beta, y, n, C, act);
     LADDER_CHECK_LAUNCH();
     return LADDER_OK;
   }
   // (the finalize kernel clears the record: no separate memset launch)
   hipLaunchKernelGGL(bn_finalize_kernel, dim3((C + 255) / 256), dim3(256), 0, stream, sums, count, eps, mean_rstd, C, y_absmax);
-  if (C % 4 == 0 && ladder_aligned16(x) && ladder_aligned16(y))
+  if (v4)
     hipLaunchKernelGGL(bn_apply_kernel, dim3(ew_grid(n / 4)), dim3(256), 0, stream, x, mean_rstd, gamma, beta, y, n, C, act, y_absmax);
   else
     hipLaunchKernelGGL(bn_apply_scalar_kernel, dim3(ew_grid(n)), dim3(256), 0, stream, x, mean_rstd, gamma, beta, y, n, C, act);
@@ -1190,18 +957,19 @@ int ladder_bn_fwd_stats_minmax(const float* x, float* sums4, size_t rows, int C,
   const size_t nblk = stats_nblk(rows);
   if (ws_bytes < nblk * (2 * (size_t)C * sizeof(double) + 2 * (size_t)C * sizeof(float))) return LADDER_E_WORKSPACE;
   if ((reinterpret_cast<uintptr_t>(sums4) & 7u) != 0 || (reinterpret_cast<uintptr_t>(ws) & 7u) != 0) return LADDER_E_ALIGN;
-  const size_t rpb = (rows + nblk - 1) / nblk;
   float* wsmm = reinterpret_cast<float*>(reinterpret_cast<double*>(ws) + nblk * 2 * (size_t)C);
-  hipLaunchKernelGGL(colstats64_stage1_v4<true>, dim3((C + 63) / 64, (unsigned)nblk), dim3(256), 0, stream, x, (double*)ws, wsmm, rows, C, rpb);
-  hipLaunchKernelGGL(colstats64_stage2, dim3((4 * C + 63) / 64), dim3(1024), 0, stream, (const double*)ws, (const float*)wsmm, sums4, (int)nblk, C);
+  stage1_launch<4>(MomentsRow<true>{x, (double*)ws, wsmm}, rows, C, nblk, stream);
+  hipLaunchKernelGGL((colstats_stage2<64, 16, 1, true, double, double>), dim3((4 * C + 63) / 64), dim3(1024), 0, stream, (const double*)ws, 2,
+                     (const float*)wsmm, 2, 0, sums4, (int)nblk, C);
   LADDER_CHECK_LAUNCH();
   return LADDER_OK;
 }
 
-// the second stage alone, for [nblk][4][C] partials emitted by a convolution epilogue
+// the second stage alone, for [nblk][4][C] partials (sum, sum of squares, min, max per tile) emitted by a convolution epilogue
 int ladder_bn_stats_minmax_from_partials(const float* partials, int nblk, float* sums4, int C, ladder_stream_t stream) {
   if (nblk <= 0 || C <= 0) return LADDER_E_SHAPE;
-  hipLaunchKernelGGL(colstats_minmax_stage2, dim3((4 * C + 15) / 16), dim3(1024), 0, stream, partials, sums4, nblk, C);
+  hipLaunchKernelGGL((colstats_stage2<16, 64, 4, true, float, double>), dim3((4 * C + 15) / 16), dim3(1024), 0, stream, partials, 4, partials, 4, 2,
+                     sums4, nblk, C);
   LADDER_CHECK_LAUNCH();
   return LADDER_OK;
 }
@@ -1226,14 +994,11 @@ int ladder_bn_bwd_stats(const float* dy, const float* x, const float* mean_rstd,
   if (rows == 0 || C <= 0) return LADDER_E_SHAPE;
   const size_t nblk = stats_nblk(rows);
   if (ws_bytes < nblk * 2 * (size_t)C * sizeof(float)) return LADDER_E_WORKSPACE;
-  const size_t rpb = (rows + nblk - 1) / nblk;
-  if (C % 4 == 0 && ladder_aligned16(x) && ladder_aligned16(dy))
-    hipLaunchKernelGGL(colstats_stage1_v4<2>, dim3((C + 63) / 64, (unsigned)nblk), dim3(256), 0, stream, dy, x, mean_rstd, gamma, beta,
-                       (float*)ws, rows, C, rpb, act);
-  else
-    hipLaunchKernelGGL(colstats_stage1<2>, dim3((C + 63) / 64, (unsigned)nblk), dim3(256), 0, stream, dy, x, mean_rstd, gamma, beta,
-                       (float*)ws, rows, C, rpb, act);
-  hipLaunchKernelGGL(colstats_stage2, dim3((2 * C + 63) / 64), dim3(1024), 0, stream, (const float*)ws, dsums, (int)nblk, C);
+  const BnBwdRow row = {dy, x, mean_rstd, gamma, beta, (float*)ws, act};
+  if (vec4_ok(C, x, dy)) stage1_launch<4>(row, rows, C, nblk, stream);
+  else stage1_launch<1>(row, rows, C, nblk, stream);
+  hipLaunchKernelGGL((colstats_stage2<64, 16, 1, false, float, float>), dim3((2 * C + 63) / 64), dim3(1024), 0, stream, (const float*)ws, 2,
+                     (const float*)nullptr, 0, 0, dsums, (int)nblk, C);
   LADDER_CHECK_LAUNCH();
   return LADDER_OK;
 }
@@ -1249,12 +1014,10 @@ int ladder_bn_bwd_apply_absmax(const float* dy, const float* x, const float* mea
                                float* dx_absmax, ladder_stream_t stream) {
   if (rows == 0 || C <= 0 || count <= 0) return LADDER_E_SHAPE;
   const size_t n = rows * (size_t)C;
-  if (dx_absmax != nullptr) {
-    if (!(dx != nullptr && C % 4 == 0 && ladder_aligned16(x) && ladder_aligned16(dy) && ladder_aligned16(dx))) return LADDER_E_SHAPE;
-  }
+  const bool v4 = dx != nullptr && vec4_ok(C, x, dy, dx);
+  if (dx_absmax != nullptr && !v4) return LADDER_E_SHAPE;
   // the parameter-gradient kernel runs first and clears the record on its way (no memset launch); without parameter gradients: memset
   const bool pgrad = dgamma != nullptr && dbeta != nullptr;
-  const bool v4 = dx != nullptr && C % 4 == 0 && ladder_aligned16(x) && ladder_aligned16(dy) && ladder_aligned16(dx);
   static const bool fold = getenv("LADDER_DISABLE_BN_FOLD") == nullptr;
   const bool pgrad_rides = fold && pgrad && v4 && dx_absmax == nullptr;   // strict fp32: workgroup 0 of the apply kernel copies them
   if (pgrad && !pgrad_rides)
@@ -1285,11 +1048,9 @@ int ladder_in_style_fwd(const float* x, const float* style, float* y, float* mea
 int ladder_in_style_fwd_absmax(const float* x, const float* style, float* y, float* mean_rstd, int N, int HW, int C, float eps, int act,
                                void* ws, size_t ws_bytes, float* y_absmax, ladder_stream_t stream) {
   if (N <= 0 || HW <= 0 || C <= 0) return LADDER_E_SHAPE;
-  if (y_absmax != nullptr) {
-    if (!(C % 4 == 0 && ws != nullptr && ws_bytes >= ladder_in_style_workspace_bytes(N, HW, C) && ladder_aligned16(x) && ladder_aligned16(y)))
-      return LADDER_E_SHAPE;                     // the record is produced by the vectorised three-kernel path only (its finalize kernel clears it)
-  }
-  if (C % 4 == 0 && ws != nullptr && ws_bytes >= ladder_in_style_workspace_bytes(N, HW, C) && ladder_aligned16(x) && ladder_aligned16(y)) {
+  const bool vec = in_vec_ok(N, HW, C, ws, ws_bytes, x, y);
+  if (y_absmax != nullptr && !vec) return LADDER_E_SHAPE;      // the record is produced by the vectorised three-kernel path only (its finalize kernel clears it)
+  if (vec) {
     const int sp = in_split(N, HW, C);
     dim3 grid((C + 63) / 64, N, sp);
     hipLaunchKernelGGL(in_stats_kernel, grid, dim3(256), 0, stream, x, (float*)ws, HW, C, sp);
@@ -1317,8 +1078,7 @@ int ladder_in_style_fwd_resize2x_keep(const float* x, const float* style, float*
   if (N <= 0 || H <= 0 || W <= 0 || C <= 0) return LADDER_E_SHAPE;
   if (y != nullptr && !ladder_aligned16(y)) return LADDER_E_ALIGN;
   const int HW = H * W;
-  if (!(C % 4 == 0 && ws != nullptr && ws_bytes >= ladder_in_style_workspace_bytes(N, HW, C) && ladder_aligned16(x) && ladder_aligned16(up)))
-    return LADDER_E_SHAPE;
+  if (!in_vec_ok(N, HW, C, ws, ws_bytes, x, up)) return LADDER_E_SHAPE;
   const int sp = in_split(N, HW, C);
   dim3 grid((C + 63) / 64, N, sp);
   hipLaunchKernelGGL(in_stats_kernel, grid, dim3(256), 0, stream, x, (float*)ws, HW, C, sp);
@@ -1338,13 +1098,9 @@ int ladder_in_style_bwd(const float* dy, const float* x, const float* style, con
 int ladder_in_style_bwd_absmax(const float* dy, const float* x, const float* style, const float* mean_rstd, float* dx, float* dstyle,
                                int N, int HW, int C, int act, void* ws, size_t ws_bytes, float* dx_absmax, ladder_stream_t stream) {
   if (N <= 0 || HW <= 0 || C <= 0) return LADDER_E_SHAPE;
-  if (dx_absmax != nullptr) {
-    if (!(C % 4 == 0 && ws != nullptr && ws_bytes >= ladder_in_style_workspace_bytes(N, HW, C) && ladder_aligned16(x) && ladder_aligned16(dy) &&
-          ladder_aligned16(dx)))
-      return LADDER_E_SHAPE;
-  }
-  if (C % 4 == 0 && ws != nullptr && ws_bytes >= ladder_in_style_workspace_bytes(N, HW, C) && ladder_aligned16(x) && ladder_aligned16(dy) &&
-      ladder_aligned16(dx)) {
+  const bool vec = in_vec_ok(N, HW, C, ws, ws_bytes, x, dy, dx);
+  if (dx_absmax != nullptr && !vec) return LADDER_E_SHAPE;
+  if (vec) {
     const int sp = in_split(N, HW, C);
     dim3 grid((C + 63) / 64, N, sp);
     hipLaunchKernelGGL(in_bwd_stats_kernel, grid, dim3(256), 0, stream, dy, x, style, mean_rstd, (float*)ws, HW, C, act, sp);

@@ -176,7 +176,7 @@ def test_dense_fwd_bwd(gpu_ctx, M, K, N, act):
 
 
 @pytest.mark.parametrize("shape,act", [((4, 8, 8, 128), "leaky_relu"), ((3, 5, 7, 20), None), ((2, 2, 2, 512), "leaky_relu"),
-                                       ((16, 32, 32, 64), "leaky_relu")])
+                                       ((16, 32, 32, 64), "leaky_relu"), ((3, 5, 7, 10), None), ((4, 4, 4, 6), "leaky_relu")])     # (C % 4 != 0: one channel per thread)
 def test_batch_norm(gpu_ctx, shape, act):
     L = _lib()
     rng = np.random.default_rng(sum(shape))
@@ -264,7 +264,7 @@ def test_batch_norm_far_off_centre_two_ranks():
     assert np.abs(out - yr.numpy()).max() / np.abs(yr.numpy()).max() < 1e-5
 
 
-@pytest.mark.parametrize("shape", [(3, 2, 2, 64), (2, 16, 16, 32), (2, 8, 8, 100), (4, 64, 64, 128)])
+@pytest.mark.parametrize("shape", [(3, 2, 2, 64), (2, 16, 16, 32), (2, 8, 8, 100), (4, 64, 64, 128), (2, 5, 5, 10)])    # (C = 10: no workspace path)
 def test_instance_norm_style(gpu_ctx, shape):
     L = _lib()
     rng = np.random.default_rng(sum(shape))
