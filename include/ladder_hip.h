@@ -885,6 +885,35 @@ int ladder_kmeans_assign(const float* X, int N, int K, int R, int it, const doub
 int ladder_kmeans_update(const float* X, int N, int K, int R, const int* labels, double* state, double tol, int max_iter, int it, void* ws,
                          size_t ws_bytes, ladder_stream_t stream);
 
+/* ---------------------------------------------------------------- N20: the variational mixture fit on a WIDE representation (csrc/vbgmm.hip, vbwide_*)
+ * sklearn.mixture.BayesianGaussianMixture(covariance_type="full") -- the fit of N13 -- in float64 on fp32 samples X [N,R] for 1 <= K <= 64 and
+ * 1 <= R <= 64 (codes/vbgmm.py sends 8 < R <= 64 here; ladder_vbgmm_* keep R <= 8), on v_mfma_f64_16x16x4_f64 like N18.  Same protocol, argument
+ * conventions and status codes as ladder_vbgmm_shard_*: per variational iteration `it` (0 = the M-step on the k-means labels, then 1 .. max_iter)
+ *     ladder_vbgmm_wide_estep(...)  ->  stats [ladder_vbgmm_wide_stats_doubles] = sum r log r | n_k [K] | sum r x~ [K,R] | sum r x~ x~^T [K,R,R]
+ *     all-reduce(stats, SUM) over the data-parallel ranks (caller)
+ *     ladder_vbgmm_wide_mstep(...)  ->  M-step from the global statistics, lower bound, convergence test into `state`; at the end of the fit
+ *                                       _set_parameters and the fp32 feed (weights [K], means [K,R], covs [K,R,R])
+ * with x~ = x - c, c = fp32 rounding of the global mean.  moments (ladder_vbgmm_wide_moments_doubles doubles) = sum_n x_n [R] | N | sum_n x~ x~^T [R,R]:
+ * ladder_vbgmm_wide_moments(pass = 0) fills the first R + 1 for the local samples, the caller all-reduces THEM; pass = 1 fills the second moments
+ * about the shift they define, the caller all-reduces those -- once per fit.  mean_prior_ and covariance_prior_ come from them.
+ *   state: ladder_vbgmm_wide_state_doubles doubles, caller-owned, zero-filled before a cold fit, kept for a warm start:
+ *          the layout of ladder_vbgmm_state_doubles from the front (wa | wb | mean_prec | dof | means | cov | prec_chol), then the E-step constants [K],
+ *          the factorisation status [K], and lower_bound_, n_iter_, converged_ (-1: ill-defined empirical covariance), done.
+ *   ws >= ladder_vbgmm_wide_workspace_bytes(N_local, K, R): responsibilities [N,K] float64 | per-slice sums | per-split partial statistics.
+ * No atomics, one fixed order for every sum; every kernel is a no-op once state[-1] != 0.  Size queries return 0 for K < 1 or R < 1.
+ * LADDER_E_SHAPE (nothing launched) for K or R outside 1 .. 64, N < 1, a prior type other than 0 / 1, pass other than 0 / 1 or a NULL array;
+ * LADDER_E_ALIGN for double arrays off 8 bytes; LADDER_E_WORKSPACE for a workspace shorter than the query's answer. */
+size_t ladder_vbgmm_wide_state_doubles(int K, int R);
+size_t ladder_vbgmm_wide_stats_doubles(int K, int R);
+size_t ladder_vbgmm_wide_moments_doubles(int R);
+size_t ladder_vbgmm_wide_workspace_bytes(int N, int K, int R);
+int ladder_vbgmm_wide_moments(const float* X, int N, int R, double* moments, int pass, ladder_stream_t stream);
+int ladder_vbgmm_wide_estep(const float* X, int N, int K, int R, const int* labels, const double* state, int prior_type, const double* moments,
+                            double* stats, void* ws, size_t ws_bytes, ladder_stream_t stream);
+int ladder_vbgmm_wide_mstep(const double* stats, const double* moments, int K, int R, double* state, int prior_type, double wc_prior,
+                            double mean_prec_prior, double reg_covar, double tol, int max_iter, int it, float* weights, float* means, float* covs,
+                            ladder_stream_t stream);
+
 /* ---------------------------------------------------------------- helpers */
 /* HOST function (no device work): CRC-32C (Castagnoli) of host memory, crc = 0 to start, chainable.  Used by the
  * tf.train.Saver checkpoint-v2 reader/writer (codes/base.py:37-85: saver_ae / saver_prior) for block and tensor checksums. */

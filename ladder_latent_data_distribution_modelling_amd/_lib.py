@@ -127,6 +127,13 @@ PROTOTYPES = {
     "ladder_kmeans_set_centres": (_i, [_p, _i, _i, _i, _p, _p, _p, _z, _p]),
     "ladder_kmeans_assign": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _z, _p]),
     "ladder_kmeans_update": (_i, [_p, _i, _i, _i, _p, _p, _d, _i, _i, _p, _z, _p]),
+    "ladder_vbgmm_wide_state_doubles": (_z, [_i, _i]),
+    "ladder_vbgmm_wide_stats_doubles": (_z, [_i, _i]),
+    "ladder_vbgmm_wide_moments_doubles": (_z, [_i]),
+    "ladder_vbgmm_wide_workspace_bytes": (_z, [_i, _i, _i]),
+    "ladder_vbgmm_wide_moments": (_i, [_p, _i, _i, _p, _i, _p]),
+    "ladder_vbgmm_wide_estep": (_i, [_p, _i, _i, _i, _p, _p, _i, _p, _p, _p, _z, _p]),
+    "ladder_vbgmm_wide_mstep": (_i, [_p, _p, _i, _i, _p, _i, _d, _d, _d, _d, _i, _i, _p, _p, _p, _p]),
     "ladder_axpy": (_i, [_p, _p, _z, _f, _i, _p]),
     "ladder_filter_pack_split_bytes": (_z, [_i, _i, _i, _i]),
     "ladder_filter_pack_split": (_i, [_p, _p, _i, _i, _i, _i, _i, _p]),

@@ -36,8 +36,8 @@ class BaseModel:
         attach_handles(self)          # graph-tensor attribute surface for `sess.run(fetches, feed_dict)` (codes/session.py)
 
     # codes/base.py:88-106 -- the producer of (prior_weight, prior_mean, prior_cov).  config["gm_fit_backend"]: "hip" (default)
-    # runs the variational fit on the device (codes/vbgmm.py -> csrc/vbgmm.hip, sklearn-parity tested); "sklearn" keeps the
-    # reference's host object.  config["kmeans_backend"]: "sklearn" (default) labels a cold device fit with sklearn's k-means on the host, "hip" with
+    # runs the variational fit on the device (codes/vbgmm.py -> csrc/vbgmm.hip, sklearn-parity tested; representation_size up to 64: past 8
+    # the float64 MFMA kernels, picked by the fit itself); "sklearn" keeps the reference's host object.  config["kmeans_backend"]: "sklearn" (default) labels a cold device fit with sklearn's k-means on the host, "hip" with
     # the same algorithm on the device (codes/kmeans.py); it has no effect on the host objects.
     def define_GM_prior(self):
         self.GM_prior_training = None

@@ -8,6 +8,12 @@ uses (covariance_type='full'; dirichlet_distribution for the per-epoch "fast" fi
 sklearn.cluster.KMeans on the host (exactly the call BaseMixture._initialize_parameters makes) with kmeans_backend="sklearn", the
 default, and the same algorithm on the device with kmeans_backend="hip" (codes/kmeans.py: the same labels); either way a fit with the
 same `random_state` reproduces sklearn's to float64 round-off (tests/test_gpu_vbgmm.py, tests/test_gpu_kmeans.py).
+
+Width of the representation: R <= 8 runs the thread-per-sample kernels (`ladder_vbgmm_fit` below SLICED_FIT_MIN_SAMPLES samples,
+`ladder_vbgmm_shard_*` from there on and for sharded fits); 8 < R <= 64 runs `ladder_vbgmm_wide_*` for every N -- the E-step's whitening
+and the statistics on the float64 MFMA, the passes the EM fit of codes/emgmm.py uses (csrc/fit_mfma.h) -- with the same protocol, state
+front and fitted attributes (tests/test_gpu_vbgmm_wide.py).  1 <= K <= 64 for both.  The fit is the only part of the prior "ours" with
+this limit alone: the engine's wide mixture term also needs R % 4 == 0, and interpolation along shortest likely paths stays at R <= 8.
 """
 import numpy as np
 import torch
@@ -19,6 +25,9 @@ from . import mixture_fit as MF
 # from this many samples on, fit() runs one E-step launch over 256-sample slices (one workgroup each) + one M-step launch per variational
 # iteration instead of the single persistent workgroup: 3.8 ms -> ~30 us per iteration at the 20 096 samples of the accurate fit
 SLICED_FIT_MIN_SAMPLES = 1024
+# past this width the fit runs the MFMA kernels (ladder_vbgmm_wide_*) for every N; the persistent one-workgroup kernel stays R <= NARROW_MAX_R
+NARROW_MAX_R = 8
+WIDE_MAX_R = 64
 
 
 class DeviceBayesianGaussianMixture:
@@ -53,7 +62,7 @@ class DeviceBayesianGaussianMixture:
         Xd = MF.device_samples(X, self.device)
         N, R = Xd.shape
         MF.check_sample_count(N, K)
-        if N >= SLICED_FIT_MIN_SAMPLES:
+        if R > NARROW_MAX_R or N >= SLICED_FIT_MIN_SAMPLES:
             return self.fit_sharded(Xd, MF.OneRank(), check_every=16)
         ptype, wc, mp = self._prior_args()
         ws = torch.empty(L.query("ladder_vbgmm_workspace_bytes", N, K), dtype=torch.uint8, device=self.device)
@@ -82,32 +91,47 @@ class DeviceBayesianGaussianMixture:
         1 + K + K R + K R^2 doubles, M-step + lower bound + convergence test (one launch, identical on every rank).  The `done` flag
         lives in device memory and is read every `check_every` iterations; iterations enqueued past the end are no-ops, so the result
         does not depend on `check_every`.  A cold start takes its k-means labels from rank 0 (sklearn.cluster.KMeans on the gathered
-        samples, as BaseMixture._initialize_parameters does) -- once; warm starts exchange statistics only."""
+        samples, as BaseMixture._initialize_parameters does) -- once; warm starts exchange statistics only.
+        R > 8 picks the ladder_vbgmm_wide_* family: same loop, the data-derived priors from two small all-reduces ([sum x | N], then the second
+        moments about the shift that defines)."""
         K = self.n_components
         Xd = MF.device_samples(X_local, self.device)
         Nl, R = Xd.shape
+        if R > WIDE_MAX_R:
+            raise ValueError("the HIP mixture fit takes a representation of at most %d dimensions, got %d" % (WIDE_MAX_R, R))
+        wide = R > NARROW_MAX_R
+        fam = "ladder_vbgmm_wide_" if wide else "ladder_vbgmm_shard_"
         ptype, wc, mp = self._prior_args()
         st = torch.cuda.current_stream(self.device).cuda_stream
         f64 = lambda n: torch.zeros(n, dtype=torch.float64, device=self.device)
-        mom = f64(L.query("ladder_vbgmm_shard_moments_doubles", R))
-        L.call("ladder_vbgmm_shard_moments", Xd.data_ptr(), Nl, R, mom.data_ptr(), st)
-        comm.allreduce_(mom)
-        n_glob = torch.full((1,), float(Nl), dtype=torch.float64, device=self.device)
-        comm.allreduce_(n_glob)
+        mom = f64(L.query(fam + "moments_doubles", R))
+        if wide:
+            L.call(fam + "moments", Xd.data_ptr(), Nl, R, mom.data_ptr(), 0, st)
+            comm.allreduce_(mom[:R + 1])                                       # [ sum x | N ]: the shift, mean_prior_ and the global count
+            n_glob = mom[R:R + 1]
+        else:
+            L.call(fam + "moments", Xd.data_ptr(), Nl, R, mom.data_ptr(), st)
+            comm.allreduce_(mom)
+            n_glob = torch.full((1,), float(Nl), dtype=torch.float64, device=self.device)
+            comm.allreduce_(n_glob)
         MF.check_sample_count(int(n_glob.item()), K)                           # sklearn's check, on the GLOBAL sample count (ADVICE r3)
-        stats = f64(L.query("ladder_vbgmm_shard_stats_doubles", K, R))
-        ws = torch.empty(L.query("ladder_vbgmm_shard_workspace_bytes", Nl, K, R), dtype=torch.uint8, device=self.device)
+        if wide:
+            L.call(fam + "moments", Xd.data_ptr(), Nl, R, mom.data_ptr(), 1, st)
+            comm.allreduce_(mom[R + 1:])                                       # sum x~ x~^T about that shift: covariance_prior_
+        stats = f64(L.query(fam + "stats_doubles", K, R))
+        ws = torch.empty(L.query(fam + "workspace_bytes", Nl, K, R), dtype=torch.uint8, device=self.device)
         do_init, rs, n_fits = MF.fit_plan(self)
         lib = L.load()
-        estep_fn, mstep_fn = lib.ladder_vbgmm_shard_estep, lib.ladder_vbgmm_shard_mstep
+        estep_fn, mstep_fn = getattr(lib, fam + "estep"), getattr(lib, fam + "mstep")
+        n_state = L.query("ladder_vbgmm_wide_state_doubles" if wide else "ladder_vbgmm_state_doubles", K, R)
 
         def one_fit():
-            state = f64(L.query("ladder_vbgmm_state_doubles", K, R)) if do_init else self._state
+            state = f64(n_state) if do_init else self._state
             state[MF.FIT_CONVERGED:] = 0.0
             labels = self._initial_labels(Xd, comm, rs) if do_init else None   # rank 0's k-means, once; warm starts exchange statistics only
             w, m, c = MF.feed_tensors(K, R, self.device)
             # (the argument lists are constant over the iterations but for `labels` / `it`: bound once, the loop is two foreign calls)
-            e_tail = (state.data_ptr(), ptype, stats.data_ptr(), ws.data_ptr(), ws.numel(), st)
+            e_tail = (state.data_ptr(), ptype) + ((mom.data_ptr(),) if wide else ()) + (stats.data_ptr(), ws.data_ptr(), ws.numel(), st)
             m_head = (stats.data_ptr(), mom.data_ptr(), K, R, state.data_ptr(), ptype, wc, mp, float(self.reg_covar), float(self.tol), self.max_iter)
             m_tail = (w.data_ptr(), m.data_ptr(), c.data_ptr(), st)
             xp = Xd.data_ptr()

@@ -22,18 +22,11 @@
 // state (doubles): weights [K] | means [K,R] | covariances [K,R,R] | precisions_cholesky [K,R,R] | log_det [K] | component status [K] |
 //                  the tail of csrc/fit_util.h: lower_bound_, n_iter_, converged_, done
 //
-// Operand lane maps of v_mfma_f64_16x16x4_f64: head of csrc/fid.hip (A [m = lane & 15][k = lane >> 4], B [k][n = lane & 15],
-// C/D reg r: row (lane >> 4) + 4 r, col lane & 15).
-#include "fit_util.h"
+// The MFMA passes -- the whitening quadratic form, the statistics and their reduction, the factorisation -- are in csrc/fit_mfma.h, shared with
+// the wide variational fit of csrc/vbgmm.hip.
+#include "fit_mfma.h"
 
 namespace {
-
-typedef double double4_t __attribute__((ext_vector_type(4)));
-
-constexpr int EM_MAXR = 64, EM_MAXK = 64;
-constexpr int EM_SLICE = 64;            // samples per E-step workgroup: 4 wavefronts x 16 MFMA rows
-constexpr int EM_LDP = 80;              // LDS row pitch of the staged P_k in doubles: the four k-rows of one B operand fall into different bank halves
-constexpr int EM_LDC = 65;              // LDS row pitch of the M-step's factorisation (odd: a thread per row or per column walks distinct banks)
 
 struct EmState {
   double *w, *means, *cov, *pchol, *logdet, *cstat, *tail;
@@ -49,11 +42,6 @@ struct EmState {
 };
 
 __host__ __device__ inline size_t em_state_doubles(int K, int R) { return (size_t)K * (3 + R + 2 * (size_t)R * R) + 4; }
-__host__ __device__ inline size_t em_stats_doubles(int K, int R) { return 1 + (size_t)K * (1 + R + (size_t)R * R); }
-inline int em_slices(int N) { return (N + EM_SLICE - 1) / EM_SLICE; }
-
-// moments = [ sum_n x_n [R] | N ], all-reduced by the caller: the shift is the GLOBAL mean rounded to fp32, the same on every rank
-__device__ __forceinline__ double em_shift(const double* mom, int R, int j) { return (double)(float)(mom[j] / mom[R]); }
 
 // ------------------------------------------------------------------------------------------------ column sums for the shift
 // One workgroup per column (column_sum_256: thread-strided partial sums, the shuffle tree, then the four wavefronts in order).
@@ -73,7 +61,7 @@ __global__ __launch_bounds__(256) void emgmm_estep_kernel(const float* __restric
   EmState S(const_cast<double*>(state), K, R);
   if (S.tail[FIT_DONE] != 0.0) return;                             // the fit is over: iterations enqueued past the end are no-ops
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, m = lane & 15, kq = lane >> 4;
-  const int n0 = blockIdx.x * EM_SLICE, rows = min(EM_SLICE, N - n0);
+  const int n0 = blockIdx.x * FIT_SLICE, rows = min(FIT_SLICE, N - n0);
   if (labels != nullptr) {                                         // iteration 0: hard labels, through the same statistics kernels
     for (int i = tid; i < rows * K; i += 256) {
       const int r = i / K, k = i - r * K;
@@ -82,50 +70,20 @@ __global__ __launch_bounds__(256) void emgmm_estep_kernel(const float* __restric
     if (tid == 0) lpn_part[blockIdx.x] = 0.0;
     return;
   }
-  __shared__ double s_P[EM_MAXR * EM_LDP], s_mu[EM_MAXR], s_ld[EM_MAXK], s_lw[EM_MAXK];
+  __shared__ double s_P[FIT_MAXR * FIT_LDP], s_mu[FIT_MAXR], s_ld[FIT_MAXK], s_lw[FIT_MAXK];
   const int nb = (R + 15) / 16, Rp = nb * 16, nsteps = (R + 3) / 4;
-  const int row = wave * 16 + m;
-  const bool rv = row < rows;
-  const float* xr = X + (size_t)(n0 + (rv ? row : 0)) * R;         // (row n0 exists: never dereferenced unless rv)
   double xa[16];                                                   // this lane's A operands: x[row][4 s + kq], zero past R
-#pragma unroll
-  for (int s = 0; s < 16; ++s) {
-    const int i = 4 * s + kq;
-    xa[s] = (rv && i < R) ? (double)xr[i] : 0.0;
-  }
+  fit_slice_rows(X, n0, rows, R, wave * 16 + m, kq, xa);
   if (tid < K) {
     s_ld[tid] = S.logdet[tid];
     s_lw[tid] = log(S.w[tid]);
   }
   for (int k = 0; k < K; ++k) {
     __syncthreads();                                               // (the previous component's operands are no longer read)
-    const double* P = S.pchol + (size_t)k * R * R;
-    for (int idx = tid; idx < Rp * Rp; idx += 256) {
-      const int i = idx / Rp, j = idx - i * Rp;
-      s_P[i * EM_LDP + j] = (i < R && j < R) ? P[i * R + j] : 0.0;
-    }
-    if (tid < EM_MAXR) s_mu[tid] = tid < R ? S.means[k * R + tid] : 0.0;
+    fit_stage_component(S.pchol + (size_t)k * R * R, S.means + k * R, R, Rp, s_P, s_mu, tid);
     __syncthreads();
-    double q4[4] = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-    for (int jb = 0; jb < 4; ++jb) {
-      if (jb < nb) {                                               // (uniform: every lane reaches every MFMA)
-        double4_t acc = double4_t{0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-        for (int s = 0; s < 4 * (jb + 1); ++s) {                   // P is upper triangular: rows past 16 jb + 15 of this column block are zero
-          if (s < nsteps) {
-            const int i = 4 * s + kq;
-            acc = __builtin_amdgcn_mfma_f64_16x16x4f64(xa[s] - s_mu[i], s_P[i * EM_LDP + 16 * jb + m], acc, 0, 0, 0);
-          }
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) q4[r] += acc[r] * acc[r];
-      }
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-#pragma unroll
-      for (int o = 1; o < 16; o <<= 1) q4[r] += __shfl_xor(q4[r], o, 64);    // over the 16 columns of the lane group: the same bits in every lane
+    double q4[4];
+    fit_whiten_sq(xa, s_mu, s_P, nb, nsteps, m, kq, q4);
     if (m == 0) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
@@ -152,134 +110,31 @@ __global__ __launch_bounds__(256) void emgmm_estep_kernel(const float* __restric
 }
 
 // ------------------------------------------------------------------------------------------------ statistics
-// blockIdx.x = component, blockIdx.y = row split.  Wavefront w owns rows 16 w .. 16 w + 15 of the R x R moment: the column blocks q >= w as MFMA
-// accumulators, plus one block whose B operand is the unit column e_0, which collects sum r x~ in its column 0.  Operands come straight from global memory.
+// blockIdx.x = component, blockIdx.y = row split: fit_stats_pass, then fit_stats_reduce with the slices' log_prob_norm sums as element 0.
 __global__ __launch_bounds__(256) void emgmm_stats_kernel(const float* __restrict__ X, const double* __restrict__ resp, const double* __restrict__ state,
                                                           const double* __restrict__ mom, int N, int K, int R, int rows, double* __restrict__ part) {
   EmState S(const_cast<double*>(state), K, R);
   if (S.tail[FIT_DONE] != 0.0) return;
-  const int k = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, m = lane & 15, kq = lane >> 4;
-  const int nb = (R + 15) / 16;
-  if (wave >= nb) return;                                          // (whole wavefronts; no barrier in this kernel)
-  const int ia = wave * 16 + m;
-  const bool va = ia < R;
-  const double ca = va ? em_shift(mom, R, ia) : 0.0;
-  int jb[4];
-  bool vb[4];
-  double cb[4];
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    jb[q] = 16 * q + m;
-    vb[q] = jb[q] < R;
-    cb[q] = vb[q] ? em_shift(mom, R, jb[q]) : 0.0;
-  }
-  const double e0 = (m == 0) ? 1.0 : 0.0;
-  const int r0 = blockIdx.y * rows, r1 = min(N, r0 + rows);
-  double4_t acc[4], acc1 = double4_t{0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-  for (int q = 0; q < 4; ++q) acc[q] = double4_t{0.0, 0.0, 0.0, 0.0};
-  double nk = 0.0;
-  for (int r = r0; r < r1; r += 4) {                               // (uniform trip count)
-    const int row = r + kq;
-    const bool ok = row < r1;
-    const float* xr = X + (size_t)(ok ? row : r0) * R;
-    const double rr = ok ? resp[(size_t)row * K + k] : 0.0;
-    nk += rr;
-    const double a = (ok && va) ? rr * ((double)xr[ia] - ca) : 0.0;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      if (q >= wave && q < nb) {
-        const double b = (ok && vb[q]) ? (double)xr[jb[q]] - cb[q] : 0.0;
-        acc[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc[q], 0, 0, 0);
-      }
-    }
-    acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(a, e0, acc1, 0, 0, 0);
-  }
-  double* out = part + (size_t)blockIdx.y * em_stats_doubles(K, R);
-  double* p_nk = out + 1;
-  double* p_x = p_nk + K + (size_t)k * R;
-  double* p_xx = out + 1 + K + (size_t)K * R + (size_t)k * R * R;
-  if (wave == 0) {                                                 // n_k: the rows r0 + kq + 4 t of lane group kq, then the four groups in order
-    const double g0 = __shfl(nk, 0, 64), g1 = __shfl(nk, 16, 64), g2 = __shfl(nk, 32, 64), g3 = __shfl(nk, 48, 64);
-    if (lane == 0) p_nk[k] = ((g0 + g1) + g2) + g3;
-  }
-#pragma unroll
-  for (int rg = 0; rg < 4; ++rg) {
-    const int i = wave * 16 + kq + 4 * rg;
-    if (i >= R) continue;
-    if (m == 0) p_x[i] = acc1[rg];
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-      if (q >= wave && q < nb && vb[q]) p_xx[(size_t)i * R + jb[q]] = acc[q][rg];
-  }
+  fit_stats_pass(X, resp, mom, N, K, R, rows, part);
 }
 
-// stats[e] = sum over the splits in index order; of the second moments only [i][j], i <= j, was computed: the lower triangle reads its mirror, so the
-// moment is exactly symmetric.  Element 0 = the slices' log_prob_norm sums in slice order.
 __global__ __launch_bounds__(256) void emgmm_reduce_kernel(const double* __restrict__ part, const double* __restrict__ lpn_part, const double* __restrict__ state,
                                                            int K, int R, int nsplit, int nslices, double* __restrict__ stats) {
   EmState S(const_cast<double*>(state), K, R);
   if (S.tail[FIT_DONE] != 0.0) return;
-  const size_t n = em_stats_doubles(K, R), e = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (e >= n) return;
-  double a = 0.0;
-  if (e == 0) {
-    for (int g = 0; g < nslices; ++g) a += lpn_part[g];
-  } else {
-    size_t src = e;
-    const size_t xx0 = 1 + (size_t)K + (size_t)K * R;
-    if (e >= xx0) {
-      const size_t q = e - xx0, kk = q / ((size_t)R * R), ij = q - kk * R * R, i = ij / R, j = ij - i * R;
-      if (j < i) src = xx0 + kk * R * R + j * R + i;
-    }
-    for (int s = 0; s < nsplit; ++s) a += part[(size_t)s * n + src];
-  }
-  stats[e] = a;
+  fit_stats_reduce(part, lpn_part, K, R, nsplit, nslices, stats);
 }
 
 // ------------------------------------------------------------------------------------------------ M-step
-// _compute_precision_cholesky for one component, by ONE wavefront (64 threads): A [R][EM_LDC] in LDS holds the covariance on entry.  Left-looking
-// Cholesky, thread i = row i; then the triangular inverse, thread c = column c of L^-1, kept in the strict upper triangle of A (A[c][i] = L^-1[i][c]) beside L.
+// _compute_precision_cholesky for one component, by ONE wavefront (64 threads): A [R][FIT_LDC] in LDS holds the covariance on entry (fit_chol_inverse).
 // Writes precisions_cholesky_[k] (upper triangular), its log-determinant and the component status (-1: a non-positive pivot).
 __device__ void em_prepare_component(double* A, int R, int k, EmState& S, int tid) {
-  __shared__ double s_d;
-  __shared__ int s_bad;
-  if (tid == 0) s_bad = 0;
-  for (int j = 0; j < R; ++j) {
-    double v = 0.0;
-    if (tid >= j && tid < R) {
-      v = A[tid * EM_LDC + j];
-      for (int p = 0; p < j; ++p) v -= A[tid * EM_LDC + p] * A[j * EM_LDC + p];
-      if (tid == j) s_d = v;
-    }
-    __syncthreads();
-    double d = s_d;
-    if (!(d > 0.0)) {                                              // sklearn: LinAlgError -> ValueError("... ill-defined empirical covariance ...")
-      if (tid == j) s_bad = 1;
-      d = 1.0;
-    }
-    const double ljj = sqrt(d);
-    if (tid == j) A[j * EM_LDC + j] = ljj;
-    else if (tid > j && tid < R) A[tid * EM_LDC + j] = v / ljj;
-    __syncthreads();
-  }
-  double* Pk = S.pchol + (size_t)k * R * R;
-  if (tid < R) {
-    const int c = tid;
-    const double xc = 1.0 / A[c * EM_LDC + c];
-    for (int i = c + 1; i < R; ++i) {
-      double v = -A[i * EM_LDC + c] * xc;
-      for (int p = c + 1; p < i; ++p) v -= A[i * EM_LDC + p] * A[c * EM_LDC + p];
-      A[c * EM_LDC + i] = v / A[i * EM_LDC + i];
-    }
-    for (int i = 0; i < R; ++i) Pk[c * R + i] = (i < c) ? 0.0 : (i == c ? xc : A[c * EM_LDC + i]);
-  }
-  __syncthreads();
+  const bool bad = fit_chol_inverse(A, R, S.pchol + (size_t)k * R * R, tid);
   if (tid == 0) {
     double ld = 0.0;
-    for (int j = 0; j < R; ++j) ld += log(1.0 / A[j * EM_LDC + j]);
+    for (int j = 0; j < R; ++j) ld += log(1.0 / A[j * FIT_LDC + j]);
     S.logdet[k] = ld;
-    S.cstat[k] = s_bad ? -1.0 : 0.0;
+    S.cstat[k] = bad ? -1.0 : 0.0;
   }
 }
 
@@ -289,7 +144,7 @@ __global__ __launch_bounds__(64) void emgmm_mstep_kernel(const double* __restric
   EmState S(state, K, R);
   if (S.tail[FIT_DONE] != 0.0) return;
   const int k = blockIdx.x, tid = threadIdx.x;
-  __shared__ double s_A[EM_MAXR * EM_LDC], s_s1[EM_MAXR], s_dm[EM_MAXR];
+  __shared__ double s_A[FIT_MAXR * FIT_LDC], s_s1[FIT_MAXR], s_dm[FIT_MAXR];
   const double* st_nk = stats + 1;
   const double* st_x = st_nk + K + (size_t)k * R;
   const double* st_xx = stats + 1 + K + (size_t)K * R + (size_t)k * R * R;
@@ -307,7 +162,7 @@ __global__ __launch_bounds__(64) void emgmm_mstep_kernel(const double* __restric
     w_out[k] = (float)w;
   }
   if (tid < R) {
-    const double c = em_shift(mom, R, tid), s1 = st_x[tid];
+    const double c = fit_shift(mom, R, tid), s1 = st_x[tid];
     const double mean = (s1 + c * nk_raw) / nk;                    // = sum r x / nk
     s_s1[tid] = s1;
     s_dm[tid] = mean - c;
@@ -323,8 +178,8 @@ __global__ __launch_bounds__(64) void emgmm_mstep_kernel(const double* __restric
     if (j < i) continue;
     double v = st_xx[e] - (s_s1[i] * s_dm[j] + s_dm[i] * s_s1[j]) + nk_raw * s_dm[i] * s_dm[j];
     v = v / nk + (i == j ? reg_covar : 0.0);
-    s_A[i * EM_LDC + j] = v;
-    s_A[j * EM_LDC + i] = v;
+    s_A[i * FIT_LDC + j] = v;
+    s_A[j * FIT_LDC + i] = v;
     C[i * R + j] = v;
     C[j * R + i] = v;
     Cf[i * R + j] = (float)v;
@@ -338,9 +193,9 @@ __global__ __launch_bounds__(64) void emgmm_mstep_kernel(const double* __restric
 __global__ __launch_bounds__(64) void emgmm_prepare_kernel(double* state, int K, int R) {
   EmState S(state, K, R);
   const int k = blockIdx.x, tid = threadIdx.x;
-  __shared__ double s_A[EM_MAXR * EM_LDC];
+  __shared__ double s_A[FIT_MAXR * FIT_LDC];
   const double* C = S.cov + (size_t)k * R * R;
-  for (int e = tid; e < R * R; e += 64) s_A[(e / R) * EM_LDC + (e % R)] = C[e];
+  for (int e = tid; e < R * R; e += 64) s_A[(e / R) * FIT_LDC + (e % R)] = C[e];
   __syncthreads();
   em_prepare_component(s_A, R, k, S, tid);
 }
@@ -383,17 +238,17 @@ __global__ void emgmm_finish_kernel(const double* __restrict__ stats, const doub
 extern "C" {
 
 size_t ladder_emgmm_state_doubles(int K, int R) { return (K < 1 || R < 1) ? 0 : em_state_doubles(K, R); }
-size_t ladder_emgmm_stats_doubles(int K, int R) { return (K < 1 || R < 1) ? 0 : em_stats_doubles(K, R); }
+size_t ladder_emgmm_stats_doubles(int K, int R) { return (K < 1 || R < 1) ? 0 : fit_stats_doubles(K, R); }
 size_t ladder_emgmm_shift_doubles(int R) { return R < 1 ? 0 : (size_t)R + 1; }
 
 size_t ladder_emgmm_workspace_bytes(int N, int K, int R) {
   if (N < 1 || K < 1 || R < 1) return 0;
   // responsibilities [N, K] | per-slice log_prob_norm sums | per-split partial statistics
-  return ((size_t)N * K + (size_t)em_slices(N) + (size_t)fit_split(N).nsplit * em_stats_doubles(K, R)) * sizeof(double);
+  return ((size_t)N * K + (size_t)fit_slices(N) + (size_t)fit_split(N).nsplit * fit_stats_doubles(K, R)) * sizeof(double);
 }
 
 int ladder_emgmm_shift(const float* X, int N, int R, double* moments, ladder_stream_t stream) {
-  if (X == nullptr || moments == nullptr || N < 1 || R < 1 || R > EM_MAXR) return LADDER_E_SHAPE;
+  if (X == nullptr || moments == nullptr || N < 1 || R < 1 || R > FIT_MAXR) return LADDER_E_SHAPE;
   if (fit_misaligned(moments)) return LADDER_E_ALIGN;
   hipLaunchKernelGGL(emgmm_shift_kernel, dim3(R), dim3(256), 0, stream, X, N, R, moments);
   LADDER_CHECK_LAUNCH();
@@ -402,13 +257,13 @@ int ladder_emgmm_shift(const float* X, int N, int R, double* moments, ladder_str
 
 int ladder_emgmm_estep(const float* X, int N, int K, int R, const int* labels, const double* state, const double* moments, double* stats, void* ws,
                        size_t ws_bytes, ladder_stream_t stream) {
-  if (X == nullptr || state == nullptr || moments == nullptr || stats == nullptr || N < 1 || K < 1 || K > EM_MAXK || R < 1 || R > EM_MAXR)
+  if (X == nullptr || state == nullptr || moments == nullptr || stats == nullptr || N < 1 || K < 1 || K > FIT_MAXK || R < 1 || R > FIT_MAXR)
     return LADDER_E_SHAPE;
   if (fit_misaligned(state) || fit_misaligned(moments) || fit_misaligned(stats) || fit_misaligned(ws)) return LADDER_E_ALIGN;
   if (ws == nullptr || ws_bytes < ladder_emgmm_workspace_bytes(N, K, R)) return LADDER_E_WORKSPACE;
   const FitSplit sp = fit_split(N);
-  const int G = em_slices(N);
-  const size_t n = em_stats_doubles(K, R);
+  const int G = fit_slices(N);
+  const size_t n = fit_stats_doubles(K, R);
   double* resp = static_cast<double*>(ws);
   double* lpn_part = resp + (size_t)N * K;
   double* part = lpn_part + G;
@@ -424,8 +279,8 @@ int ladder_emgmm_estep(const float* X, int N, int K, int R, const int* labels, c
 
 int ladder_emgmm_mstep(const double* stats, const double* moments, int K, int R, double* state, double reg_covar, double tol, int max_iter, int it,
                        float* weights, float* means, float* covs, ladder_stream_t stream) {
-  if (stats == nullptr || moments == nullptr || state == nullptr || weights == nullptr || means == nullptr || covs == nullptr || K < 1 || K > EM_MAXK ||
-      R < 1 || R > EM_MAXR || max_iter < 0 || it < 0)
+  if (stats == nullptr || moments == nullptr || state == nullptr || weights == nullptr || means == nullptr || covs == nullptr || K < 1 || K > FIT_MAXK ||
+      R < 1 || R > FIT_MAXR || max_iter < 0 || it < 0)
     return LADDER_E_SHAPE;
   if (fit_misaligned(stats) || fit_misaligned(moments) || fit_misaligned(state)) return LADDER_E_ALIGN;
   hipLaunchKernelGGL(emgmm_mstep_kernel, dim3(K), dim3(64), 0, stream, stats, moments, state, K, R, reg_covar, it, weights, means, covs);
@@ -436,7 +291,7 @@ int ladder_emgmm_mstep(const double* stats, const double* moments, int K, int R,
 }
 
 int ladder_emgmm_prepare(double* state, int K, int R, ladder_stream_t stream) {
-  if (state == nullptr || K < 1 || K > EM_MAXK || R < 1 || R > EM_MAXR) return LADDER_E_SHAPE;
+  if (state == nullptr || K < 1 || K > FIT_MAXK || R < 1 || R > FIT_MAXR) return LADDER_E_SHAPE;
   if (fit_misaligned(state)) return LADDER_E_ALIGN;
   hipLaunchKernelGGL(emgmm_prepare_kernel, dim3(K), dim3(64), 0, stream, state, K, R);
   LADDER_CHECK_LAUNCH();

@@ -4,9 +4,10 @@
 // weight_concentration_prior=0.1, warm_start=True).fit(t_samples)  (codes/base.py:93-99, 681-789).
 //
 // The problem is tiny and strictly sequential (N ~ 2e3..2e4 samples of R <= 8 dims, K <= 64 components, 10..1000 dependent E/M
-// iterations).  Arithmetic is float64 like sklearn's; every reduction has one fixed order, so a fit gives the same bits on every run
+// iterations; a representation of 9 .. 64 dims takes the vbwide_* kernels at the end of this file, on the float64 MFMA).  Arithmetic is float64 like sklearn's; every reduction has one fixed order, so a fit gives the same bits on every run
 // and on every rank.  Two paths call the SAME device functions (vb_*) for all that sklearn defines -- the one-hot start, the E-step, the
-// Dirichlet / Wishart update with its Cholesky and inverse, the lower bound, _set_parameters:
+// Dirichlet / Wishart update with its Cholesky and inverse, the lower bound, _set_parameters (the wide fit calls vb_digamma, vb_estep_constant,
+// vb_log_wishart_term, vb_lower_bound and vb_write_feed too, and takes its E-step, statistics and factorisation from csrc/fit_mfma.h):
 //   vbgmm_fit_kernel                   below 1 024 samples: ONE persistent workgroup of 16 wavefronts keeps the whole VB loop in one launch
 //   vbgmm_shard_{estep,mstep}_kernel   every other fit: an E-step launch over 256-sample slices + an M-step launch per iteration, the samples
 //                                      possibly sharded over the data-parallel ranks
@@ -15,7 +16,7 @@
 // The functions are forced-inline and restate sklearn 1.7's _bayesian_mixture.py / _gaussian_mixture.py (BSD-3) in sklearn's evaluation
 // order -- do not reorder a sum or merge (x - mu) P: -ffp-contract=fast fuses by what surrounds a statement.  tests/test_gpu_vbgmm.py
 // compares against sklearn itself through its public API.
-#include "fit_util.h"
+#include "fit_mfma.h"
 
 namespace {
 
@@ -40,11 +41,13 @@ __device__ double vb_digamma(double x) {
 }
 
 // state layout (doubles): wa[K] wb[K] mean_prec[K] dof[K] means[K*R] cov[K*R*R] prec_chol[K*R*R] | the four tail doubles of fit_util.h
+// The wide fit (R > 8, below) keeps `extra` = 2 more doubles per component before the tail: the E-step constants ck[K] and the
+// factorisation status cstat[K].
 struct VbState {
-  double *wa, *wb, *mprec, *dof, *means, *cov, *pchol, *tail;
-  __device__ VbState(double* s, int K, int R) {
+  double *wa, *wb, *mprec, *dof, *means, *cov, *pchol, *ck, *cstat, *tail;
+  __device__ VbState(double* s, int K, int R, int extra = 0) {
     wa = s; wb = wa + K; mprec = wb + K; dof = mprec + K; means = dof + K; cov = means + (size_t)K * R;
-    pchol = cov + (size_t)K * R * R; tail = pchol + (size_t)K * R * R;
+    pchol = cov + (size_t)K * R * R; ck = pchol + (size_t)K * R * R; cstat = ck + K; tail = ck + (size_t)extra * K;
   }
 };
 
@@ -52,6 +55,30 @@ struct VbState {
 // _initialize_parameters: one-hot responsibilities from the k-means labels
 __device__ __forceinline__ void vb_onehot(const int* __restrict__ labels, int N, int K, double* __restrict__ resp, int tid, int nthreads) {
   for (size_t i = tid; i < (size_t)N * K; i += nthreads) resp[i] = (labels[i / K] == (int)(i % K)) ? 1.0 : 0.0;
+}
+
+// What _estimate_log_prob + _estimate_log_weights give per component, all but the quadratic form: Pk = precisions_cholesky_[k] (global memory or an
+// LDS copy), dig_sum = digamma(sum_k wa) (dirichlet_distribution only).  s_stick, if given, holds digamma(wb_j) - digamma(wa_j + wb_j) per component:
+// the stick-breaking prefix adds the same terms in the same order either way.
+__device__ __forceinline__ double vb_estep_constant(int k, const double* Pk, const VbState& S, const VbCfg& c, double dig_sum,
+                                                    const double* s_stick = nullptr) {
+  const int R = c.R;
+  double log_det = 0.0, log_lambda = R * log(2.0);
+  for (int j = 0; j < R; ++j) {
+    log_det += log(Pk[j * R + j]);
+    log_lambda += vb_digamma(0.5 * (S.dof[k] - j));
+  }
+  double lw;
+  if (c.prior_type == 0) {
+    lw = vb_digamma(S.wa[k]) - dig_sum;
+  } else {            // stick breaking: digamma(a) - digamma(a+b) + sum_{j<k} (digamma(b_j) - digamma(a_j+b_j))
+    lw = vb_digamma(S.wa[k]) - vb_digamma(S.wa[k] + S.wb[k]);
+    if (s_stick != nullptr)
+      for (int j = 0; j < k; ++j) lw += s_stick[j];
+    else
+      for (int j = 0; j < k; ++j) lw += vb_digamma(S.wb[j]) - vb_digamma(S.wa[j] + S.wb[j]);
+  }
+  return -0.5 * R * log(2.0 * M_PI) + log_det - 0.5 * R * log(S.dof[k]) + 0.5 * (log_lambda - R / S.mprec[k]) + lw;
 }
 
 // The E-step on the N rows of X (_estimate_log_prob_resp): resp <- responsibilities; returns sum r log r in thread 0 (0 elsewhere).
@@ -67,22 +94,7 @@ __device__ __forceinline__ double vb_estep(const float* __restrict__ X, int N, c
   for (int i = tid; i < K * R; i += VB_THREADS) s_mu[i] = S.means[i];
   for (int i = tid; i < K * R * R; i += VB_THREADS) s_pc[i] = S.pchol[i];
   __syncthreads();
-  if (tid < K) {                                                  // s_ck[k]: what _estimate_log_prob + _estimate_log_weights give per component
-    const int k = tid;
-    double log_det = 0.0, log_lambda = R * log(2.0);
-    for (int j = 0; j < R; ++j) {
-      log_det += log(s_pc[(k * R + j) * R + j]);
-      log_lambda += vb_digamma(0.5 * (S.dof[k] - j));
-    }
-    double lw;
-    if (c.prior_type == 0) {
-      lw = vb_digamma(S.wa[k]) - s_scal[0];
-    } else {            // stick breaking: digamma(a) - digamma(a+b) + sum_{j<k} (digamma(b_j) - digamma(a_j+b_j))
-      lw = vb_digamma(S.wa[k]) - vb_digamma(S.wa[k] + S.wb[k]);
-      for (int j = 0; j < k; ++j) lw += vb_digamma(S.wb[j]) - vb_digamma(S.wa[j] + S.wb[j]);
-    }
-    s_ck[k] = -0.5 * R * log(2.0 * M_PI) + log_det - 0.5 * R * log(S.dof[k]) + 0.5 * (log_lambda - R / S.mprec[k]) + lw;
-  }
+  if (tid < K) s_ck[tid] = vb_estep_constant(tid, s_pc + (size_t)tid * R * R, S, c, s_scal[0]);
   __syncthreads();
   double ent = 0.0;
   for (int n = tid; n < N; n += VB_THREADS) {
@@ -178,19 +190,26 @@ __device__ __forceinline__ void vb_update_component(int k, const VbState& S, con
   }
 }
 
-// _compute_lower_bound (log-Wishart, log-norm-weight) from the updated state and this iteration's sum r log r.  One thread.
-__device__ __forceinline__ double vb_lower_bound(const VbState& S, const VbCfg& c, double entropy) {
+// Component k's term of _log_wishart_norm, as _compute_lower_bound sums it.
+__device__ __forceinline__ double vb_log_wishart_term(int k, const VbState& S, const VbCfg& c) {
+  const int R = c.R;
+  const double* Pk = S.pchol + (size_t)k * R * R;
+  double ld = 0.0, lg = 0.0;
+  for (int j = 0; j < R; ++j) {
+    ld += log(Pk[j * R + j]);
+    lg += lgamma(0.5 * (S.dof[k] - j));
+  }
+  ld -= 0.5 * R * log(S.dof[k]);
+  return -(S.dof[k] * ld + S.dof[k] * R * 0.5 * log(2.0) + lg);
+}
+
+// _compute_lower_bound (log-Wishart, log-norm-weight) from the updated state and this iteration's sum r log r.  One thread.  s_lw, if given,
+// holds vb_log_wishart_term per component (computed by a thread each): the sum over the components keeps its order.
+__device__ __forceinline__ double vb_lower_bound(const VbState& S, const VbCfg& c, double entropy, const double* s_lw = nullptr) {
   const int K = c.K, R = c.R;
   double log_wishart = 0.0, sum_log_mp = 0.0, log_norm_weight;
   for (int k = 0; k < K; ++k) {
-    const double* Pk = S.pchol + (size_t)k * R * R;
-    double ld = 0.0, lg = 0.0;
-    for (int j = 0; j < R; ++j) {
-      ld += log(Pk[j * R + j]);
-      lg += lgamma(0.5 * (S.dof[k] - j));
-    }
-    ld -= 0.5 * R * log(S.dof[k]);
-    log_wishart += -(S.dof[k] * ld + S.dof[k] * R * 0.5 * log(2.0) + lg);
+    log_wishart += s_lw != nullptr ? s_lw[k] : vb_log_wishart_term(k, S, c);
     sum_log_mp += log(S.mprec[k]);
   }
   if (c.prior_type == 0) {
@@ -451,6 +470,214 @@ __global__ __launch_bounds__(256) void vbgmm_shard_mstep_kernel(const double* __
   vb_write_feed(S, c, s_ck, w_out, m_out, c_out, tid, 256);
 }
 
+// ================================================================================================ the WIDE fit: 8 < R <= 64
+// The thread-per-sample E-step above keeps a sample in registers and every factor in LDS, which ends at R = 8.  Past it one variational iteration
+// keeps the protocol of the sharded fit -- E-step + local statistics / all-reduce / M-step + convergence test, every kernel a no-op once `done` is
+// set -- on the float64 MFMA passes of csrc/fit_mfma.h, which the EM fit (csrc/emgmm.hip) runs too:
+//   vbwide_estep_kernel    a workgroup owns 64 samples; per component the whitening quadratic form |(x - mean_k) P_k|^2, then w = ck[k] - q / 2 with
+//                          the constants the finish kernel left in the state; logsumexp, responsibilities, the slice's sum r log r
+//   vbwide_stats_kernel    n_k, sum r x~, sum r x~ x~^T about ONE shift c (the fp32-rounded global mean) over row splits; vbwide_reduce_kernel adds
+//                          the splits (and the slices' sum r log r) in index order: stats = [ sum r log r | n_k | sum r x~ | sum r x~ x~^T ]
+//   (all-reduce of stats, by the caller)
+//   vbwide_mstep_kernel    one workgroup per component: weight parameters, mean precision, mean, the Wishart covariance from the shifted moments
+//                          centred here, Cholesky factor and triangular inverse in LDS; a non-positive pivot is a status
+//   vbwide_finish_kernel   one workgroup: the next E-step's constants (vb_estep_constant), the lower bound, the convergence test, and at the end of
+//                          the fit _set_parameters + the fp32 feed
+// moments = [ sum x [R] | N | sum x~ x~^T [R,R] ]: the first R + 1 are all-reduced, then the second moments about the shift they define; from them
+// mean_prior_ = X.mean(0) and covariance_prior_ = cov(X.T) = (sum x~ x~^T - N d d^T) / (N - 1), d = mean_prior_ - c.
+constexpr int VBW_EXTRA = 2;             // ck[K] | cstat[K] between prec_chol and the tail
+
+__global__ __launch_bounds__(256) void vbwide_moments1_kernel(const float* __restrict__ X, int N, int R, double* __restrict__ mom) {
+  const int j = blockIdx.x, tid = threadIdx.x;
+  __shared__ double s_red[4];
+  const double a = column_sum_256(X, N, R, j, s_red, tid);
+  if (tid == 0) {
+    mom[j] = a;
+    if (j == 0) mom[R] = (double)N;
+  }
+}
+
+// grid (R, R): workgroup (j, i), i <= j, sums x~_i x~_j over the local samples and writes both mirrors
+__global__ __launch_bounds__(256) void vbwide_moments2_kernel(const float* __restrict__ X, int N, int R, double* mom) {
+  const int j = blockIdx.x, i = blockIdx.y, tid = threadIdx.x;
+  if (j < i) return;
+  __shared__ double s_red[4];
+  const double ci = fit_shift(mom, R, i), cj = fit_shift(mom, R, j);
+  double a = 0.0;
+  for (int n = tid; n < N; n += 256) a += ((double)X[(size_t)n * R + i] - ci) * ((double)X[(size_t)n * R + j] - cj);
+  a = block_sum_256(a, s_red, tid);
+  if (tid == 0) {
+    mom[R + 1 + i * R + j] = a;
+    mom[R + 1 + j * R + i] = a;
+  }
+}
+
+__global__ __launch_bounds__(256) void vbwide_estep_kernel(const float* __restrict__ X, const int* __restrict__ labels, const double* state, int N, int K,
+                                                           int R, double* resp, double* __restrict__ ent_part) {
+  VbState S(const_cast<double*>(state), K, R, VBW_EXTRA);
+  if (S.tail[FIT_DONE] != 0.0) return;                             // the fit is over: iterations enqueued past the end are no-ops
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, m = lane & 15, kq = lane >> 4;
+  const int n0 = blockIdx.x * FIT_SLICE, rows = min(FIT_SLICE, N - n0);
+  if (labels != nullptr) {                                         // iteration 0: _initialize_parameters' one-hot responsibilities
+    for (int i = tid; i < rows * K; i += 256) {
+      const int r = i / K, k = i - r * K;
+      resp[(size_t)(n0 + r) * K + k] = (labels[n0 + r] == k) ? 1.0 : 0.0;
+    }
+    if (tid == 0) ent_part[blockIdx.x] = 0.0;
+    return;
+  }
+  __shared__ double s_P[FIT_MAXR * FIT_LDP], s_mu[FIT_MAXR], s_ck[FIT_MAXK];
+  const int nb = (R + 15) / 16, Rp = nb * 16, nsteps = (R + 3) / 4;
+  double xa[16];
+  fit_slice_rows(X, n0, rows, R, wave * 16 + m, kq, xa);
+  if (tid < K) s_ck[tid] = S.ck[tid];
+  for (int k = 0; k < K; ++k) {
+    __syncthreads();                                               // (the previous component's operands are no longer read)
+    fit_stage_component(S.pchol + (size_t)k * R * R, S.means + k * R, R, Rp, s_P, s_mu, tid);
+    __syncthreads();
+    double q4[4];
+    fit_whiten_sq(xa, s_mu, s_P, nb, nsteps, m, kq, q4);
+    if (m == 0) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int rr = wave * 16 + kq + 4 * r;
+        if (rr < rows) resp[(size_t)(n0 + rr) * K + k] = s_ck[k] - 0.5 * q4[r];
+      }
+    }
+  }
+  __syncthreads();
+  double ent = 0.0;
+  if (tid < rows) {                                                // as vb_estep: logsumexp, r = exp(log r), sum r log r
+    double* wr = resp + (size_t)(n0 + tid) * K;
+    double mx = -INFINITY;
+    for (int k = 0; k < K; ++k) mx = fmax(mx, wr[k]);
+    double se = 0.0;
+    for (int k = 0; k < K; ++k) se += exp(wr[k] - mx);
+    const double lse = mx + log(se);
+    for (int k = 0; k < K; ++k) {
+      const double lr = wr[k] - lse, r = exp(lr);
+      wr[k] = r;
+      ent += r * lr;
+    }
+  }
+  if (wave == 0) {
+    ent = wave_sum_d(ent);
+    if (lane == 0) ent_part[blockIdx.x] = ent;
+  }
+}
+
+__global__ __launch_bounds__(256) void vbwide_stats_kernel(const float* __restrict__ X, const double* __restrict__ resp, const double* __restrict__ state,
+                                                           const double* __restrict__ mom, int N, int K, int R, int rows, double* __restrict__ part) {
+  VbState S(const_cast<double*>(state), K, R, VBW_EXTRA);
+  if (S.tail[FIT_DONE] != 0.0) return;
+  fit_stats_pass(X, resp, mom, N, K, R, rows, part);
+}
+
+__global__ __launch_bounds__(256) void vbwide_reduce_kernel(const double* __restrict__ part, const double* __restrict__ ent_part,
+                                                            const double* __restrict__ state, int K, int R, int nsplit, int nslices,
+                                                            double* __restrict__ stats) {
+  VbState S(const_cast<double*>(state), K, R, VBW_EXTRA);
+  if (S.tail[FIT_DONE] != 0.0) return;
+  fit_stats_reduce(part, ent_part, K, R, nsplit, nslices, stats);
+}
+
+// _m_step for component blockIdx.x, 64 threads: what vb_update_component states per component, with the empirical covariance centred from the
+// shifted moments (as emgmm_mstep_kernel) and the factorisation of fit_chol_inverse.
+__global__ __launch_bounds__(64) void vbwide_mstep_kernel(const double* __restrict__ stats, const double* __restrict__ mom, double* state, VbCfg c) {
+  const int K = c.K, R = c.R, k = blockIdx.x, tid = threadIdx.x;
+  VbState S(state, K, R, VBW_EXTRA);
+  if (S.tail[FIT_DONE] != 0.0) return;
+  __shared__ double s_A[FIT_MAXR * FIT_LDC], s_s1[FIT_MAXR], s_dm[FIT_MAXR], s_dx[FIT_MAXR], s_dp[FIT_MAXR];
+  const double* st_nk = stats + 1;
+  const double* st_x = st_nk + K + (size_t)k * R;
+  const double* st_xx = stats + 1 + K + (size_t)K * R + (size_t)k * R * R;
+  const double* m2 = mom + R + 1;
+  const double Ntot = mom[R];
+  const double nk_raw = st_nk[k], nk = nk_raw + kEps10;            // nk = resp.sum(axis=0) + 10 * eps
+  const double mp = c.mean_prec_prior + nk, dof = (double)R + nk;  // degrees_of_freedom_prior_ = n_features
+  if (tid == 0) {
+    if (c.prior_type == 0) {
+      S.wa[k] = c.wc_prior + nk;                                   // dirichlet_distribution
+      S.wb[k] = 0.0;
+    } else {
+      double tail = 0.0;                                           // sum_{j>k} nk_j
+      for (int j = K - 1; j > k; --j) tail += st_nk[j] + kEps10;
+      S.wa[k] = 1.0 + nk;
+      S.wb[k] = c.wc_prior + tail;
+    }
+    S.mprec[k] = mp;
+    S.dof[k] = dof;
+  }
+  if (tid < R) {
+    const double cs = fit_shift(mom, R, tid), s1 = st_x[tid];
+    const double xk = (s1 + cs * nk_raw) / nk;                     // = sum r x / nk
+    const double pm = mom[tid] / Ntot;                             // mean_prior_
+    s_s1[tid] = s1;
+    s_dm[tid] = xk - cs;
+    s_dp[tid] = pm - cs;
+    s_dx[tid] = xk - pm;
+    S.means[k * R + tid] = (c.mean_prec_prior * pm + nk * xk) / mp;
+  }
+  __syncthreads();
+  double* C = S.cov + (size_t)k * R * R;
+  for (int e = tid; e < R * R; e += 64) {
+    const int i = e / R, j = e - i * R;
+    if (j < i) continue;
+    // sk = sum r (x - xk)(x - xk)^T / nk + reg_covar from the shifted moments, d = xk - c
+    double sk = st_xx[e] - (s_s1[i] * s_dm[j] + s_dm[i] * s_s1[j]) + nk_raw * s_dm[i] * s_dm[j];
+    sk = sk / nk + (i == j ? c.reg_covar : 0.0);
+    const double pc = (m2[e] - Ntot * s_dp[i] * s_dp[j]) / (Ntot - 1.0);                        // covariance_prior_
+    const double v = (pc + nk * sk + nk * c.mean_prec_prior / mp * (s_dx[i] * s_dx[j])) / dof;   // _estimate_wishart_full
+    s_A[i * FIT_LDC + j] = v;
+    s_A[j * FIT_LDC + i] = v;
+    C[i * R + j] = v;
+    C[j * R + i] = v;
+  }
+  __syncthreads();
+  const bool bad = fit_chol_inverse(s_A, R, S.pchol + (size_t)k * R * R, tid);
+  if (tid == 0) S.cstat[k] = bad ? -1.0 : 0.0;
+}
+
+__global__ __launch_bounds__(256) void vbwide_finish_kernel(const double* __restrict__ stats, double* state, VbCfg c, int it, float* __restrict__ w_out,
+                                                            float* __restrict__ m_out, float* __restrict__ c_out) {
+  const int K = c.K, R = c.R, tid = threadIdx.x;
+  VbState S(state, K, R, VBW_EXTRA);
+  if (S.tail[FIT_DONE] != 0.0) return;
+  __shared__ double s_ck[FIT_MAXK], s_stick[FIT_MAXK], s_lw[FIT_MAXK], s_dig;
+  __shared__ int s_done;
+  if (tid == 0) {
+    double sw = 0.0;
+    for (int k = 0; k < K; ++k) sw += S.wa[k];
+    s_dig = c.prior_type == 0 ? vb_digamma(sw) : 0.0;
+    s_done = 0;
+  }
+  if (tid < K) {
+    s_stick[tid] = c.prior_type == 0 ? 0.0 : vb_digamma(S.wb[tid]) - vb_digamma(S.wa[tid] + S.wb[tid]);
+    s_lw[tid] = vb_log_wishart_term(tid, S, c);
+  }
+  __syncthreads();
+  if (tid < K) S.ck[tid] = vb_estep_constant(tid, S.pchol + (size_t)tid * R * R, S, c, s_dig, s_stick);
+  if (tid == 0) {
+    bool bad = false;
+    for (int k = 0; k < K; ++k) bad = bad || (S.cstat[k] < 0.0);
+    if (bad) {                                                     // ill-defined empirical covariance (sklearn raises)
+      S.tail[FIT_CONVERGED] = -1.0; S.tail[FIT_DONE] = 1.0; s_done = 2;
+    } else if (it == 0) {
+      S.tail[FIT_LB] = -INFINITY; S.tail[FIT_NITER] = 0.0;         // _initialize: no lower bound yet
+      if (c.max_iter == 0) { S.tail[FIT_DONE] = 1.0; s_done = 1; }
+    } else {
+      const double lb = vb_lower_bound(S, c, stats[0], s_lw);
+      const bool conv = fabs(lb - S.tail[FIT_LB]) < c.tol;
+      S.tail[FIT_LB] = lb; S.tail[FIT_NITER] = (double)it;
+      if (conv) { S.tail[FIT_CONVERGED] = 1.0; S.tail[FIT_DONE] = 1.0; s_done = 1; }
+      else if (it >= c.max_iter) { S.tail[FIT_DONE] = 1.0; s_done = 1; }
+    }
+  }
+  __syncthreads();
+  if (s_done != 1) return;
+  vb_write_feed(S, c, s_ck, w_out, m_out, c_out, tid, 256);
+}
+
 inline bool vb_bad_shape(int K, int R, int prior_type) { return K < 1 || K > VB_MAXK || R < 1 || R > VB_MAXR || (prior_type != 0 && prior_type != 1); }
 inline VbCfg vb_cfg(int N, int K, int R, int prior_type, const int* labels, int max_iter = 0, double wc_prior = 0.0, double mean_prec_prior = 0.0,
                     double reg_covar = 0.0, double tol = 0.0) {
@@ -518,6 +745,67 @@ int ladder_vbgmm_shard_mstep(const double* stats, const double* moments, int K, 
   if (max_iter < 0 || it < 0 || vb_bad_shape(K, R, prior_type)) return LADDER_E_SHAPE;
   const VbCfg c = vb_cfg(0, K, R, prior_type, nullptr, max_iter, wc_prior, mean_prec_prior, reg_covar, tol);
   hipLaunchKernelGGL(vbgmm_shard_mstep_kernel, dim3(1), dim3(256), 0, stream, stats, moments, state, c, it, weights, means, covs);
+  LADDER_CHECK_LAUNCH();
+  return LADDER_OK;
+}
+
+// ---- the wide fit (8 < R <= 64; the kernels take 1 <= R <= 64): see vbwide_* above.  The caller all-reduces moments[0 .. R] after pass 0,
+// moments[R + 1 ..] after pass 1, and `stats` once per iteration between the two launches.
+static bool vbw_bad_shape(int K, int R, int prior_type) {
+  return K < 1 || K > FIT_MAXK || R < 1 || R > FIT_MAXR || (prior_type != 0 && prior_type != 1);
+}
+
+size_t ladder_vbgmm_wide_state_doubles(int K, int R) { return (K < 1 || R < 1) ? 0 : (size_t)K * (4 + VBW_EXTRA + R + 2 * (size_t)R * R) + 4; }
+size_t ladder_vbgmm_wide_stats_doubles(int K, int R) { return (K < 1 || R < 1) ? 0 : fit_stats_doubles(K, R); }
+size_t ladder_vbgmm_wide_moments_doubles(int R) { return R < 1 ? 0 : (size_t)R + 1 + (size_t)R * R; }
+
+size_t ladder_vbgmm_wide_workspace_bytes(int N, int K, int R) {
+  if (N < 1 || K < 1 || R < 1) return 0;
+  // responsibilities [N, K] | per-slice sums of r log r | per-split partial statistics
+  return ((size_t)N * K + (size_t)fit_slices(N) + (size_t)fit_split(N).nsplit * fit_stats_doubles(K, R)) * sizeof(double);
+}
+
+int ladder_vbgmm_wide_moments(const float* X, int N, int R, double* moments, int pass, ladder_stream_t stream) {
+  if (X == nullptr || moments == nullptr || N < 1 || R < 1 || R > FIT_MAXR || (pass != 0 && pass != 1)) return LADDER_E_SHAPE;
+  if (fit_misaligned(moments)) return LADDER_E_ALIGN;
+  if (pass == 0) hipLaunchKernelGGL(vbwide_moments1_kernel, dim3(R), dim3(256), 0, stream, X, N, R, moments);
+  else hipLaunchKernelGGL(vbwide_moments2_kernel, dim3(R, R), dim3(256), 0, stream, X, N, R, moments);
+  LADDER_CHECK_LAUNCH();
+  return LADDER_OK;
+}
+
+int ladder_vbgmm_wide_estep(const float* X, int N, int K, int R, const int* labels, const double* state, int prior_type, const double* moments,
+                            double* stats, void* ws, size_t ws_bytes, ladder_stream_t stream) {
+  if (X == nullptr || state == nullptr || moments == nullptr || stats == nullptr || N < 1 || vbw_bad_shape(K, R, prior_type)) return LADDER_E_SHAPE;
+  if (fit_misaligned(state) || fit_misaligned(moments) || fit_misaligned(stats) || fit_misaligned(ws)) return LADDER_E_ALIGN;
+  if (ws == nullptr || ws_bytes < ladder_vbgmm_wide_workspace_bytes(N, K, R)) return LADDER_E_WORKSPACE;
+  const FitSplit sp = fit_split(N);
+  const int G = fit_slices(N);
+  const size_t n = fit_stats_doubles(K, R);
+  double* resp = static_cast<double*>(ws);
+  double* ent_part = resp + (size_t)N * K;
+  double* part = ent_part + G;
+  hipLaunchKernelGGL(vbwide_estep_kernel, dim3(G), dim3(256), 0, stream, X, labels, state, N, K, R, resp, ent_part);
+  LADDER_CHECK_LAUNCH();
+  hipLaunchKernelGGL(vbwide_stats_kernel, dim3(K, sp.nsplit), dim3(256), 0, stream, X, (const double*)resp, state, moments, N, K, R, sp.rows, part);
+  LADDER_CHECK_LAUNCH();
+  hipLaunchKernelGGL(vbwide_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, (const double*)part, (const double*)ent_part, state, K,
+                     R, sp.nsplit, G, stats);
+  LADDER_CHECK_LAUNCH();
+  return LADDER_OK;
+}
+
+int ladder_vbgmm_wide_mstep(const double* stats, const double* moments, int K, int R, double* state, int prior_type, double wc_prior,
+                            double mean_prec_prior, double reg_covar, double tol, int max_iter, int it, float* weights, float* means, float* covs,
+                            ladder_stream_t stream) {
+  if (stats == nullptr || moments == nullptr || state == nullptr || weights == nullptr || means == nullptr || covs == nullptr || max_iter < 0 ||
+      it < 0 || vbw_bad_shape(K, R, prior_type))
+    return LADDER_E_SHAPE;
+  if (fit_misaligned(stats) || fit_misaligned(moments) || fit_misaligned(state)) return LADDER_E_ALIGN;
+  const VbCfg c = vb_cfg(0, K, R, prior_type, nullptr, max_iter, wc_prior, mean_prec_prior, reg_covar, tol);
+  hipLaunchKernelGGL(vbwide_mstep_kernel, dim3(K), dim3(64), 0, stream, stats, moments, state, c);
+  LADDER_CHECK_LAUNCH();
+  hipLaunchKernelGGL(vbwide_finish_kernel, dim3(1), dim3(256), 0, stream, stats, state, c, it, weights, means, covs);
   LADDER_CHECK_LAUNCH();
   return LADDER_OK;
 }
