@@ -791,6 +791,18 @@ size_t ladder_slp_state_bytes(int P, int n_step, int R);
 int ladder_slp_optimise(const float* start, const float* end, float* pts, const float* packed, int K, int R, int P, int n_step, int n_iter,
                         int t0, double lr, double beta1, double beta2, double eps, double clip, double w_path, double w_equal, double* state,
                         double* record, ladder_stream_t stream);
+/* The same loop for WIDE representations (csrc/slp_wide.hip): every argument means what it means in ladder_slp_optimise, state and record
+ * included, and the float64 part of the iteration is the same code; the mixture term (fp32 at the fp32-rounded points) runs on
+ * v_mfma_f32_16x16x4_f32 from the buffer `params` that ladder_gmm_prepare_dense fills (ladder_gmm_dense_param_floats), with the components
+ * strided over the four wavefronts of a path's workgroup and merged in a fixed order.  Deterministic; a path's result depends neither on P
+ * nor on its index; launches chained through `state` equal one long launch bit for bit.
+ * ladder_slp_wide_state_bytes: 3 * P * n_step * R doubles; 0 outside the limits.
+ * LADDER_E_SHAPE (nothing launched) unless 8 < R <= 64 and R % 4 == 0, 1 <= K <= 1024, 1 <= n_step <= 64 and n_step * R <= 2048 (the float64
+ * path state stays in LDS), P >= 1, 1 <= n_iter <= 4096, t0 >= 0, state != NULL when t0 > 0, and start / end / pts / params != NULL. */
+size_t ladder_slp_wide_state_bytes(int P, int n_step, int R);
+int ladder_slp_wide_optimise(const float* start, const float* end, float* pts, const float* params, int K, int R, int P, int n_step, int n_iter,
+                             int t0, double lr, double beta1, double beta2, double eps, double clip, double w_path, double w_equal, double* state,
+                             double* record, ladder_stream_t stream);
 
 /* ---------------------------------------------------------------- N17: FID evaluation (csrc/fid.hip)
  * codes/utils.py:127-200 (`compute_FID_score`, FID_network == "VGG").  The 13 convolutions of VGG16 run on ladder_conv2d_fwd / ladder_conv3x3_split

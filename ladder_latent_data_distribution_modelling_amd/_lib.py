@@ -238,6 +238,8 @@ PROTOTYPES = {
     "ladder_images_to_u8": (_i, [_p, _p, _z, _p]),
     "ladder_slp_state_bytes": (_z, [_i, _i, _i]),
     "ladder_slp_optimise": (_i, [_p, _p, _p, _p] + [_i] * 6 + [_d] * 7 + [_p, _p, _p]),
+    "ladder_slp_wide_state_bytes": (_z, [_i, _i, _i]),
+    "ladder_slp_wide_optimise": (_i, [_p, _p, _p, _p] + [_i] * 6 + [_d] * 7 + [_p, _p, _p]),
     "ladder_fid_preprocess": (_i, [_p, _i, _p] + [_i] * 7 + [_p]),
     "ladder_maxpool2x2_fwd": (_i, [_p, _p] + [_i] * 4 + [_p]),
     "ladder_global_pool": (_i, [_p, _p] + [_i] * 4 + [_p]),

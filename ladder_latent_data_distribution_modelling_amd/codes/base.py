@@ -504,9 +504,12 @@ class BaseTrain_joint(BaseTrain):
         starts, ends [P, R]; **kw goes to SLPInterpolator.optimise_batch (lr, w_equal_length, w_path_dist, init, clip, record).
         -> (pts [P, n_step, R], rec, images [P, n_step + 2, H, W, C] or None without `decode`)."""
         prior, R = self.config["prior"], int(self.config.get("representation_size", 0))
-        if prior != "ours" or not 1 <= R <= 8:
-            raise ValueError("interpolate_paths needs the mixture on the representation t with R <= 8 (prior 'ours'); this model's prior is %r, R = %d"
-                             % (prior, R))
+        if prior != "ours" or not (1 <= R <= 8 or (8 < R <= 64 and R % 4 == 0)):
+            raise ValueError("interpolate_paths needs the mixture on the representation t (prior 'ours') with R <= 8, or 8 < R <= 64 and "
+                             "R %% 4 == 0; this model's prior is %r, R = %d" % (prior, R))
+        if R > 8 and not (np.ndim(starts) == 2 and np.shape(starts) == np.shape(ends) and np.shape(starts)[1] == R):
+            raise ValueError("interpolate_paths: starts and ends must be [P, %d] points of the mixture on the representation t (got %s and %s)"
+                             % (R, np.shape(starts), np.shape(ends)))
         mixture = self.gm_params if mode == "crude-GM" else getattr(self, "gm_final_params", None)
         if mixture is None:
             raise RuntimeError("interpolation with mode %r needs the %s mixture, which has not been fitted yet (fit_GMM_VI(mode=%r))"

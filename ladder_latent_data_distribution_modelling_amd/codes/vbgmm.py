@@ -13,7 +13,7 @@ Width of the representation: R <= 8 runs the thread-per-sample kernels (`ladder_
 `ladder_vbgmm_shard_*` from there on and for sharded fits); 8 < R <= 64 runs `ladder_vbgmm_wide_*` for every N -- the E-step's whitening
 and the statistics on the float64 MFMA, the passes the EM fit of codes/emgmm.py uses (csrc/fit_mfma.h) -- with the same protocol, state
 front and fitted attributes (tests/test_gpu_vbgmm_wide.py).  1 <= K <= 64 for both.  The fit is the only part of the prior "ours" with
-this limit alone: the engine's wide mixture term also needs R % 4 == 0, and interpolation along shortest likely paths stays at R <= 8.
+this limit alone: the engine's wide mixture term also needs R % 4 == 0, and so does interpolation along shortest likely paths (csrc/slp_wide.hip reads the same dense buffer; n_step * R <= 2048).
 """
 import numpy as np
 import torch

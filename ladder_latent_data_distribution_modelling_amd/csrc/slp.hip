@@ -18,27 +18,17 @@
 //            fixed shuffle tree) and writes the record row.
 // Points and both moments live in LDS as float64 for the whole launch; `state` carries them between chained launches, and because the
 // step size is a function of the absolute iteration number t (pow, not a running product) a chained run equals a single launch bit for bit.
+// Everything but the mixture term -- loading and storing a path, the path algebra, phase B -- is csrc/slp_common.h, shared with the kernel for
+// wide representations (csrc/slp_wide.hip, 8 < R <= 64).
 #include "common.h"
 #include "gmm_packed.h"
+#include "slp_common.h"
 
 namespace {
 
-constexpr int SLP_THREADS = 256, SLP_WAVES = SLP_THREADS / 64, SLP_MAX_STEP = 64;
 // LDS budget for the packed mixture: 4096 floats = 16 KB (K = 64, R = 8 is 2880 floats = 11.5 KB; with the <= 21 KB of float64 path state a
 // workgroup stays below 40 KB, four workgroups per CU).  A larger mixture is read from global memory, where its <= 180 KB stay cache-resident.
 constexpr int SLP_LDS_FLOATS = 4096;
-
-struct SlpArgs {
-  const float* start;
-  const float* end;
-  float* pts;
-  const float* packed;
-  int K, n_step, n_iter, t0;
-  double lr, beta1, beta2, eps, clip, w_path, w_equal;
-  double* state;
-  double* record;
-  size_t plane;                // P * n_step * R: elements of one plane of `state` (points | m | v)
-};
 
 // log p(t) and -d log p / d t of one point for the calling wavefront (all 64 lanes active); results valid on every lane.
 template <int R>
@@ -77,28 +67,14 @@ __global__ __launch_bounds__(SLP_THREADS) void slp_optimise_kernel(SlpArgs A) {
 
   constexpr int STRIDE = GmmPacked<R>::STRIDE;
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int n = A.n_step, ne = n * R, K = A.K;
-  const size_t p = blockIdx.x, base = p * (size_t)ne;
-  double* s_pts = s_full + R;
+  const int n = A.n_step, K = A.K;
+  const size_t p = blockIdx.x;
+  const double* s_pts = s_full + R;
   const bool in_lds = K * STRIDE <= SLP_LDS_FLOATS;
 
   if (in_lds)
     for (int i = tid; i < K * STRIDE; i += SLP_THREADS) s_packed[i] = A.packed[i];
-  if (tid < R) {
-    s_full[tid] = (double)A.start[p * R + tid];
-    s_full[(n + 1) * R + tid] = (double)A.end[p * R + tid];
-  }
-  for (int e = tid; e < ne; e += SLP_THREADS) {
-    if (A.t0 > 0) {
-      s_pts[e] = A.state[base + e];
-      s_m[e] = A.state[A.plane + base + e];
-      s_v[e] = A.state[2 * A.plane + base + e];
-    } else {
-      s_pts[e] = (double)A.pts[base + e];
-      s_m[e] = 0.0;
-      s_v[e] = 0.0;
-    }
-  }
+  slp_load_path(A, R, tid, p, s_full, s_m, s_v);
   __syncthreads();
 
   for (int it = 0; it < A.n_iter; ++it) {
@@ -114,93 +90,15 @@ __global__ __launch_bounds__(SLP_THREADS) void slp_optimise_kernel(SlpArgs A) {
         for (int j = 0; j < R; ++j) s_gn[i * R + j] = g_[j];
       }
     }
-    if (wv == SLP_WAVES - 1) {
-#pragma clang fp contract(off)
-      const int ns = n + 1;                                  // segments; a lane owns segments lane and lane + 64 (ns <= 65)
-      double ln_[2] = {0.0, 0.0}, sum = 0.0;
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        const int s = lane + 64 * h;
-        if (s < ns) {
-          double q = 0.0;
-#pragma unroll
-          for (int j = 0; j < R; ++j) {
-            const double d = s_full[(s + 1) * R + j] - s_full[s * R + j];
-            q += d * d;
-          }
-          ln_[h] = sqrt(q);
-          sum += ln_[h];
-        }
-      }
-      sum = wave_sum_d(sum);
-      const double mean = sum / (double)ns;
-      double var = 0.0;
-#pragma unroll
-      for (int h = 0; h < 2; ++h)
-        if (lane + 64 * h < ns) var += (ln_[h] - mean) * (ln_[h] - mean);
-      var = wave_sum_d(var) / (double)ns;
-      const double sd = sqrt(var);                           // population standard deviation (tf.math.reduce_std)
-      const double cden = (double)ns * fmax(sd, 1e-30);
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        const int s = lane + 64 * h;
-        if (s < ns) {
-          const double den = fmax(ln_[h], 1e-30);
-#pragma unroll
-          for (int j = 0; j < R; ++j) s_unit[s * R + j] = (s_full[(s + 1) * R + j] - s_full[s * R + j]) / den;
-          s_c[s] = (ln_[h] - mean) / cden;                   // d std / d len_s
-        }
-      }
-      if (lane == 0) {
-        const double t = (double)(A.t0 + it + 1);
-        s_scal[0] = sum;
-        s_scal[1] = sd;
-        s_scal[2] = A.lr * sqrt(1.0 - pow(A.beta2, t)) / (1.0 - pow(A.beta1, t));
-      }
-    }
+    if (wv == SLP_WAVES - 1) slp_path_algebra(A, R, lane, it, s_full, s_unit, s_c, s_scal);
     __syncthreads();
 
     // ---- phase B: clip + Adam on the n_step * R elements, record row
-    {
-#pragma clang fp contract(off)
-      const double step = s_scal[2];
-      for (int e = tid; e < ne; e += SLP_THREADS) {
-        const int i = e / R, j = e - i * R;
-        const double u0 = s_unit[i * R + j], u1 = s_unit[(i + 1) * R + j];
-        const double g_len = u0 - u1;                        // + from the segment ending at p_i, - from the one leaving it
-        const double g_std = s_c[i] * u0 - s_c[i + 1] * u1;
-        double g = A.w_path * g_len + A.w_equal * g_std + (double)s_gn[e];
-        g = fmin(fmax(g, -A.clip), A.clip);                  // model.ClipIfNotNone
-        const double m = A.beta1 * s_m[e] + (1.0 - A.beta1) * g;
-        const double v = A.beta2 * s_v[e] + (1.0 - A.beta2) * g * g;
-        s_m[e] = m;
-        s_v[e] = v;
-        s_pts[e] = s_pts[e] - step * m / (sqrt(v) + A.eps);
-      }
-      if (A.record != nullptr && wv == 0) {
-        double nll = 0.0;
-        for (int i = lane; i < n; i += 64) nll -= (double)s_lp[i];
-        nll = wave_sum_d(nll);
-        if (lane == 0) {
-          double* r = A.record + (p * (size_t)A.n_iter + it) * 4;
-          r[0] = A.w_path * s_scal[0] + A.w_equal * s_scal[1] + nll;
-          r[1] = s_scal[0];
-          r[2] = s_scal[1];
-          r[3] = nll;
-        }
-      }
-    }
+    slp_clip_adam_record(A, R, tid, p, it, s_full, s_m, s_v, s_unit, s_c, s_scal, s_gn, s_lp);
     __syncthreads();
   }
 
-  for (int e = tid; e < ne; e += SLP_THREADS) {
-    A.pts[base + e] = (float)s_pts[e];
-    if (A.state != nullptr) {
-      A.state[base + e] = s_pts[e];
-      A.state[A.plane + base + e] = s_m[e];
-      A.state[2 * A.plane + base + e] = s_v[e];
-    }
-  }
+  slp_store_path(A, R, tid, p, s_full, s_m, s_v);
 }
 
 }  // namespace

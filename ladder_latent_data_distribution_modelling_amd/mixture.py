@@ -1,6 +1,7 @@
 """The fitted full-covariance Gaussian mixture on the device: the one owner of the prepared parameter buffer and of the choice between
 its two forms -- packed {c_k, mean_k, Linv_k} for narrow latents (R <= 8: csrc/mixture.hip, csrc/gmm_packed.h; also what
-`ladder_slp_optimise` reads) and the whitening-GEMM form for wide ones (8 < R <= 64, prior "GMM").  The ELBO term (LadderEngine), the demo's
+`ladder_slp_optimise` reads) and the whitening-GEMM form for wide ones (8 < R <= 64, R % 4 == 0: prior "GMM", or prior "ours" on a wide
+representation; also what `ladder_slp_wide_optimise` reads).  The ELBO term (LadderEngine), the demo's
 `log_prob` (demo/demo_tools.py) and the SLP interpolation (codes/interpolation.py) all evaluate the mixture through this class.
 """
 import numpy as np
