@@ -41,42 +41,20 @@ class DeviceGaussianMixture:
 
     def fit_sharded(self, X_local, comm, check_every=8):
         """The fit with the samples SHARDED over the data-parallel ranks: `X_local` [N_local, R] are THIS rank's samples, `comm` the engine's
-        communicator.  Per EM iteration: E-step + local statistics, all-reduce of 1 + K (1 + R + R^2) doubles (the sum of log_prob_norm
-        travels with the moments: the lower bound is a global mean), M-step + convergence test, identical on every rank.  The `done` flag
-        lives in device memory and is read every `check_every` iterations; iterations enqueued past the end are no-ops, so the result does
-        not depend on `check_every`.  A cold start takes its k-means labels from rank 0, once; warm starts exchange statistics only."""
-        K = self.n_components
-        Xd = MF.device_samples(X_local, self.device)
-        Nl, R = Xd.shape
-        st = torch.cuda.current_stream(self.device).cuda_stream
-        f64 = lambda n: torch.zeros(n, dtype=torch.float64, device=self.device)
-        mom = f64(L.query("ladder_emgmm_shift_doubles", R))                   # [ sum_n x_n | N ]: the shift vector and the global count
-        L.call("ladder_emgmm_shift", Xd.data_ptr(), Nl, R, mom.data_ptr(), st)
-        comm.allreduce_(mom)
-        MF.check_sample_count(int(mom[-1].item()), K)                          # sklearn's check, on the GLOBAL sample count
-        stats = f64(L.query("ladder_emgmm_stats_doubles", K, R))
-        ws = torch.empty(L.query("ladder_emgmm_workspace_bytes", Nl, K, R), dtype=torch.uint8, device=self.device)
-        do_init, rs, n_fits = MF.fit_plan(self)
-        lib = L.load()
-        estep_fn, mstep_fn = lib.ladder_emgmm_estep, lib.ladder_emgmm_mstep
+        communicator.  The loop is MF.fit_sliced's: per EM iteration E-step + local statistics, all-reduce of 1 + K (1 + R + R^2) doubles
+        (the sum of log_prob_norm travels with the moments: the lower bound is a global mean), M-step + convergence test."""
+        def moments(Xd, comm, f64, st, check):
+            Nl, R = Xd.shape
+            mom = f64(L.query("ladder_emgmm_shift_doubles", R))               # [ sum_n x_n | N ]: the shift vector and the global count
+            L.call("ladder_emgmm_shift", Xd.data_ptr(), Nl, R, mom.data_ptr(), st)
+            comm.allreduce_(mom)
+            check(int(mom[-1].item()))
+            self.converged_ = False                                            # (sklearn sets it before the first restart: a failed fit leaves it)
+            return mom
 
-        def one_fit():
-            state = f64(L.query("ladder_emgmm_state_doubles", K, R)) if do_init else self._state
-            state[MF.FIT_CONVERGED:] = 0.0
-            labels = self._initial_labels(Xd, comm, rs) if do_init else None
-            w, m, c = MF.feed_tensors(K, R, self.device)
-            e_head = (Xd.data_ptr(), Nl, K, R)
-            e_tail = (state.data_ptr(), mom.data_ptr(), stats.data_ptr(), ws.data_ptr(), ws.numel(), st)
-            m_head = (stats.data_ptr(), mom.data_ptr(), K, R, state.data_ptr(), float(self.reg_covar), float(self.tol), self.max_iter)
-            m_tail = (w.data_ptr(), m.data_ptr(), c.data_ptr(), st)
-            MF.iterate_until_done(lambda it: estep_fn(*e_head, labels.data_ptr() if (labels is not None and it == 0) else None, *e_tail),
-                                  lambda it: mstep_fn(*m_head, it, *m_tail), comm.allreduce_ if comm.on else None, stats, state[MF.FIT_DONE:],
-                                  0 if do_init else 1, self.max_iter, check_every, "EM mixture fit")
-            return state, w, m, c
-
-        self.converged_ = False                                                # (sklearn sets it before the first restart: a failed fit leaves it)
-        MF.keep_best(self, MF.best_of_restarts(n_fits, one_fit))
-        self._R = R
+        fam = MF.Family("ladder_emgmm_", moments, "ladder_emgmm_state_doubles", lambda mom: (mom.data_ptr(),), (), "EM mixture fit")
+        MF.keep_best(self, MF.fit_sliced(self, X_local, comm, check_every, fam))
+        self._R = self.means_dev.shape[1]
         return self
 
     def _prepare_state(self, state, R):

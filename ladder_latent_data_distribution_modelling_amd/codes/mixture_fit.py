@@ -1,8 +1,10 @@
 """What the two device mixture fits share (codes/vbgmm.py: variational Bayes on t, codes/emgmm.py: EM on z): the single-process
 communicator, the k-means labels of a cold start (on the gathered samples of rank 0: sklearn.cluster.KMeans on the host, exactly the call
-BaseMixture._initialize_parameters makes, or with kmeans_backend="hip" the same algorithm on the device, codes/kmeans.py), the loop that drives the E-step / all-reduce / M-step launches against the device-side
-`done` flag, the choice among `n_init` restarts and sklearn's messages.
+BaseMixture._initialize_parameters makes, or with kmeans_backend="hip" the same algorithm on the device, codes/kmeans.py), fit_sliced -- the one
+driver of the EM, the narrow sharded and the wide variational fit -- with the loop that drives its E-step / all-reduce / M-step launches against
+the device-side `done` flag, the choice among `n_init` restarts and sklearn's messages.
 """
+import collections
 import warnings
 
 import numpy as np
@@ -143,6 +145,47 @@ def iterate_until_done(estep, mstep, exchange, stats, flag, first_it, max_iter, 
             if it > max_iter:
                 break
         done = bool(flag.item() != 0) or it > max_iter                         # (identical on every rank: same all-reduced statistics)
+
+
+# One family of entry points, as fit_sliced drives it.  prefix: of its stats_doubles / workspace_bytes / estep / mstep; moments(Xd, comm, f64, st,
+# check) -> the all-reduced moments, having called check(global sample count) where sklearn checks it; state_query: the size of a fresh state;
+# e_mid(mom): the E-step's arguments between `state` and `stats`; m_mid: the M-step's between `state` and reg_covar; what: names a failed launch.
+Family = collections.namedtuple("Family", "prefix moments state_query e_mid m_mid what")
+
+
+def fit_sliced(gm, X_local, comm, check_every, fam):
+    """The fit of `gm` on THIS rank's samples `X_local` [N_local, R] with the kernels of `fam`: moments, then per restart and iteration
+    E-step + local statistics / all-reduce of `stats` / M-step + convergence test, identical on every rank, against the device-side `done`
+    flag (iterate_until_done).  A cold start takes its k-means labels from rank 0, once per restart; warm starts exchange statistics only.
+    -> what best_of_restarts returns."""
+    from .. import _lib as L
+    K = gm.n_components
+    Xd = device_samples(X_local, gm.device)
+    Nl, R = Xd.shape
+    st = torch.cuda.current_stream(gm.device).cuda_stream
+    f64 = lambda n: torch.zeros(n, dtype=torch.float64, device=gm.device)
+    mom = fam.moments(Xd, comm, f64, st, lambda n: check_sample_count(n, K))    # sklearn's check, on the GLOBAL sample count
+    stats = f64(L.query(fam.prefix + "stats_doubles", K, R))
+    ws = torch.empty(L.query(fam.prefix + "workspace_bytes", Nl, K, R), dtype=torch.uint8, device=gm.device)
+    do_init, rs, n_fits = fit_plan(gm)
+    lib = L.load()
+    estep_fn, mstep_fn = getattr(lib, fam.prefix + "estep"), getattr(lib, fam.prefix + "mstep")
+    n_state = L.query(fam.state_query, K, R)
+
+    def one_fit():
+        state = f64(n_state) if do_init else gm._state
+        state[FIT_CONVERGED:] = 0.0
+        labels = gm._initial_labels(Xd, comm, rs) if do_init else None
+        w, m, c = feed_tensors(K, R, gm.device)                    # (below: argument lists bound once, the loop is two foreign calls)
+        e_head, e_tail = (Xd.data_ptr(), Nl, K, R), (state.data_ptr(),) + fam.e_mid(mom) + (stats.data_ptr(), ws.data_ptr(), ws.numel(), st)
+        m_head = (stats.data_ptr(), mom.data_ptr(), K, R, state.data_ptr()) + fam.m_mid + (float(gm.reg_covar), float(gm.tol), gm.max_iter)
+        m_tail = (w.data_ptr(), m.data_ptr(), c.data_ptr(), st)
+        iterate_until_done(lambda it: estep_fn(*e_head, labels.data_ptr() if (labels is not None and it == 0) else None, *e_tail),
+                           lambda it: mstep_fn(*m_head, it, *m_tail), comm.allreduce_ if comm.on else None, stats, state[FIT_DONE:],
+                           0 if do_init else 1, gm.max_iter, check_every, fam.what)
+        return state, w, m, c
+
+    return best_of_restarts(n_fits, one_fit)
 
 
 def read_tail(state):

@@ -87,60 +87,38 @@ class DeviceBayesianGaussianMixture:
     def fit_sharded(self, X_local, comm, check_every=8):
         """The same fit with the samples SHARDED over the data-parallel ranks (exchange step C5 of SURVEY 2.3 as north_star words it:
         an all-reduce of the mixture's sufficient statistics): `X_local` [N_local, R] are THIS rank's samples, `comm` the engine's
-        communicator (all-reduce over RCCL / xGMI).  Per variational iteration: E-step + local statistics (one launch), all-reduce of
-        1 + K + K R + K R^2 doubles, M-step + lower bound + convergence test (one launch, identical on every rank).  The `done` flag
-        lives in device memory and is read every `check_every` iterations; iterations enqueued past the end are no-ops, so the result
-        does not depend on `check_every`.  A cold start takes its k-means labels from rank 0 (sklearn.cluster.KMeans on the gathered
-        samples, as BaseMixture._initialize_parameters does) -- once; warm starts exchange statistics only.
+        communicator (all-reduce over RCCL / xGMI).  The loop is MF.fit_sliced's: per variational iteration E-step + local statistics,
+        all-reduce of 1 + K + K R + K R^2 doubles, M-step + lower bound + convergence test; the result does not depend on `check_every`.
         R > 8 picks the ladder_vbgmm_wide_* family: same loop, the data-derived priors from two small all-reduces ([sum x | N], then the second
         moments about the shift that defines)."""
-        K = self.n_components
         Xd = MF.device_samples(X_local, self.device)
-        Nl, R = Xd.shape
+        R = Xd.shape[1]
         if R > WIDE_MAX_R:
             raise ValueError("the HIP mixture fit takes a representation of at most %d dimensions, got %d" % (WIDE_MAX_R, R))
         wide = R > NARROW_MAX_R
-        fam = "ladder_vbgmm_wide_" if wide else "ladder_vbgmm_shard_"
+        prefix = "ladder_vbgmm_wide_" if wide else "ladder_vbgmm_shard_"
         ptype, wc, mp = self._prior_args()
-        st = torch.cuda.current_stream(self.device).cuda_stream
-        f64 = lambda n: torch.zeros(n, dtype=torch.float64, device=self.device)
-        mom = f64(L.query(fam + "moments_doubles", R))
-        if wide:
-            L.call(fam + "moments", Xd.data_ptr(), Nl, R, mom.data_ptr(), 0, st)
-            comm.allreduce_(mom[:R + 1])                                       # [ sum x | N ]: the shift, mean_prior_ and the global count
-            n_glob = mom[R:R + 1]
-        else:
-            L.call(fam + "moments", Xd.data_ptr(), Nl, R, mom.data_ptr(), st)
-            comm.allreduce_(mom)
-            n_glob = torch.full((1,), float(Nl), dtype=torch.float64, device=self.device)
-            comm.allreduce_(n_glob)
-        MF.check_sample_count(int(n_glob.item()), K)                           # sklearn's check, on the GLOBAL sample count (ADVICE r3)
-        if wide:
-            L.call(fam + "moments", Xd.data_ptr(), Nl, R, mom.data_ptr(), 1, st)
-            comm.allreduce_(mom[R + 1:])                                       # sum x~ x~^T about that shift: covariance_prior_
-        stats = f64(L.query(fam + "stats_doubles", K, R))
-        ws = torch.empty(L.query(fam + "workspace_bytes", Nl, K, R), dtype=torch.uint8, device=self.device)
-        do_init, rs, n_fits = MF.fit_plan(self)
-        lib = L.load()
-        estep_fn, mstep_fn = getattr(lib, fam + "estep"), getattr(lib, fam + "mstep")
-        n_state = L.query("ladder_vbgmm_wide_state_doubles" if wide else "ladder_vbgmm_state_doubles", K, R)
 
-        def one_fit():
-            state = f64(n_state) if do_init else self._state
-            state[MF.FIT_CONVERGED:] = 0.0
-            labels = self._initial_labels(Xd, comm, rs) if do_init else None   # rank 0's k-means, once; warm starts exchange statistics only
-            w, m, c = MF.feed_tensors(K, R, self.device)
-            # (the argument lists are constant over the iterations but for `labels` / `it`: bound once, the loop is two foreign calls)
-            e_tail = (state.data_ptr(), ptype) + ((mom.data_ptr(),) if wide else ()) + (stats.data_ptr(), ws.data_ptr(), ws.numel(), st)
-            m_head = (stats.data_ptr(), mom.data_ptr(), K, R, state.data_ptr(), ptype, wc, mp, float(self.reg_covar), float(self.tol), self.max_iter)
-            m_tail = (w.data_ptr(), m.data_ptr(), c.data_ptr(), st)
-            xp = Xd.data_ptr()
-            MF.iterate_until_done(lambda it: estep_fn(xp, Nl, K, R, labels.data_ptr() if (labels is not None and it == 0) else None, *e_tail),
-                                  lambda it: mstep_fn(*m_head, it, *m_tail), comm.allreduce_ if comm.on else None, stats, state[MF.FIT_DONE:],
-                                  0 if do_init else 1, self.max_iter, check_every, "sharded mixture fit")
-            return state, w, m, c
+        def moments(Xd, comm, f64, st, check):
+            Nl = Xd.shape[0]
+            mom = f64(L.query(prefix + "moments_doubles", R))
+            if wide:
+                L.call(prefix + "moments", Xd.data_ptr(), Nl, R, mom.data_ptr(), 0, st)
+                comm.allreduce_(mom[:R + 1])                                   # [ sum x | N ]: the shift, mean_prior_ and the global count
+                check(int(mom[R].item()))
+                L.call(prefix + "moments", Xd.data_ptr(), Nl, R, mom.data_ptr(), 1, st)
+                comm.allreduce_(mom[R + 1:])                                   # sum x~ x~^T about that shift: covariance_prior_
+            else:
+                L.call(prefix + "moments", Xd.data_ptr(), Nl, R, mom.data_ptr(), st)
+                comm.allreduce_(mom)
+                n_glob = torch.full((1,), float(Nl), dtype=torch.float64, device=self.device)
+                comm.allreduce_(n_glob)
+                check(int(n_glob.item()))
+            return mom
 
-        return MF.keep_best(self, MF.best_of_restarts(n_fits, one_fit))
+        fam = MF.Family(prefix, moments, "ladder_vbgmm_wide_state_doubles" if wide else "ladder_vbgmm_state_doubles",
+                        (lambda mom: (ptype, mom.data_ptr())) if wide else (lambda mom: (ptype,)), (ptype, wc, mp), "sharded mixture fit")
+        return MF.keep_best(self, MF.fit_sliced(self, Xd, comm, check_every, fam))
 
     # float64 views of the fitted parameters, as sklearn exposes them
     def _unpack(self):

@@ -3,27 +3,30 @@
 // _estimate_gaussian_parameters, _compute_precision_cholesky, _estimate_log_gaussian_prob, _m_step and the loop of BaseMixture.fit_predict.
 //
 // One EM iteration `it` (0 = the M-step on the hard k-means labels, then 1 .. max_iter) is
-//   emgmm_estep_kernel     a workgroup owns 64 samples; per component k it stages the upper-triangular P_k = precisions_cholesky_[k] in LDS, forms
+//   emgmm_estep_kernel     fit_estep_slice under the policy EmEstep: a workgroup owns 64 samples; per component k it stages the upper-triangular P_k = precisions_cholesky_[k] in LDS, forms
 //                          y = (x - mu_k) P_k on v_mfma_f64_16x16x4_f64 (the all-zero 16 x 16 blocks below the diagonal are skipped) and reduces |y|^2 per
 //                          row; after the last k: logsumexp per row, responsibilities [N, K] float64, the slice's sum of log_prob_norm.
 //                          it = 0: the responsibilities are the one-hot labels.
-//   emgmm_stats_kernel     grid (component, row split): n_k, sum r x~ and the 16 x 16 blocks on and above the diagonal of sum r x~ x~^T on the same MFMA,
+//   fit_stats_kernel       grid (component, row split): n_k, sum r x~ and the 16 x 16 blocks on and above the diagonal of sum r x~ x~^T on the same MFMA,
 //                          x~ = x - c with ONE shift vector c for all components (the fp32-rounded global mean: x - c is exact in float64 and the raw
 //                          second moments carry no uncentred cancellation); partials go to the workspace
-//   emgmm_reduce_kernel    adds the partials in the order split 0, 1, ... (and the slices' log_prob_norm sums in slice order) into
+//   fit_reduce_kernel      adds the partials in the order split 0, 1, ... (and the slices' log_prob_norm sums in slice order) into
 //                          stats = [ sum log_prob_norm | n_k [K] | sum r x~ [K,R] | sum r x~ x~^T [K,R,R] ]; the lower triangle mirrors the upper one
 //   (all-reduce of stats over the data-parallel ranks, by the caller: the lower bound is a GLOBAL mean, so its sum travels with the rest)
-//   emgmm_mstep_kernel     one workgroup per component: weight, mean, covariance centred from the shifted raw moments + reg_covar, Cholesky factor,
+//   emgmm_mstep_kernel     one workgroup per component: weight, mean, covariance centred from the shifted raw moments + reg_covar
+//                          (fit_centre_mean / fit_centred_cov), Cholesky factor,
 //                          its triangular inverse (precisions_cholesky_), log-determinant, fp32 copies for the engine's feed
-//   emgmm_finish_kernel    lower_bound = sum log_prob_norm / N of THIS iteration's E-step, |change| < tol, n_iter_, converged_ and the `done` flag
+//   emgmm_finish_kernel    fit_end_iteration with lower_bound = sum log_prob_norm / N of THIS iteration's E-step: |change| < tol, n_iter_,
+//                          converged_ and the `done` flag
 // Every kernel returns at once when `done` is set, so the host may enqueue iterations ahead and read the flag every few iterations (the contract of
 // ladder_vbgmm_shard_*).  No atomics: every sum has one fixed order, so a fit gives the same bits on every run and for every `check_every`.
 //
 // state (doubles): weights [K] | means [K,R] | covariances [K,R,R] | precisions_cholesky [K,R,R] | log_det [K] | component status [K] |
 //                  the tail of csrc/fit_util.h: lower_bound_, n_iter_, converged_, done
 //
-// The MFMA passes -- the whitening quadratic form, the statistics and their reduction, the factorisation -- are in csrc/fit_mfma.h, shared with
-// the wide variational fit of csrc/vbgmm.hip.
+// All but the policy, the M-step's own arithmetic and the state layout is shared with the wide variational fit of csrc/vbgmm.hip: the E-step body,
+// the column-sum / statistics / reduce kernels, the host side of the E-step, the centring and the factorisation in csrc/fit_mfma.h, the `done`
+// test and the end of an iteration in csrc/fit_util.h.
 #include "fit_mfma.h"
 
 namespace {
@@ -43,86 +46,29 @@ struct EmState {
 
 __host__ __device__ inline size_t em_state_doubles(int K, int R) { return (size_t)K * (3 + R + 2 * (size_t)R * R) + 4; }
 
-// ------------------------------------------------------------------------------------------------ column sums for the shift
-// One workgroup per column (column_sum_256: thread-strided partial sums, the shuffle tree, then the four wavefronts in order).
-__global__ __launch_bounds__(256) void emgmm_shift_kernel(const float* __restrict__ X, int N, int R, double* __restrict__ mom) {
-  const int j = blockIdx.x, tid = threadIdx.x;
-  __shared__ double s_red[4];
-  const double a = column_sum_256(X, N, R, j, s_red, tid);
-  if (tid == 0) {
-    mom[j] = a;
-    if (j == 0) mom[R] = (double)N;
-  }
-}
-
 // ------------------------------------------------------------------------------------------------ E-step
+// _estimate_weighted_log_prob and _estimate_log_prob_resp as the policy of fit_estep_slice: constants log|P_k| and log w_k, the slice scalar is
+// the sum of log_prob_norm.
+struct EmEstep {
+  static constexpr int NCONST = 2;
+  const double *logdet, *w;
+  int R;
+  __device__ void load(double* s_c, int k) const {
+    s_c[k] = logdet[k];
+    s_c[FIT_MAXK + k] = log(w[k]);
+  }
+  __device__ double log_term(const double* s_c, int k, double q) const { return (-0.5 * (R * kLog2Pi + q) + s_c[k]) + s_c[FIT_MAXK + k]; }
+  __device__ double finish_row(double* wr, int K, double lpn) const {
+    for (int k = 0; k < K; ++k) wr[k] = exp(wr[k] - lpn);
+    return lpn;
+  }
+};
+
 __global__ __launch_bounds__(256) void emgmm_estep_kernel(const float* __restrict__ X, const int* __restrict__ labels, const double* state, int N, int K,
                                                           int R, double* resp, double* __restrict__ lpn_part) {
   EmState S(const_cast<double*>(state), K, R);
-  if (S.tail[FIT_DONE] != 0.0) return;                             // the fit is over: iterations enqueued past the end are no-ops
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, m = lane & 15, kq = lane >> 4;
-  const int n0 = blockIdx.x * FIT_SLICE, rows = min(FIT_SLICE, N - n0);
-  if (labels != nullptr) {                                         // iteration 0: hard labels, through the same statistics kernels
-    for (int i = tid; i < rows * K; i += 256) {
-      const int r = i / K, k = i - r * K;
-      resp[(size_t)(n0 + r) * K + k] = (labels[n0 + r] == k) ? 1.0 : 0.0;
-    }
-    if (tid == 0) lpn_part[blockIdx.x] = 0.0;
-    return;
-  }
-  __shared__ double s_P[FIT_MAXR * FIT_LDP], s_mu[FIT_MAXR], s_ld[FIT_MAXK], s_lw[FIT_MAXK];
-  const int nb = (R + 15) / 16, Rp = nb * 16, nsteps = (R + 3) / 4;
-  double xa[16];                                                   // this lane's A operands: x[row][4 s + kq], zero past R
-  fit_slice_rows(X, n0, rows, R, wave * 16 + m, kq, xa);
-  if (tid < K) {
-    s_ld[tid] = S.logdet[tid];
-    s_lw[tid] = log(S.w[tid]);
-  }
-  for (int k = 0; k < K; ++k) {
-    __syncthreads();                                               // (the previous component's operands are no longer read)
-    fit_stage_component(S.pchol + (size_t)k * R * R, S.means + k * R, R, Rp, s_P, s_mu, tid);
-    __syncthreads();
-    double q4[4];
-    fit_whiten_sq(xa, s_mu, s_P, nb, nsteps, m, kq, q4);
-    if (m == 0) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int rr = wave * 16 + kq + 4 * r;
-        if (rr < rows) resp[(size_t)(n0 + rr) * K + k] = (-0.5 * (R * kLog2Pi + q4[r]) + s_ld[k]) + s_lw[k];
-      }
-    }
-  }
-  __syncthreads();
-  double lpn = 0.0;
-  if (tid < rows) {
-    double* wr = resp + (size_t)(n0 + tid) * K;
-    double mx = -INFINITY;
-    for (int k = 0; k < K; ++k) mx = fmax(mx, wr[k]);
-    double se = 0.0;
-    for (int k = 0; k < K; ++k) se += exp(wr[k] - mx);
-    lpn = log(se) + mx;
-    for (int k = 0; k < K; ++k) wr[k] = exp(wr[k] - lpn);
-  }
-  if (wave == 0) {
-    lpn = wave_sum_d(lpn);
-    if (lane == 0) lpn_part[blockIdx.x] = lpn;
-  }
-}
-
-// ------------------------------------------------------------------------------------------------ statistics
-// blockIdx.x = component, blockIdx.y = row split: fit_stats_pass, then fit_stats_reduce with the slices' log_prob_norm sums as element 0.
-__global__ __launch_bounds__(256) void emgmm_stats_kernel(const float* __restrict__ X, const double* __restrict__ resp, const double* __restrict__ state,
-                                                          const double* __restrict__ mom, int N, int K, int R, int rows, double* __restrict__ part) {
-  EmState S(const_cast<double*>(state), K, R);
-  if (S.tail[FIT_DONE] != 0.0) return;
-  fit_stats_pass(X, resp, mom, N, K, R, rows, part);
-}
-
-__global__ __launch_bounds__(256) void emgmm_reduce_kernel(const double* __restrict__ part, const double* __restrict__ lpn_part, const double* __restrict__ state,
-                                                           int K, int R, int nsplit, int nslices, double* __restrict__ stats) {
-  EmState S(const_cast<double*>(state), K, R);
-  if (S.tail[FIT_DONE] != 0.0) return;
-  fit_stats_reduce(part, lpn_part, K, R, nsplit, nslices, stats);
+  if (fit_done(S.tail)) return;
+  fit_estep_slice(EmEstep{S.logdet, S.w, R}, X, labels, S.pchol, S.means, N, K, R, resp, lpn_part);
 }
 
 // ------------------------------------------------------------------------------------------------ M-step
@@ -142,42 +88,35 @@ __global__ __launch_bounds__(64) void emgmm_mstep_kernel(const double* __restric
                                                          double reg_covar, int it, float* __restrict__ w_out, float* __restrict__ m_out,
                                                          float* __restrict__ c_out) {
   EmState S(state, K, R);
-  if (S.tail[FIT_DONE] != 0.0) return;
+  if (fit_done(S.tail)) return;
   const int k = blockIdx.x, tid = threadIdx.x;
   __shared__ double s_A[FIT_MAXR * FIT_LDC], s_s1[FIT_MAXR], s_dm[FIT_MAXR];
-  const double* st_nk = stats + 1;
-  const double* st_x = st_nk + K + (size_t)k * R;
-  const double* st_xx = stats + 1 + K + (size_t)K * R + (size_t)k * R * R;
-  const double nk_raw = st_nk[k], nk = nk_raw + kEps10;            // nk = resp.sum(axis=0) + 10 * eps
+  const FitStats<const double> st(stats, K, R, k);
+  const double nk_raw = st.nk[k], nk = nk_raw + kEps10;            // nk = resp.sum(axis=0) + 10 * eps
   if (tid == 0) {
     double w;
     if (it == 0) {
       w = nk / mom[R];                                             // _initialize: weights = nk / n_samples
     } else {
       double tot = 0.0;                                            // _m_step: weights_ = nk; weights_ /= weights_.sum()
-      for (int j = 0; j < K; ++j) tot += st_nk[j] + kEps10;
+      for (int j = 0; j < K; ++j) tot += st.nk[j] + kEps10;
       w = nk / tot;
     }
     S.w[k] = w;
     w_out[k] = (float)w;
   }
   if (tid < R) {
-    const double c = fit_shift(mom, R, tid), s1 = st_x[tid];
-    const double mean = (s1 + c * nk_raw) / nk;                    // = sum r x / nk
-    s_s1[tid] = s1;
-    s_dm[tid] = mean - c;
+    const double mean = fit_centre_mean(mom, R, tid, st.x[tid], nk_raw, nk, s_s1, s_dm);
     S.means[k * R + tid] = mean;
     m_out[k * R + tid] = (float)mean;
   }
   __syncthreads();
-  // sum r (x - mean)(x - mean)^T = S2 - s1 d^T - d s1^T + n_k d d^T with d = mean - c; [i][j] for i <= j, mirrored
-  double* C = S.cov + (size_t)k * R * R;
+  double* C = S.cov + (size_t)k * R * R;                           // [i][j] for i <= j, mirrored
   float* Cf = c_out + (size_t)k * R * R;
   for (int e = tid; e < R * R; e += 64) {
     const int i = e / R, j = e - i * R;
     if (j < i) continue;
-    double v = st_xx[e] - (s_s1[i] * s_dm[j] + s_dm[i] * s_s1[j]) + nk_raw * s_dm[i] * s_dm[j];
-    v = v / nk + (i == j ? reg_covar : 0.0);
+    const double v = fit_centred_cov(st.xx[e], s_s1, s_dm, i, j, nk_raw, nk, reg_covar);
     s_A[i * FIT_LDC + j] = v;
     s_A[j * FIT_LDC + i] = v;
     C[i * R + j] = v;
@@ -206,31 +145,10 @@ __global__ void emgmm_finish_kernel(const double* __restrict__ stats, const doub
                                     int it) {
   EmState S(state, K, R);
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  if (it >= 0 && S.tail[FIT_DONE] != 0.0) return;
+  if (it >= 0 && fit_done(S.tail)) return;
   bool bad = false;
   for (int k = 0; k < K; ++k) bad = bad || (S.cstat[k] < 0.0);
-  if (bad) {
-    S.tail[FIT_CONVERGED] = -1.0;
-    S.tail[FIT_DONE] = 1.0;
-    return;
-  }
-  if (it < 0) return;
-  if (it == 0) {
-    S.tail[FIT_LB] = -INFINITY;                                    // a cold start has no lower bound yet
-    S.tail[FIT_NITER] = 0.0;
-    if (max_iter == 0) S.tail[FIT_DONE] = 1.0;
-    return;
-  }
-  const double lb = stats[0] / mom[R];                             // np.mean(log_prob_norm) over ALL samples
-  const bool conv = fabs(lb - S.tail[FIT_LB]) < tol;
-  S.tail[FIT_LB] = lb;
-  S.tail[FIT_NITER] = (double)it;
-  if (conv) {
-    S.tail[FIT_CONVERGED] = 1.0;
-    S.tail[FIT_DONE] = 1.0;
-  } else if (it >= max_iter) {
-    S.tail[FIT_DONE] = 1.0;
-  }
+  fit_end_iteration(S.tail, bad, it, tol, max_iter, [&] { return stats[0] / mom[R]; });      // np.mean(log_prob_norm) over ALL samples
 }
 
 }  // namespace
@@ -241,40 +159,20 @@ size_t ladder_emgmm_state_doubles(int K, int R) { return (K < 1 || R < 1) ? 0 : 
 size_t ladder_emgmm_stats_doubles(int K, int R) { return (K < 1 || R < 1) ? 0 : fit_stats_doubles(K, R); }
 size_t ladder_emgmm_shift_doubles(int R) { return R < 1 ? 0 : (size_t)R + 1; }
 
-size_t ladder_emgmm_workspace_bytes(int N, int K, int R) {
-  if (N < 1 || K < 1 || R < 1) return 0;
-  // responsibilities [N, K] | per-slice log_prob_norm sums | per-split partial statistics
-  return ((size_t)N * K + (size_t)fit_slices(N) + (size_t)fit_split(N).nsplit * fit_stats_doubles(K, R)) * sizeof(double);
-}
+size_t ladder_emgmm_workspace_bytes(int N, int K, int R) { return fit_sliced_workspace_bytes(N, K, R); }
 
 int ladder_emgmm_shift(const float* X, int N, int R, double* moments, ladder_stream_t stream) {
   if (X == nullptr || moments == nullptr || N < 1 || R < 1 || R > FIT_MAXR) return LADDER_E_SHAPE;
   if (fit_misaligned(moments)) return LADDER_E_ALIGN;
-  hipLaunchKernelGGL(emgmm_shift_kernel, dim3(R), dim3(256), 0, stream, X, N, R, moments);
+  hipLaunchKernelGGL(fit_colsum_kernel, dim3(R), dim3(256), 0, stream, X, N, R, moments);
   LADDER_CHECK_LAUNCH();
   return LADDER_OK;
 }
 
 int ladder_emgmm_estep(const float* X, int N, int K, int R, const int* labels, const double* state, const double* moments, double* stats, void* ws,
                        size_t ws_bytes, ladder_stream_t stream) {
-  if (X == nullptr || state == nullptr || moments == nullptr || stats == nullptr || N < 1 || K < 1 || K > FIT_MAXK || R < 1 || R > FIT_MAXR)
-    return LADDER_E_SHAPE;
-  if (fit_misaligned(state) || fit_misaligned(moments) || fit_misaligned(stats) || fit_misaligned(ws)) return LADDER_E_ALIGN;
-  if (ws == nullptr || ws_bytes < ladder_emgmm_workspace_bytes(N, K, R)) return LADDER_E_WORKSPACE;
-  const FitSplit sp = fit_split(N);
-  const int G = fit_slices(N);
-  const size_t n = fit_stats_doubles(K, R);
-  double* resp = static_cast<double*>(ws);
-  double* lpn_part = resp + (size_t)N * K;
-  double* part = lpn_part + G;
-  hipLaunchKernelGGL(emgmm_estep_kernel, dim3(G), dim3(256), 0, stream, X, labels, state, N, K, R, resp, lpn_part);
-  LADDER_CHECK_LAUNCH();
-  hipLaunchKernelGGL(emgmm_stats_kernel, dim3(K, sp.nsplit), dim3(256), 0, stream, X, (const double*)resp, state, moments, N, K, R, sp.rows, part);
-  LADDER_CHECK_LAUNCH();
-  hipLaunchKernelGGL(emgmm_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, (const double*)part, (const double*)lpn_part, state, K, R,
-                     sp.nsplit, G, stats);
-  LADDER_CHECK_LAUNCH();
-  return LADDER_OK;
+  return fit_sliced_estep(emgmm_estep_kernel, false, X, N, K, R, labels, state, em_state_doubles(K, R), moments, stats, ws, ws_bytes,
+                          stream);
 }
 
 int ladder_emgmm_mstep(const double* stats, const double* moments, int K, int R, double* state, double reg_covar, double tol, int max_iter, int it,

@@ -1,9 +1,14 @@
-// The float64 MFMA pieces of the two wide mixture fits (csrc/emgmm.hip: EM on z; csrc/vbgmm.hip, the vbwide_* kernels: variational Bayes on t),
+// What the two wide mixture fits share on the float64 MFMA (csrc/emgmm.hip: EM on z; csrc/vbgmm.hip, the vbwide_* kernels: variational Bayes on t),
 // 1 <= R <= 64, 1 <= K <= 64:
-//   fit_slice_rows / fit_stage_component / fit_whiten_sq   the whitening quadratic form |(x - mu_k) P_k|^2 of a 64-sample slice
-//   fit_stats_pass / fit_stats_reduce                      n_k, sum r x~, sum r x~ x~^T over row splits, then the splits in index order
+//   fit_estep_slice<Policy>                                the E-step of a 64-sample slice: one-hot start, the whitening quadratic form
+//                                                          |(x - mu_k) P_k|^2 (fit_slice_rows / fit_stage_component / fit_whiten_sq), logsumexp per
+//                                                          row; the policy states the fit's constants, log term and per-row finish
+//   fit_colsum_kernel / fit_stats_kernel / fit_reduce_kernel   column sums; n_k, sum r x~, sum r x~ x~^T over row splits; the splits in index order
+//   fit_sliced_estep / fit_sliced_workspace_bytes          the host side of an E-step: checks, workspace, the three launches
+//   FitStats, fit_centre_mean / fit_centred_cov            the view into `stats`; the shifted raw moments centred in the M-step
 //   fit_chol_inverse                                       Cholesky factor and its triangular inverse in LDS, by one wavefront
-// The callers are __global__ wrappers that test their own state's `done` flag first.  No atomics: every sum has one fixed order.
+// Each of the two files instantiates its own copy of the three kernels; they find the `done` flag through the state's tail pointer (fit_util.h).
+// No atomics: every sum has one fixed order.
 //
 // Operand lane maps of v_mfma_f64_16x16x4_f64: head of csrc/fid.hip (A [m = lane & 15][k = lane >> 4], B [k][n = lane & 15],
 // C/D reg r: row (lane >> 4) + 4 r, col lane & 15).
@@ -20,6 +25,18 @@ constexpr int FIT_LDC = 65;             // LDS row pitch of the M-step's factori
 // stats = [ one scalar | n_k [K] | sum r x~ [K,R] | sum r x~ x~^T [K,R,R] ]: one buffer, one all-reduce
 __host__ __device__ inline size_t fit_stats_doubles(int K, int R) { return 1 + (size_t)K * (1 + R + (size_t)R * R); }
 inline int fit_slices(int N) { return (N + FIT_SLICE - 1) / FIT_SLICE; }
+// n_k [K] from component 0, sum r x~ [R] and sum r x~ x~^T [R,R] from component k on (T: double or const double)
+template <class T>
+struct FitStats {
+  T *nk, *x, *xx;
+  __device__ FitStats(T* stats, int K, int R, int k = 0) : nk(stats + 1), x(nk + K + (size_t)k * R), xx(nk + K + (size_t)K * R + (size_t)k * R * R) {}
+};
+
+// workspace of a sliced E-step: responsibilities [N, K] | per-slice scalars | per-split partial statistics
+inline size_t fit_sliced_workspace_bytes(int N, int K, int R) {
+  if (N < 1 || K < 1 || R < 1) return 0;
+  return ((size_t)N * K + (size_t)fit_slices(N) + (size_t)fit_split(N).nsplit * fit_stats_doubles(K, R)) * sizeof(double);
+}
 
 // moments = [ sum_n x_n [R] | N | ... ], all-reduced by the caller: the shift is the GLOBAL mean rounded to fp32, the same on every rank
 __device__ __forceinline__ double fit_shift(const double* mom, int R, int j) { return (double)(float)(mom[j] / mom[R]); }
@@ -72,12 +89,77 @@ __device__ __forceinline__ void fit_whiten_sq(const double (&xa)[16], const doub
     for (int o = 1; o < 16; o <<= 1) q4[r] += __shfl_xor(q4[r], o, 64);      // over the 16 columns of the lane group: the same bits in every lane
 }
 
+// The E-step of slice blockIdx.x (FIT_SLICE samples, 256 threads).  labels != nullptr (iteration 0): the one-hot responsibilities, slice scalar 0.
+// Else per component k: P_k = pchol[k] (upper triangular) and means[k] staged in LDS, resp[n][k] = pol.log_term(s_c, k, |(x_n - mu_k) P_k|^2);
+// after the last k each row's logsumexp `lse`, then pol.finish_row(row, K, lse) turns the log terms into responsibilities and returns the row's
+// share of the slice scalar, summed over the rows by wavefront 0 into slice_part[blockIdx.x].  Policy::NCONST constants per component live in LDS
+// (s_c, FIT_MAXK apart), loaded by pol.load(s_c, k).
+template <class Policy>
+__device__ __forceinline__ void fit_estep_slice(const Policy& pol, const float* __restrict__ X, const int* __restrict__ labels, const double* pchol,
+                                                const double* means, int N, int K, int R, double* resp, double* __restrict__ slice_part) {
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, m = lane & 15, kq = lane >> 4;
+  const int n0 = blockIdx.x * FIT_SLICE, rows = min(FIT_SLICE, N - n0);
+  if (labels != nullptr) {
+    fit_onehot(labels + n0, rows, K, resp + (size_t)n0 * K, tid, 256);
+    if (tid == 0) slice_part[blockIdx.x] = 0.0;
+    return;
+  }
+  __shared__ double s_P[FIT_MAXR * FIT_LDP], s_mu[FIT_MAXR], s_c[Policy::NCONST * FIT_MAXK];
+  const int nb = (R + 15) / 16, Rp = nb * 16, nsteps = (R + 3) / 4;
+  double xa[16];                                                   // this lane's A operands: x[row][4 s + kq], zero past R
+  fit_slice_rows(X, n0, rows, R, wave * 16 + m, kq, xa);
+  if (tid < K) pol.load(s_c, tid);
+  for (int k = 0; k < K; ++k) {
+    __syncthreads();                                               // (the previous component's operands are no longer read)
+    fit_stage_component(pchol + (size_t)k * R * R, means + k * R, R, Rp, s_P, s_mu, tid);
+    __syncthreads();
+    double q4[4];
+    fit_whiten_sq(xa, s_mu, s_P, nb, nsteps, m, kq, q4);
+    if (m == 0) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int rr = wave * 16 + kq + 4 * r;
+        if (rr < rows) resp[(size_t)(n0 + rr) * K + k] = pol.log_term(s_c, k, q4[r]);
+      }
+    }
+  }
+  __syncthreads();
+  double a = 0.0;
+  if (tid < rows) {
+    double* wr = resp + (size_t)(n0 + tid) * K;
+    double mx = -INFINITY;
+    for (int k = 0; k < K; ++k) mx = fmax(mx, wr[k]);
+    double se = 0.0;
+    for (int k = 0; k < K; ++k) se += exp(wr[k] - mx);
+    a = pol.finish_row(wr, K, log(se) + mx);
+  }
+  if (wave == 0) {
+    a = wave_sum_d(a);
+    if (lane == 0) slice_part[blockIdx.x] = a;
+  }
+}
+
 // ------------------------------------------------------------------------------------------------ statistics
+// The three kernels both fits launch; each translation unit instantiates its own copy.
+namespace {
+
+// mom = [ sum_n x_n [R] | N ]: one workgroup per column (column_sum_256)
+__global__ __launch_bounds__(256) void fit_colsum_kernel(const float* __restrict__ X, int N, int R, double* __restrict__ mom) {
+  const int j = blockIdx.x, tid = threadIdx.x;
+  __shared__ double s_red[4];
+  const double a = column_sum_256(X, N, R, j, s_red, tid);
+  if (tid == 0) {
+    mom[j] = a;
+    if (j == 0) mom[R] = (double)N;
+  }
+}
+
 // Grid (component, row split), 256 threads.  Wavefront w owns rows 16 w .. 16 w + 15 of the R x R moment: the column blocks q >= w as MFMA
 // accumulators, plus one block whose B operand is the unit column e_0, which collects sum r x~ in its column 0.  Operands come straight from global
 // memory; x~ = x - c with ONE shift vector c for all components (fit_shift).  Partials of split s go to part + s * fit_stats_doubles(K, R).
-__device__ __forceinline__ void fit_stats_pass(const float* __restrict__ X, const double* __restrict__ resp, const double* __restrict__ mom, int N, int K,
-                                               int R, int rows, double* __restrict__ part) {
+__global__ __launch_bounds__(256) void fit_stats_kernel(const float* __restrict__ X, const double* __restrict__ resp, const double* __restrict__ tail,
+                                                        const double* __restrict__ mom, int N, int K, int R, int rows, double* __restrict__ part) {
+  if (fit_done(tail)) return;
   const int k = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, m = lane & 15, kq = lane >> 4;
   const int nb = (R + 15) / 16;
   if (wave >= nb) return;                                          // (whole wavefronts; no barrier in this pass)
@@ -115,30 +197,29 @@ __device__ __forceinline__ void fit_stats_pass(const float* __restrict__ X, cons
     }
     acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(a, e0, acc1, 0, 0, 0);
   }
-  double* out = part + (size_t)blockIdx.y * fit_stats_doubles(K, R);
-  double* p_nk = out + 1;
-  double* p_x = p_nk + K + (size_t)k * R;
-  double* p_xx = out + 1 + K + (size_t)K * R + (size_t)k * R * R;
+  const FitStats<double> p(part + (size_t)blockIdx.y * fit_stats_doubles(K, R), K, R, k);
   if (wave == 0) {                                                 // n_k: the rows r0 + kq + 4 t of lane group kq, then the four groups in order
     const double g0 = __shfl(nk, 0, 64), g1 = __shfl(nk, 16, 64), g2 = __shfl(nk, 32, 64), g3 = __shfl(nk, 48, 64);
-    if (lane == 0) p_nk[k] = ((g0 + g1) + g2) + g3;
+    if (lane == 0) p.nk[k] = ((g0 + g1) + g2) + g3;
   }
 #pragma unroll
   for (int rg = 0; rg < 4; ++rg) {
     const int i = wave * 16 + kq + 4 * rg;
     if (i >= R) continue;
-    if (m == 0) p_x[i] = acc1[rg];
+    if (m == 0) p.x[i] = acc1[rg];
 #pragma unroll
     for (int q = 0; q < 4; ++q)
-      if (q >= wave && q < nb && vb[q]) p_xx[(size_t)i * R + jb[q]] = acc[q][rg];
+      if (q >= wave && q < nb && vb[q]) p.xx[(size_t)i * R + jb[q]] = acc[q][rg];
   }
 }
 
 // stats[e] = sum over the splits in index order, a thread per element (grid ceil(fit_stats_doubles / 256) x 256 threads); of the second moments
 // only [i][j], i <= j, was computed: the lower triangle reads its mirror, so the moment is exactly symmetric.  Element 0 = the slices' scalar
 // partials in slice order.
-__device__ __forceinline__ void fit_stats_reduce(const double* __restrict__ part, const double* __restrict__ slice_part, int K, int R, int nsplit,
-                                                 int nslices, double* __restrict__ stats) {
+__global__ __launch_bounds__(256) void fit_reduce_kernel(const double* __restrict__ part, const double* __restrict__ slice_part,
+                                                         const double* __restrict__ tail, int K, int R, int nsplit, int nslices,
+                                                         double* __restrict__ stats) {
+  if (fit_done(tail)) return;
   const size_t n = fit_stats_doubles(K, R), e = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (e >= n) return;
   double a = 0.0;
@@ -154,6 +235,51 @@ __device__ __forceinline__ void fit_stats_reduce(const double* __restrict__ part
     for (int s = 0; s < nsplit; ++s) a += part[(size_t)s * n + src];
   }
   stats[e] = a;
+}
+
+}  // namespace
+
+// The host side of a sliced E-step: `estep` (signature of fit_estep_slice's wrappers) over the slices, then the statistics and their reduction.
+// state_doubles: the length of `state`, whose tail holds `done`; bad_shape: what the caller refuses beyond the checks below.
+template <class EstepKernel>
+inline int fit_sliced_estep(EstepKernel estep, bool bad_shape, const float* X, int N, int K, int R, const int* labels, const double* state,
+                            size_t state_doubles, const double* moments, double* stats, void* ws, size_t ws_bytes, ladder_stream_t stream) {
+  if (bad_shape || X == nullptr || state == nullptr || moments == nullptr || stats == nullptr || N < 1 || K < 1 || K > FIT_MAXK || R < 1 || R > FIT_MAXR)
+    return LADDER_E_SHAPE;
+  if (fit_misaligned(state) || fit_misaligned(moments) || fit_misaligned(stats) || fit_misaligned(ws)) return LADDER_E_ALIGN;
+  if (ws == nullptr || ws_bytes < fit_sliced_workspace_bytes(N, K, R)) return LADDER_E_WORKSPACE;
+  const FitSplit sp = fit_split(N);
+  const int G = fit_slices(N);
+  const size_t n = fit_stats_doubles(K, R);
+  const double* tail = fit_tail(state, state_doubles);
+  double* resp = static_cast<double*>(ws);
+  double* slice_part = resp + (size_t)N * K;
+  double* part = slice_part + G;
+  hipLaunchKernelGGL(estep, dim3(G), dim3(256), 0, stream, X, labels, state, N, K, R, resp, slice_part);
+  LADDER_CHECK_LAUNCH();
+  hipLaunchKernelGGL(fit_stats_kernel, dim3(K, sp.nsplit), dim3(256), 0, stream, X, (const double*)resp, tail, moments, N, K, R, sp.rows, part);
+  LADDER_CHECK_LAUNCH();
+  hipLaunchKernelGGL(fit_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, (const double*)part, (const double*)slice_part, tail, K, R,
+                     sp.nsplit, G, stats);
+  LADDER_CHECK_LAUNCH();
+  return LADDER_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ the M-step's centring
+// Component k's moments about the shift c (FitStats) -> sum r x / nk, with s1 and d = mean - c left in LDS for fit_centred_cov.  Thread j < R.
+__device__ __forceinline__ double fit_centre_mean(const double* mom, int R, int j, double s1, double nk_raw, double nk, double* s_s1, double* s_dm) {
+  const double c = fit_shift(mom, R, j);
+  const double mean = (s1 + c * nk_raw) / nk;
+  s_s1[j] = s1;
+  s_dm[j] = mean - c;
+  return mean;
+}
+
+// sum r (x - mean)(x - mean)^T / nk + reg_covar at [i][j] = (S2 - s1 d^T - d s1^T + n_k d d^T) / nk from xx = S2[i][j]; after a barrier.
+__device__ __forceinline__ double fit_centred_cov(double xx, const double* s_s1, const double* s_dm, int i, int j, double nk_raw, double nk,
+                                                  double reg_covar) {
+  const double v = xx - (s_s1[i] * s_dm[j] + s_dm[i] * s_s1[j]) + nk_raw * s_dm[i] * s_dm[j];
+  return v / nk + (i == j ? reg_covar : 0.0);
 }
 
 // ------------------------------------------------------------------------------------------------ factorisation

@@ -21,7 +21,7 @@
 //   kmeans_assign_kernel   a workgroup owns 64 samples: the shifted centres (zero-padded to multiples of 16 x 4) and their squared norms are staged in
 //                          LDS, |c_k|^2 - 2 x~.c_k comes from v_mfma_f64_16x16x4_f64, row argmin with the lowest index winning (numpy.argmin); the
 //                          label, the squared distance to the own centre by direct differences, integer counters: samples per cluster, changed labels
-//   kmeans_sums_kernel     onehot(labels)^T x~ over row splits on the same MFMA (emgmm_stats_kernel at it == 0); partials per split
+//   kmeans_sums_kernel     onehot(labels)^T x~ over row splits on the same MFMA (fit_stats_kernel at it == 0); partials per split
 //   kmeans_update_kernel   ONE workgroup: partials added in split order, empty-cluster relocation, new centres, sum |c_new - c_old|^2, the convergence
 //                          test of _kmeans_single_lloyd: labels unchanged -> strict convergence, the labels stand; else shift <= tol_ or it == max_iter
 //                          -> ONE more assignment against the final centres (the next assign / update pair, which only sums inertia_ and sets `done`).

@@ -5,9 +5,11 @@
 //
 // The problem is tiny and strictly sequential (N ~ 2e3..2e4 samples of R <= 8 dims, K <= 64 components, 10..1000 dependent E/M
 // iterations; a representation of 9 .. 64 dims takes the vbwide_* kernels at the end of this file, on the float64 MFMA).  Arithmetic is float64 like sklearn's; every reduction has one fixed order, so a fit gives the same bits on every run
-// and on every rank.  Two paths call the SAME device functions (vb_*) for all that sklearn defines -- the one-hot start, the E-step, the
+// and on every rank.  Two paths call the SAME device functions (vb_*) for all that sklearn defines -- the E-step, the
 // Dirichlet / Wishart update with its Cholesky and inverse, the lower bound, _set_parameters (the wide fit calls vb_digamma, vb_estep_constant,
-// vb_log_wishart_term, vb_lower_bound and vb_write_feed too, and takes its E-step, statistics and factorisation from csrc/fit_mfma.h):
+// vb_log_wishart_term, vb_lower_bound and vb_write_feed too, and takes its E-step body, statistics, centring and factorisation from
+// csrc/fit_mfma.h); the one-hot start, the `done` test and the end of an iteration (fit_end_iteration) are those of csrc/fit_util.h, which the EM
+// fit of csrc/emgmm.hip follows too:
 //   vbgmm_fit_kernel                   below 1 024 samples: ONE persistent workgroup of 16 wavefronts keeps the whole VB loop in one launch
 //   vbgmm_shard_{estep,mstep}_kernel   every other fit: an E-step launch over 256-sample slices + an M-step launch per iteration, the samples
 //                                      possibly sharded over the data-parallel ranks
@@ -52,11 +54,6 @@ struct VbState {
 };
 
 // ---------------------------------------------------------------------------------------------------------------- shared by both paths
-// _initialize_parameters: one-hot responsibilities from the k-means labels
-__device__ __forceinline__ void vb_onehot(const int* __restrict__ labels, int N, int K, double* __restrict__ resp, int tid, int nthreads) {
-  for (size_t i = tid; i < (size_t)N * K; i += nthreads) resp[i] = (labels[i / K] == (int)(i % K)) ? 1.0 : 0.0;
-}
-
 // What _estimate_log_prob + _estimate_log_weights give per component, all but the quadratic form: Pk = precisions_cholesky_[k] (global memory or an
 // LDS copy), dig_sum = digamma(sum_k wa) (dirichlet_distribution only).  s_stick, if given, holds digamma(wb_j) - digamma(wa_j + wb_j) per component:
 // the stick-breaking prefix adds the same terms in the same order either way.
@@ -275,7 +272,7 @@ __global__ __launch_bounds__(VB_THREADS) void vbgmm_fit_kernel(const float* __re
     a = wave_sum_d(a);
     if (lane == 0) s_prior_cov[p] = a / (N - 1);
   }
-  if (c.init_from_labels) vb_onehot(labels, N, K, resp, tid, VB_THREADS);
+  if (c.init_from_labels) fit_onehot(labels, N, K, resp, tid, VB_THREADS);
   __syncthreads();
   double lower_bound = c.init_from_labels ? -INFINITY : S.tail[FIT_LB];
   int n_iter = 0, converged = 0;
@@ -371,7 +368,7 @@ __global__ __launch_bounds__(VB_THREADS) void vbgmm_shard_estep_kernel(const flo
                                                                        double* __restrict__ stats, const int per, const size_t stats_stride) {
   const int K = c.K, R = c.R, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   VbState S(const_cast<double*>(state), K, R);
-  if (S.tail[FIT_DONE] != 0.0) return;                           // the fit is over: later (speculatively enqueued) iterations are no-ops
+  if (fit_done(S.tail)) return;                                  // the fit is over: later (speculatively enqueued) iterations are no-ops
   const int n_first = blockIdx.x * per, N = min(per, c.N - n_first);
   X += (size_t)n_first * R;
   if (labels != nullptr) labels += n_first;
@@ -379,12 +376,12 @@ __global__ __launch_bounds__(VB_THREADS) void vbgmm_shard_estep_kernel(const flo
   stats += (size_t)blockIdx.x * stats_stride;
   __shared__ double s_ck[VB_MAXK], s_mu[VB_MAXK * VB_MAXR], s_pc[VB_MAXK * VB_MAXR * VB_MAXR], s_red[VB_WAVES], s_scal[1];
   double entropy = 0.0;
-  if (c.init_from_labels) vb_onehot(labels, N, K, resp, tid, VB_THREADS);
+  if (c.init_from_labels) fit_onehot(labels, N, K, resp, tid, VB_THREADS);
   else entropy = vb_estep(X, N, S, c, s_mu, s_pc, s_ck, s_scal, s_red, resp, tid);
   __syncthreads();
   // local sufficient statistics (fixed order: lane-strided partial sums, then the shuffle tree)
   if (tid == 0) stats[0] = entropy;
-  double *st_nk = stats + 1, *st_x = st_nk + K, *st_xx = st_x + (size_t)K * R;
+  const FitStats<double> st(stats, K, R);
   for (int p = wave; p < K * (1 + R + R * R); p += VB_WAVES) {
     double a = 0.0;
     if (p < K) {
@@ -399,21 +396,20 @@ __global__ __launch_bounds__(VB_THREADS) void vbgmm_shard_estep_kernel(const flo
     }
     a = wave_sum_d(a);
     if (lane == 0) {
-      if (p < K) st_nk[p] = a;
-      else if (p < K + K * R) st_x[p - K] = a;
+      if (p < K) st.nk[p] = a;
+      else if (p < K + K * R) st.x[p - K] = a;
       else {
         const int q = p - K - K * R, k = q / (R * R), ij = q - k * R * R, i = ij / R, j = ij - i * R;
-        st_xx[(size_t)k * R * R + i * R + j] = a;
-        st_xx[(size_t)k * R * R + j * R + i] = a;
+        st.xx[(size_t)k * R * R + i * R + j] = a;
+        st.xx[(size_t)k * R * R + j * R + i] = a;
       }
     }
   }
 }
 
-__global__ __launch_bounds__(256) void vbgmm_stats_reduce_kernel(const double* __restrict__ partial, const double* __restrict__ state,
-                                                                 int K, int R, int G, int n, double* __restrict__ stats) {
-  VbState S(const_cast<double*>(state), K, R);
-  if (S.tail[FIT_DONE] != 0.0) return;
+__global__ __launch_bounds__(256) void vbgmm_stats_reduce_kernel(const double* __restrict__ partial, const double* __restrict__ tail, int G, int n,
+                                                                 double* __restrict__ stats) {
+  if (fit_done(tail)) return;
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
   double a = 0.0;
@@ -426,45 +422,32 @@ __global__ __launch_bounds__(256) void vbgmm_shard_mstep_kernel(const double* __
                                                                 float* __restrict__ m_out, float* __restrict__ c_out) {
   const int K = c.K, R = c.R, tid = threadIdx.x;
   VbState S(state, K, R);
-  if (S.tail[FIT_DONE] != 0.0) return;
+  if (fit_done(S.tail)) return;
   __shared__ double s_nk[VB_MAXK], s_xk[VB_MAXK * VB_MAXR], s_sk[VB_MAXK * VB_MAXR * VB_MAXR], s_ck[VB_MAXK];
   __shared__ double s_prior_mean[VB_MAXR], s_prior_cov[VB_MAXR * VB_MAXR];
   __shared__ int s_flag, s_done;
   const double Ntot = moments[0];
   if (tid < R) s_prior_mean[tid] = moments[1 + tid] / Ntot;
-  if (tid == 0) { s_flag = 0; s_done = 0; }
+  if (tid == 0) s_flag = 0;
   __syncthreads();
   if (tid < R * R) {
     const int i = tid / R, j = tid - i * R;
     s_prior_cov[tid] = (moments[1 + R + tid] - Ntot * s_prior_mean[i] * s_prior_mean[j]) / (Ntot - 1.0);
   }
-  const double *st_nk = stats + 1, *st_x = st_nk + K, *st_xx = st_x + (size_t)K * R;
-  if (tid < K) s_nk[tid] = st_nk[tid] + kEps10;
+  const FitStats<const double> st(stats, K, R);
+  if (tid < K) s_nk[tid] = st.nk[tid] + kEps10;
   __syncthreads();
-  for (int p = tid; p < K * R; p += 256) s_xk[p] = st_x[p] / s_nk[p / R];
+  for (int p = tid; p < K * R; p += 256) s_xk[p] = st.x[p] / s_nk[p / R];
   __syncthreads();
   // the raw second moments, centred here
   for (int p = tid; p < K * R * R; p += 256) {
     const int k = p / (R * R), ij = p - k * R * R, i = ij / R, j = ij - i * R;
-    s_sk[p] = st_xx[p] / s_nk[k] - s_xk[k * R + i] * s_xk[k * R + j] + (i == j ? c.reg_covar : 0.0);
+    s_sk[p] = st.xx[p] / s_nk[k] - s_xk[k * R + i] * s_xk[k * R + j] + (i == j ? c.reg_covar : 0.0);
   }
   __syncthreads();
   if (tid < K) vb_update_component(tid, S, c, s_nk, s_xk, s_sk, s_prior_mean, s_prior_cov, &s_flag);
   __syncthreads();
-  if (tid == 0) {
-    if (s_flag) {                                                  // ill-defined empirical covariance (sklearn raises)
-      S.tail[FIT_CONVERGED] = -1.0; S.tail[FIT_DONE] = 1.0; s_done = 2;
-    } else if (it == 0) {
-      S.tail[FIT_LB] = -INFINITY; S.tail[FIT_NITER] = 0.0;         // _initialize: no lower bound yet
-      if (c.max_iter == 0) { S.tail[FIT_DONE] = 1.0; s_done = 1; }
-    } else {
-      const double lb = vb_lower_bound(S, c, stats[0]);
-      const bool conv = fabs(lb - S.tail[FIT_LB]) < c.tol;
-      S.tail[FIT_LB] = lb; S.tail[FIT_NITER] = (double)it;
-      if (conv) { S.tail[FIT_CONVERGED] = 1.0; S.tail[FIT_DONE] = 1.0; s_done = 1; }
-      else if (it >= c.max_iter) { S.tail[FIT_DONE] = 1.0; s_done = 1; }
-    }
-  }
+  if (tid == 0) s_done = fit_end_iteration(S.tail, s_flag != 0, it, c.tol, c.max_iter, [&] { return vb_lower_bound(S, c, stats[0]); });
   __syncthreads();
   if (s_done != 1) return;
   vb_write_feed(S, c, s_ck, w_out, m_out, c_out, tid, 256);
@@ -474,28 +457,20 @@ __global__ __launch_bounds__(256) void vbgmm_shard_mstep_kernel(const double* __
 // The thread-per-sample E-step above keeps a sample in registers and every factor in LDS, which ends at R = 8.  Past it one variational iteration
 // keeps the protocol of the sharded fit -- E-step + local statistics / all-reduce / M-step + convergence test, every kernel a no-op once `done` is
 // set -- on the float64 MFMA passes of csrc/fit_mfma.h, which the EM fit (csrc/emgmm.hip) runs too:
-//   vbwide_estep_kernel    a workgroup owns 64 samples; per component the whitening quadratic form |(x - mean_k) P_k|^2, then w = ck[k] - q / 2 with
-//                          the constants the finish kernel left in the state; logsumexp, responsibilities, the slice's sum r log r
-//   vbwide_stats_kernel    n_k, sum r x~, sum r x~ x~^T about ONE shift c (the fp32-rounded global mean) over row splits; vbwide_reduce_kernel adds
+//   vbwide_estep_kernel    fit_estep_slice under the policy VbwEstep: a workgroup owns 64 samples; per component the whitening quadratic form
+//                          |(x - mean_k) P_k|^2, then w = ck[k] - q / 2 with the constants the finish kernel left in the state; logsumexp,
+//                          responsibilities, the slice's sum r log r
+//   fit_stats_kernel       n_k, sum r x~, sum r x~ x~^T about ONE shift c (the fp32-rounded global mean) over row splits; fit_reduce_kernel adds
 //                          the splits (and the slices' sum r log r) in index order: stats = [ sum r log r | n_k | sum r x~ | sum r x~ x~^T ]
 //   (all-reduce of stats, by the caller)
 //   vbwide_mstep_kernel    one workgroup per component: weight parameters, mean precision, mean, the Wishart covariance from the shifted moments
-//                          centred here, Cholesky factor and triangular inverse in LDS; a non-positive pivot is a status
-//   vbwide_finish_kernel   one workgroup: the next E-step's constants (vb_estep_constant), the lower bound, the convergence test, and at the end of
-//                          the fit _set_parameters + the fp32 feed
+//                          centred here (fit_centre_mean / fit_centred_cov), Cholesky factor and triangular inverse in LDS; a non-positive pivot
+//                          is a status
+//   vbwide_finish_kernel   one workgroup: the next E-step's constants (vb_estep_constant), then fit_end_iteration with vb_lower_bound, and at the
+//                          end of the fit _set_parameters + the fp32 feed
 // moments = [ sum x [R] | N | sum x~ x~^T [R,R] ]: the first R + 1 are all-reduced, then the second moments about the shift they define; from them
 // mean_prior_ = X.mean(0) and covariance_prior_ = cov(X.T) = (sum x~ x~^T - N d d^T) / (N - 1), d = mean_prior_ - c.
 constexpr int VBW_EXTRA = 2;             // ck[K] | cstat[K] between prec_chol and the tail
-
-__global__ __launch_bounds__(256) void vbwide_moments1_kernel(const float* __restrict__ X, int N, int R, double* __restrict__ mom) {
-  const int j = blockIdx.x, tid = threadIdx.x;
-  __shared__ double s_red[4];
-  const double a = column_sum_256(X, N, R, j, s_red, tid);
-  if (tid == 0) {
-    mom[j] = a;
-    if (j == 0) mom[R] = (double)N;
-  }
-}
 
 // grid (R, R): workgroup (j, i), i <= j, sums x~_i x~_j over the local samples and writes both mirrors
 __global__ __launch_bounds__(256) void vbwide_moments2_kernel(const float* __restrict__ X, int N, int R, double* mom) {
@@ -512,73 +487,28 @@ __global__ __launch_bounds__(256) void vbwide_moments2_kernel(const float* __res
   }
 }
 
-__global__ __launch_bounds__(256) void vbwide_estep_kernel(const float* __restrict__ X, const int* __restrict__ labels, const double* state, int N, int K,
-                                                           int R, double* resp, double* __restrict__ ent_part) {
-  VbState S(const_cast<double*>(state), K, R, VBW_EXTRA);
-  if (S.tail[FIT_DONE] != 0.0) return;                             // the fit is over: iterations enqueued past the end are no-ops
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, m = lane & 15, kq = lane >> 4;
-  const int n0 = blockIdx.x * FIT_SLICE, rows = min(FIT_SLICE, N - n0);
-  if (labels != nullptr) {                                         // iteration 0: _initialize_parameters' one-hot responsibilities
-    for (int i = tid; i < rows * K; i += 256) {
-      const int r = i / K, k = i - r * K;
-      resp[(size_t)(n0 + r) * K + k] = (labels[n0 + r] == k) ? 1.0 : 0.0;
-    }
-    if (tid == 0) ent_part[blockIdx.x] = 0.0;
-    return;
-  }
-  __shared__ double s_P[FIT_MAXR * FIT_LDP], s_mu[FIT_MAXR], s_ck[FIT_MAXK];
-  const int nb = (R + 15) / 16, Rp = nb * 16, nsteps = (R + 3) / 4;
-  double xa[16];
-  fit_slice_rows(X, n0, rows, R, wave * 16 + m, kq, xa);
-  if (tid < K) s_ck[tid] = S.ck[tid];
-  for (int k = 0; k < K; ++k) {
-    __syncthreads();                                               // (the previous component's operands are no longer read)
-    fit_stage_component(S.pchol + (size_t)k * R * R, S.means + k * R, R, Rp, s_P, s_mu, tid);
-    __syncthreads();
-    double q4[4];
-    fit_whiten_sq(xa, s_mu, s_P, nb, nsteps, m, kq, q4);
-    if (m == 0) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int rr = wave * 16 + kq + 4 * r;
-        if (rr < rows) resp[(size_t)(n0 + rr) * K + k] = s_ck[k] - 0.5 * q4[r];
-      }
-    }
-  }
-  __syncthreads();
-  double ent = 0.0;
-  if (tid < rows) {                                                // as vb_estep: logsumexp, r = exp(log r), sum r log r
-    double* wr = resp + (size_t)(n0 + tid) * K;
-    double mx = -INFINITY;
-    for (int k = 0; k < K; ++k) mx = fmax(mx, wr[k]);
-    double se = 0.0;
-    for (int k = 0; k < K; ++k) se += exp(wr[k] - mx);
-    const double lse = mx + log(se);
+// _estimate_log_prob_resp as the policy of fit_estep_slice (what vb_estep does per row): the constant ck, the slice scalar is the sum of r log r.
+struct VbwEstep {
+  static constexpr int NCONST = 1;
+  const double* ck;
+  __device__ void load(double* s_c, int k) const { s_c[k] = ck[k]; }
+  __device__ double log_term(const double* s_c, int k, double q) const { return s_c[k] - 0.5 * q; }
+  __device__ double finish_row(double* wr, int K, double lse) const {
+    double ent = 0.0;
     for (int k = 0; k < K; ++k) {
       const double lr = wr[k] - lse, r = exp(lr);
       wr[k] = r;
       ent += r * lr;
     }
+    return ent;
   }
-  if (wave == 0) {
-    ent = wave_sum_d(ent);
-    if (lane == 0) ent_part[blockIdx.x] = ent;
-  }
-}
+};
 
-__global__ __launch_bounds__(256) void vbwide_stats_kernel(const float* __restrict__ X, const double* __restrict__ resp, const double* __restrict__ state,
-                                                           const double* __restrict__ mom, int N, int K, int R, int rows, double* __restrict__ part) {
+__global__ __launch_bounds__(256) void vbwide_estep_kernel(const float* __restrict__ X, const int* __restrict__ labels, const double* state, int N, int K,
+                                                           int R, double* resp, double* __restrict__ ent_part) {
   VbState S(const_cast<double*>(state), K, R, VBW_EXTRA);
-  if (S.tail[FIT_DONE] != 0.0) return;
-  fit_stats_pass(X, resp, mom, N, K, R, rows, part);
-}
-
-__global__ __launch_bounds__(256) void vbwide_reduce_kernel(const double* __restrict__ part, const double* __restrict__ ent_part,
-                                                            const double* __restrict__ state, int K, int R, int nsplit, int nslices,
-                                                            double* __restrict__ stats) {
-  VbState S(const_cast<double*>(state), K, R, VBW_EXTRA);
-  if (S.tail[FIT_DONE] != 0.0) return;
-  fit_stats_reduce(part, ent_part, K, R, nsplit, nslices, stats);
+  if (fit_done(S.tail)) return;
+  fit_estep_slice(VbwEstep{S.ck}, X, labels, S.pchol, S.means, N, K, R, resp, ent_part);
 }
 
 // _m_step for component blockIdx.x, 64 threads: what vb_update_component states per component, with the empirical covariance centred from the
@@ -586,14 +516,12 @@ __global__ __launch_bounds__(256) void vbwide_reduce_kernel(const double* __rest
 __global__ __launch_bounds__(64) void vbwide_mstep_kernel(const double* __restrict__ stats, const double* __restrict__ mom, double* state, VbCfg c) {
   const int K = c.K, R = c.R, k = blockIdx.x, tid = threadIdx.x;
   VbState S(state, K, R, VBW_EXTRA);
-  if (S.tail[FIT_DONE] != 0.0) return;
+  if (fit_done(S.tail)) return;
   __shared__ double s_A[FIT_MAXR * FIT_LDC], s_s1[FIT_MAXR], s_dm[FIT_MAXR], s_dx[FIT_MAXR], s_dp[FIT_MAXR];
-  const double* st_nk = stats + 1;
-  const double* st_x = st_nk + K + (size_t)k * R;
-  const double* st_xx = stats + 1 + K + (size_t)K * R + (size_t)k * R * R;
+  const FitStats<const double> st(stats, K, R, k);
   const double* m2 = mom + R + 1;
   const double Ntot = mom[R];
-  const double nk_raw = st_nk[k], nk = nk_raw + kEps10;            // nk = resp.sum(axis=0) + 10 * eps
+  const double nk_raw = st.nk[k], nk = nk_raw + kEps10;            // nk = resp.sum(axis=0) + 10 * eps
   const double mp = c.mean_prec_prior + nk, dof = (double)R + nk;  // degrees_of_freedom_prior_ = n_features
   if (tid == 0) {
     if (c.prior_type == 0) {
@@ -601,7 +529,7 @@ __global__ __launch_bounds__(64) void vbwide_mstep_kernel(const double* __restri
       S.wb[k] = 0.0;
     } else {
       double tail = 0.0;                                           // sum_{j>k} nk_j
-      for (int j = K - 1; j > k; --j) tail += st_nk[j] + kEps10;
+      for (int j = K - 1; j > k; --j) tail += st.nk[j] + kEps10;
       S.wa[k] = 1.0 + nk;
       S.wb[k] = c.wc_prior + tail;
     }
@@ -609,11 +537,8 @@ __global__ __launch_bounds__(64) void vbwide_mstep_kernel(const double* __restri
     S.dof[k] = dof;
   }
   if (tid < R) {
-    const double cs = fit_shift(mom, R, tid), s1 = st_x[tid];
-    const double xk = (s1 + cs * nk_raw) / nk;                     // = sum r x / nk
+    const double xk = fit_centre_mean(mom, R, tid, st.x[tid], nk_raw, nk, s_s1, s_dm), cs = fit_shift(mom, R, tid);
     const double pm = mom[tid] / Ntot;                             // mean_prior_
-    s_s1[tid] = s1;
-    s_dm[tid] = xk - cs;
     s_dp[tid] = pm - cs;
     s_dx[tid] = xk - pm;
     S.means[k * R + tid] = (c.mean_prec_prior * pm + nk * xk) / mp;
@@ -623,9 +548,7 @@ __global__ __launch_bounds__(64) void vbwide_mstep_kernel(const double* __restri
   for (int e = tid; e < R * R; e += 64) {
     const int i = e / R, j = e - i * R;
     if (j < i) continue;
-    // sk = sum r (x - xk)(x - xk)^T / nk + reg_covar from the shifted moments, d = xk - c
-    double sk = st_xx[e] - (s_s1[i] * s_dm[j] + s_dm[i] * s_s1[j]) + nk_raw * s_dm[i] * s_dm[j];
-    sk = sk / nk + (i == j ? c.reg_covar : 0.0);
+    const double sk = fit_centred_cov(st.xx[e], s_s1, s_dm, i, j, nk_raw, nk, c.reg_covar);
     const double pc = (m2[e] - Ntot * s_dp[i] * s_dp[j]) / (Ntot - 1.0);                        // covariance_prior_
     const double v = (pc + nk * sk + nk * c.mean_prec_prior / mp * (s_dx[i] * s_dx[j])) / dof;   // _estimate_wishart_full
     s_A[i * FIT_LDC + j] = v;
@@ -642,14 +565,13 @@ __global__ __launch_bounds__(256) void vbwide_finish_kernel(const double* __rest
                                                             float* __restrict__ m_out, float* __restrict__ c_out) {
   const int K = c.K, R = c.R, tid = threadIdx.x;
   VbState S(state, K, R, VBW_EXTRA);
-  if (S.tail[FIT_DONE] != 0.0) return;
+  if (fit_done(S.tail)) return;
   __shared__ double s_ck[FIT_MAXK], s_stick[FIT_MAXK], s_lw[FIT_MAXK], s_dig;
   __shared__ int s_done;
   if (tid == 0) {
     double sw = 0.0;
     for (int k = 0; k < K; ++k) sw += S.wa[k];
     s_dig = c.prior_type == 0 ? vb_digamma(sw) : 0.0;
-    s_done = 0;
   }
   if (tid < K) {
     s_stick[tid] = c.prior_type == 0 ? 0.0 : vb_digamma(S.wb[tid]) - vb_digamma(S.wa[tid] + S.wb[tid]);
@@ -660,18 +582,7 @@ __global__ __launch_bounds__(256) void vbwide_finish_kernel(const double* __rest
   if (tid == 0) {
     bool bad = false;
     for (int k = 0; k < K; ++k) bad = bad || (S.cstat[k] < 0.0);
-    if (bad) {                                                     // ill-defined empirical covariance (sklearn raises)
-      S.tail[FIT_CONVERGED] = -1.0; S.tail[FIT_DONE] = 1.0; s_done = 2;
-    } else if (it == 0) {
-      S.tail[FIT_LB] = -INFINITY; S.tail[FIT_NITER] = 0.0;         // _initialize: no lower bound yet
-      if (c.max_iter == 0) { S.tail[FIT_DONE] = 1.0; s_done = 1; }
-    } else {
-      const double lb = vb_lower_bound(S, c, stats[0], s_lw);
-      const bool conv = fabs(lb - S.tail[FIT_LB]) < c.tol;
-      S.tail[FIT_LB] = lb; S.tail[FIT_NITER] = (double)it;
-      if (conv) { S.tail[FIT_CONVERGED] = 1.0; S.tail[FIT_DONE] = 1.0; s_done = 1; }
-      else if (it >= c.max_iter) { S.tail[FIT_DONE] = 1.0; s_done = 1; }
-    }
+    s_done = fit_end_iteration(S.tail, bad, it, c.tol, c.max_iter, [&] { return vb_lower_bound(S, c, stats[0], s_lw); });
   }
   __syncthreads();
   if (s_done != 1) return;
@@ -734,7 +645,9 @@ int ladder_vbgmm_shard_estep(const float* X, int N, int K, int R, const int* lab
   // one slice writes `stats` itself; several write per-slice partials, reduced in slice order
   hipLaunchKernelGGL(vbgmm_shard_estep_kernel, dim3(G), dim3(VB_THREADS), 0, stream, X, labels, state, c, resp, G == 1 ? stats : partial, VB_SLICE,
                      (size_t)(G == 1 ? 0 : n));
-  if (G > 1) hipLaunchKernelGGL(vbgmm_stats_reduce_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, (const double*)partial, state, K, R, G, n, stats);
+  if (G > 1)
+    hipLaunchKernelGGL(vbgmm_stats_reduce_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, (const double*)partial,
+                       fit_tail(state, ladder_vbgmm_state_doubles(K, R)), G, n, stats);
   LADDER_CHECK_LAUNCH();
   return LADDER_OK;
 }
@@ -759,16 +672,12 @@ size_t ladder_vbgmm_wide_state_doubles(int K, int R) { return (K < 1 || R < 1) ?
 size_t ladder_vbgmm_wide_stats_doubles(int K, int R) { return (K < 1 || R < 1) ? 0 : fit_stats_doubles(K, R); }
 size_t ladder_vbgmm_wide_moments_doubles(int R) { return R < 1 ? 0 : (size_t)R + 1 + (size_t)R * R; }
 
-size_t ladder_vbgmm_wide_workspace_bytes(int N, int K, int R) {
-  if (N < 1 || K < 1 || R < 1) return 0;
-  // responsibilities [N, K] | per-slice sums of r log r | per-split partial statistics
-  return ((size_t)N * K + (size_t)fit_slices(N) + (size_t)fit_split(N).nsplit * fit_stats_doubles(K, R)) * sizeof(double);
-}
+size_t ladder_vbgmm_wide_workspace_bytes(int N, int K, int R) { return fit_sliced_workspace_bytes(N, K, R); }
 
 int ladder_vbgmm_wide_moments(const float* X, int N, int R, double* moments, int pass, ladder_stream_t stream) {
   if (X == nullptr || moments == nullptr || N < 1 || R < 1 || R > FIT_MAXR || (pass != 0 && pass != 1)) return LADDER_E_SHAPE;
   if (fit_misaligned(moments)) return LADDER_E_ALIGN;
-  if (pass == 0) hipLaunchKernelGGL(vbwide_moments1_kernel, dim3(R), dim3(256), 0, stream, X, N, R, moments);
+  if (pass == 0) hipLaunchKernelGGL(fit_colsum_kernel, dim3(R), dim3(256), 0, stream, X, N, R, moments);
   else hipLaunchKernelGGL(vbwide_moments2_kernel, dim3(R, R), dim3(256), 0, stream, X, N, R, moments);
   LADDER_CHECK_LAUNCH();
   return LADDER_OK;
@@ -776,23 +685,8 @@ int ladder_vbgmm_wide_moments(const float* X, int N, int R, double* moments, int
 
 int ladder_vbgmm_wide_estep(const float* X, int N, int K, int R, const int* labels, const double* state, int prior_type, const double* moments,
                             double* stats, void* ws, size_t ws_bytes, ladder_stream_t stream) {
-  if (X == nullptr || state == nullptr || moments == nullptr || stats == nullptr || N < 1 || vbw_bad_shape(K, R, prior_type)) return LADDER_E_SHAPE;
-  if (fit_misaligned(state) || fit_misaligned(moments) || fit_misaligned(stats) || fit_misaligned(ws)) return LADDER_E_ALIGN;
-  if (ws == nullptr || ws_bytes < ladder_vbgmm_wide_workspace_bytes(N, K, R)) return LADDER_E_WORKSPACE;
-  const FitSplit sp = fit_split(N);
-  const int G = fit_slices(N);
-  const size_t n = fit_stats_doubles(K, R);
-  double* resp = static_cast<double*>(ws);
-  double* ent_part = resp + (size_t)N * K;
-  double* part = ent_part + G;
-  hipLaunchKernelGGL(vbwide_estep_kernel, dim3(G), dim3(256), 0, stream, X, labels, state, N, K, R, resp, ent_part);
-  LADDER_CHECK_LAUNCH();
-  hipLaunchKernelGGL(vbwide_stats_kernel, dim3(K, sp.nsplit), dim3(256), 0, stream, X, (const double*)resp, state, moments, N, K, R, sp.rows, part);
-  LADDER_CHECK_LAUNCH();
-  hipLaunchKernelGGL(vbwide_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, (const double*)part, (const double*)ent_part, state, K,
-                     R, sp.nsplit, G, stats);
-  LADDER_CHECK_LAUNCH();
-  return LADDER_OK;
+  return fit_sliced_estep(vbwide_estep_kernel, prior_type != 0 && prior_type != 1, X, N, K, R, labels, state,
+                          ladder_vbgmm_wide_state_doubles(K, R), moments, stats, ws, ws_bytes, stream);
 }
 
 int ladder_vbgmm_wide_mstep(const double* stats, const double* moments, int K, int R, double* state, int prior_type, double wc_prior,

@@ -34,6 +34,8 @@ CASES = [
     (1300, 64, 3, 200, 5, 0.25, 8, (7, 3)),        # R at the limit
     (5003, 2, 12, 2000, 5, 1.5, 5, (9, 5)),        # many slices
     (4099, 64, 30, 3, 30, 0.3, 2, (3, None)),      # full K R width, unconverged; the refit would leave a component 15 samples in 64 dimensions
+    (129, 5, 1, 200, 3, 1.0, 5, (2, 3)),           # two full slices and a one-sample slice, K = 1
+    (257, 17, 2, 200, 3, 0.5, 4, (4, 5)),          # two components at an R just past a tile, one-sample last slice
 ]
 KW = dict(covariance_type="full", tol=1e-3, reg_covar=1e-6, n_init=1, warm_start=True, random_state=7)
 

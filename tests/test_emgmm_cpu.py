@@ -51,7 +51,7 @@ def test_abi_is_declared_exported_and_bound():
     assert int(re.search(r"#define LADDER_ABI_VERSION (\d+)", header).group(1)) == 2
 
 
-@pytest.mark.parametrize("case", [E.CASES[0], E.CASES[2]], ids=["600x3x7", "1100x33x6"])
+@pytest.mark.parametrize("case", [E.CASES[0], E.CASES[2], E.CASES[7], E.CASES[8]], ids=["600x3x7", "1100x33x6", "129x5x1", "257x17x2"])
 def test_numpy_restatement_reproduces_sklearn(case):
     """Cold fit + warm refit: same iteration count and convergence, lower bound and parameters to 1e-10 (measured: lower bound 3e-15, weights 2e-14,
     means 1e-14, covariances 2e-14, precisions_cholesky_ 3e-12, relative to each array's largest magnitude)."""
