@@ -56,7 +56,7 @@ int ladder_conv2d_fwd_kernel_id(int N, int H, int W, int Cin, int Ho, int Wo, in
 /* Kernel the dense calls below dispatch to (strict fp32): 1 = the persistent 128x128x32 kernels of csrc/densef32.hip -- gemm_f32_kernel for
  * ladder_dense_fwd (M x K x N) and ladder_dense_bwd_data (pass its M, N, K: the contraction runs over N), gemm_tn_f32_kernel + the fixed-order
  * split sum for ladder_dense_bwd_weight; M >= 8192, M and the output width multiples of 128, the contraction a multiple of 32 -- 0 = the
- * implicit-GEMM kernels of csrc/igemm.hip. */
+ * implicit-GEMM kernels of csrc/igemm.hip (forward, backward-data) and csrc/igemm_wgrad.hip (backward-weight). */
 /* The two forward-type dense calls with the weight operand K-CONTIGUOUS (strict fp32, shapes for which ladder_dense_fwd_is_persistent is 1; LADDER_E_SHAPE
  * otherwise): y [M,N] = act(x [M,K] . wT^T + bias) with wT [N][K], and dx [M,K] = (dy [M,N] . w^T ...) -- i.e. dx = dy . (w [K][N])^T -- times act'(gate_y).
  * gemm_nt16_f32_kernel (csrc/densef32.hip): v_mfma_f32_16x16x4_f32, both fragments 128-bit LDS reads.  The projected decoder pairs hold both wcat and

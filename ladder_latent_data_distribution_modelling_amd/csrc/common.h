@@ -24,6 +24,15 @@
     default: return LADDER_E_SHAPE;                \
   }
 
+// Host-side dispatch on the split-precision format of a call (LADDER_PREC_F16X3 / _BF16X6 / _BF16X3; split16.h): runs the statement with
+// `constexpr int PP = prec`.  The calling export has checked prec_ok(prec); like the if-chains this replaces, anything else runs as BF16X3.
+#define LADDER_PREC_SWITCH(prec, ...) \
+  switch (prec) {                      \
+    case LADDER_PREC_F16X3: { constexpr int PP = LADDER_PREC_F16X3; __VA_ARGS__; } break;   \
+    case LADDER_PREC_BF16X6: { constexpr int PP = LADDER_PREC_BF16X6; __VA_ARGS__; } break; \
+    default: { constexpr int PP = LADDER_PREC_BF16X3; __VA_ARGS__; }                        \
+  }
+
 static inline bool ladder_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 __device__ __forceinline__ float ladder_act_fn(float v, int act) {

@@ -468,7 +468,7 @@ namespace {
 // the direct filter gradient on the upsampled map accumulates -- the same 25 / 36 as the forward.  The last output row / column are a 1x3 /
 // 3x1 convolution of the 1-D upsampled last row / column of x with the taps w[0][s] + w[1][s] / w[r][0] + w[r][1] (convsplit.hip:
 // ladder_conv3x3_up2_edges), so their contribution is a 1x3 / 3x1 filter gradient E_row[s] / E_col[r] added to dw[0][s], dw[1][s] / dw[r][0],
-// dw[r][1].  Kernel = wgrad3x3_halo_kernel's structure (igemm.hip: 12 wavefronts, 64 ci x 128 co slab, 1x32-pixel patches, LDS-DMA staging,
+// dw[r][1].  Kernel = wgrad3x3_halo_kernel's structure (igemm_wgrad.hip: 12 wavefronts, 64 ci x 128 co slab, 1x32-pixel patches, LDS-DMA staging,
 // double buffered) on ONE parity class per workgroup:
 //   classes (0, b): wavefront -> (filter row dr = 0..2, ci half, co pair); 3 - b column shifts x 2 co blocks = 6 / 4 MFMAs per k-step
 //   (patches are 2 x 32 low-resolution pixels -- the halo overhead halves and one LDS-DMA round trip / barrier carries twice the MFMA work:

@@ -13,6 +13,7 @@
 // pixel, so both operands are read with the transposing LDS read (ds_read_b64_tr_b16) from pixel-major fp16 plane images exactly as in
 // wgrad3x3_split_kernel; each workgroup reduces a run of patches, partials are summed in a fixed order by ladder_reduce_splits.
 #include "split16.h"
+#include "igemm.h"
 
 namespace {
 
@@ -557,15 +558,10 @@ int ladder_conv_rgb_s2_bwd_filter_f32(const float* x, const float* dy, float* dw
   if (!ladder_aligned16(dw)) return LADDER_E_ALIGN;
   const RgbWgradPlan p = plan_rgb_wgrad(N, H, W, Cout);
   if (ws == nullptr || ws_bytes < (size_t)p.splits * (27 * (size_t)Cout + Cout) * sizeof(float)) return LADDER_E_WORKSPACE;
-  float* part = (float*)ws;
-  float* bias_part = db != nullptr ? part + (size_t)p.splits * 27 * Cout : nullptr;
-  hipLaunchKernelGGL(conv_rgb_s2_wgrad_f32_kernel, dim3(p.tiles_co * p.splits), dim3(RW_THREADS), 0, stream, x, dy, part, bias_part, N, H, W, Cout,
+  const WgradTail t = wgrad_tail(ws, p.splits, (size_t)27 * Cout, Cout, dw, db);
+  hipLaunchKernelGGL(conv_rgb_s2_wgrad_f32_kernel, dim3(p.tiles_co * p.splits), dim3(RW_THREADS), 0, stream, x, dy, t.part, t.bias_part, N, H, W, Cout,
                      p.tiles_co, p.pps);
-  LADDER_CHECK_LAUNCH();
-  int rc = ladder_reduce_splits(part, dw, p.splits, (size_t)27 * Cout, stream);
-  if (rc != LADDER_OK) return rc;
-  if (db != nullptr) rc = ladder_reduce_splits(bias_part, db, p.splits, (size_t)Cout, stream);
-  return rc;
+  return t.reduce(stream);
 }
 
 size_t ladder_conv_rgb_s2_bwd_filter_workspace_bytes(int N, int H, int W, int Cout) {
@@ -580,15 +576,10 @@ int ladder_conv_rgb_s2_bwd_filter(const float* x, const float* x_absmax, const f
   if (!ladder_aligned16(dy) || !ladder_aligned16(dw)) return LADDER_E_ALIGN;
   if (ws == nullptr || ws_bytes < ladder_conv_rgb_s2_bwd_filter_workspace_bytes(N, H, W, Cout)) return LADDER_E_WORKSPACE;
   const RgbWgradPlan p = plan_rgb_wgrad(N, H, W, Cout);
-  float* part = (float*)ws;
-  float* bias_part = db != nullptr ? part + (size_t)p.splits * 27 * Cout : nullptr;
-  hipLaunchKernelGGL(conv_rgb_s2_wgrad_kernel, dim3(p.tiles_co * p.splits), dim3(RW_THREADS), 0, stream, x, dy, part, bias_part, N, H, W, Cout,
+  const WgradTail t = wgrad_tail(ws, p.splits, (size_t)27 * Cout, Cout, dw, db);
+  hipLaunchKernelGGL(conv_rgb_s2_wgrad_kernel, dim3(p.tiles_co * p.splits), dim3(RW_THREADS), 0, stream, x, dy, t.part, t.bias_part, N, H, W, Cout,
                      p.tiles_co, p.pps, x_absmax, dy_absmax);
-  LADDER_CHECK_LAUNCH();
-  int rc = ladder_reduce_splits(part, dw, p.splits, (size_t)27 * Cout, stream);
-  if (rc != LADDER_OK) return rc;
-  if (db != nullptr) rc = ladder_reduce_splits(bias_part, db, p.splits, (size_t)Cout, stream);
-  return rc;
+  return t.reduce(stream);
 }
 
 }  // extern "C"

@@ -29,6 +29,7 @@
 #include "split16.h"
 #include "filterbank.h"
 #include "convf32.h"
+#include "igemm.h"
 
 namespace {
 
@@ -810,7 +811,7 @@ __global__ __launch_bounds__(F_THREADS) void conv3x3_halo_split16_kernel(const f
 // One workgroup = 8 wavefronts owns a 64 ci x 128 co slab of dW for all 9 taps (72 MFMA tiles); wavefront (cb, nq) owns ALL 9 taps
 // of a 32 ci x 32 co block (9 tiles, 144 accumulator registers): per 16-pixel K-step one dy fragment serves 27 MFMAs and the three
 // shifted x fragments of a filter row 9 -- 20 fragment reads per 27 MFMAs (the first version, 12 wavefronts x 6 tiles as in
-// wgrad3x3_halo_kernel of igemm.hip, needed 20 per 18: 983 KB of LDS reads per patch against 6912 MFMA cycles).  2 wavefronts per SIMD
+// wgrad3x3_halo_kernel of igemm_wgrad.hip, needed 20 per 18: 983 KB of LDS reads per patch against 6912 MFMA cycles).  2 wavefronts per SIMD
 // leave 256 registers per lane.  The workgroup walks 2x32-pixel patches (K = 4 x 16 pixels; 4x34 halo) DOWN a 32-pixel column of an
 // image, double-buffered in LDS; partial sums over the patch split are reduced in a fixed order by the caller.
 // Memory side (measured, conv7 at batch 64): walking along W with the slabs of one pixel split on different XCDs read 2.14 GB from HBM
@@ -1228,9 +1229,7 @@ int ladder_presplit(const float* x, const float* x_absmax, void* planes, size_t 
   size_t blocks = (n8 + 255) / 256;
   blocks = blocks > 4096 ? 4096 : blocks;
   const dim3 grid((unsigned)blocks), block(256);
-  if (prec == LADDER_PREC_F16X3) hipLaunchKernelGGL(presplit_kernel<LADDER_PREC_F16X3>, grid, block, 0, stream, x, x_absmax, (uint4*)planes, n8, sample8);
-  else if (prec == LADDER_PREC_BF16X6) hipLaunchKernelGGL(presplit_kernel<LADDER_PREC_BF16X6>, grid, block, 0, stream, x, x_absmax, (uint4*)planes, n8, sample8);
-  else hipLaunchKernelGGL(presplit_kernel<LADDER_PREC_BF16X3>, grid, block, 0, stream, x, x_absmax, (uint4*)planes, n8, sample8);
+  LADDER_PREC_SWITCH(prec, hipLaunchKernelGGL(presplit_kernel<PP>, grid, block, 0, stream, x, x_absmax, (uint4*)planes, n8, sample8));
   LADDER_CHECK_LAUNCH();
   return LADDER_OK;
 }
@@ -1260,12 +1259,8 @@ int ladder_filter_pack_split(const float* w, void* packed, int ntaps, int Cin, i
     const int rc = ladder_absmax(w, (size_t)ntaps * (transpose_flip == 4 ? Cin / 4 : Cin) * ((transpose_flip == 2 || transpose_flip == 3) ? Cout / 4 : Cout), wamax, stream);
     if (rc != LADDER_OK) return rc;
     if (transpose_flip >= 3) hipLaunchKernelGGL(record_times4_kernel, dim3(1), dim3(256), 0, stream, wamax);   // |W_eff| <= 4 max|w|
-    hipLaunchKernelGGL(filter_pack_kernel<LADDER_PREC_F16X3>, grid, block, 0, stream, w, (uint4*)packed, ntaps, Cin, Cout, transpose_flip, total, wamax);
-  } else if (prec == LADDER_PREC_BF16X6) {
-    hipLaunchKernelGGL(filter_pack_kernel<LADDER_PREC_BF16X6>, grid, block, 0, stream, w, (uint4*)packed, ntaps, Cin, Cout, transpose_flip, total, wamax);
-  } else {
-    hipLaunchKernelGGL(filter_pack_kernel<LADDER_PREC_BF16X3>, grid, block, 0, stream, w, (uint4*)packed, ntaps, Cin, Cout, transpose_flip, total, wamax);
   }
+  LADDER_PREC_SWITCH(prec, hipLaunchKernelGGL(filter_pack_kernel<PP>, grid, block, 0, stream, w, (uint4*)packed, ntaps, Cin, Cout, transpose_flip, total, wamax));
   LADDER_CHECK_LAUNCH();
   return LADDER_OK;
 }
@@ -1288,9 +1283,7 @@ int ladder_filter_pack_split_multi(const ladder_pack_job_t* jobs_dev, int njobs,
   if (scratch == nullptr || scratch_bytes < ladder_filter_pack_split_multi_scratch_bytes(njobs)) return LADDER_E_WORKSPACE;
   hipLaunchKernelGGL(filter_absmax_multi_kernel, dim3(PK_PARTS, njobs), dim3(256), 0, stream, jobs_dev, (float*)scratch);
   const dim3 grid(total_blocks), block(256);
-  if (prec == LADDER_PREC_F16X3) hipLaunchKernelGGL(filter_pack_multi_kernel<LADDER_PREC_F16X3>, grid, block, 0, stream, jobs_dev, njobs, (const float*)scratch);
-  else if (prec == LADDER_PREC_BF16X6) hipLaunchKernelGGL(filter_pack_multi_kernel<LADDER_PREC_BF16X6>, grid, block, 0, stream, jobs_dev, njobs, (const float*)scratch);
-  else hipLaunchKernelGGL(filter_pack_multi_kernel<LADDER_PREC_BF16X3>, grid, block, 0, stream, jobs_dev, njobs, (const float*)scratch);
+  LADDER_PREC_SWITCH(prec, hipLaunchKernelGGL(filter_pack_multi_kernel<PP>, grid, block, 0, stream, jobs_dev, njobs, (const float*)scratch));
   LADDER_CHECK_LAUNCH();
   return LADDER_OK;
 }
@@ -1331,9 +1324,9 @@ static int conv3x3_split_launch(const float* x, const float* x_absmax, const voi
     } else {
       if (prec == LADDER_PREC_F16X3) LADDER_SPLIT16_LAUNCH(LADDER_PREC_F16X3, false); else LADDER_SPLIT16_LAUNCH(LADDER_PREC_BF16X3, false);
     }
-  } else if (prec == LADDER_PREC_F16X3) LADDER_SPLIT_LAUNCH(LADDER_PREC_F16X3);
-  else if (prec == LADDER_PREC_BF16X6) LADDER_SPLIT_LAUNCH(LADDER_PREC_BF16X6);
-  else LADDER_SPLIT_LAUNCH(LADDER_PREC_BF16X3);
+  } else {
+    LADDER_PREC_SWITCH(prec, LADDER_SPLIT_LAUNCH(PP));
+  }
 #undef LADDER_SPLIT_LAUNCH
 #undef LADDER_SPLIT_LAUNCH_
 #undef LADDER_SPLIT_LAUNCH__
@@ -1514,20 +1507,14 @@ int ladder_conv3x3_wgrad_split(const float* x, const float* x_absmax, const floa
   if (!ladder_aligned16(x) || !ladder_aligned16(dy) || !ladder_aligned16(dw)) return LADDER_E_ALIGN;
   if (prec == LADDER_PREC_F16X3 && (x_absmax == nullptr || dy_absmax == nullptr)) return LADDER_E_SHAPE;
   if (ws == nullptr || ws_bytes < ladder_conv3x3_wgrad_split_workspace_bytes(N, H, W, Cin, Cout)) return LADDER_E_WORKSPACE;
-  const size_t kn = (size_t)9 * Cin * Cout;
-  float* part = (float*)ws;
-  float* bias_part = db != nullptr ? part + (size_t)p.splits * kn : nullptr;
+  const WgradTail t = wgrad_tail(ws, p.splits, (size_t)9 * Cin * Cout, Cout, dw, db);
   const dim3 grid(p.tiles_ci * p.tiles_co * ((p.splits + 7) / 8) * 8), block(WS_THREADS);
 #define LADDER_WS_LAUNCH(P_) \
-  hipLaunchKernelGGL(wgrad3x3_split_kernel<P_>, grid, block, 0, stream, x, dy, part, bias_part, N, H, W, Cin, Cout, p.tiles_ci, p.tiles_co, p.splits, p.pps, x_absmax, dy_absmax)
+  hipLaunchKernelGGL(wgrad3x3_split_kernel<P_>, grid, block, 0, stream, x, dy, t.part, t.bias_part, N, H, W, Cin, Cout, p.tiles_ci, p.tiles_co, p.splits, p.pps, x_absmax, dy_absmax)
   if (prec == LADDER_PREC_F16X3) LADDER_WS_LAUNCH(LADDER_PREC_F16X3);
   else LADDER_WS_LAUNCH(LADDER_PREC_BF16X3);
 #undef LADDER_WS_LAUNCH
-  LADDER_CHECK_LAUNCH();
-  int rc = ladder_reduce_splits(part, dw, p.splits, kn, stream);
-  if (rc != LADDER_OK) return rc;
-  if (db != nullptr) rc = ladder_reduce_splits(bias_part, db, p.splits, (size_t)Cout, stream);
-  return rc;
+  return t.reduce(stream);
 }
 
 }  // extern "C"

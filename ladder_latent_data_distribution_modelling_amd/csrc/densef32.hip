@@ -329,7 +329,7 @@ __global__ __launch_bounds__(GB_THREADS, 2) void gemm_nt16_f32_kernel(const floa
 // Filter gradient of the projected pairs: dWcat [Kc][N] = X^T D, X [M][Kc] (the low-resolution layer input), D [M][N] (the nine gradient planes); the
 // reduction runs over the M pixels, so both operands sit in LDS pixel-major exactly as they lie in memory ([32 pixels][128 channels], 512-byte rows:
 // conflict-free 32-bit fragment reads, lane = channel) and a (128 x 128 tile, pixel range) pair is one workgroup.  Partial tiles [split][Kc][N] are
-// summed in a fixed order by the caller (launch_reduce_splits, csrc/igemm.hip): bit-reproducible.  The bias gradient (column sums of D) rides along
+// summed in a fixed order by the caller (launch_reduce_splits, csrc/igemm_wgrad.hip): bit-reproducible.  The bias gradient (column sums of D) rides along
 // in the workgroups of tile row 0, which stream every D row anyway.  Same software pipeline as gemm_f32_kernel.
 __global__ __launch_bounds__(GB_THREADS, 2) void gemm_tn_f32_kernel(const float* __restrict__ X, const float* __restrict__ D, float* __restrict__ part,
                                                                     float* __restrict__ bias_part, const int M, const int Kc, const int N,

@@ -1,4 +1,4 @@
-// Operand splitting helpers shared by the split-precision contraction kernels (convsplit.hip, igemm.hip): precision formats,
+// Operand splitting helpers shared by the split-precision contraction kernels (convsplit.hip, igemm_split.hip): precision formats,
 // fp32 -> 16-bit plane splitting, the power-of-two tensor scale of the fp16 format and the 16-bit MFMA wrapper.  See the header
 // comment of convsplit.hip for the numerics.
 #pragma once

@@ -1,4 +1,4 @@
-"""Parity of the split-precision contraction kernels (csrc/convsplit.hip, the *_split kernels of csrc/igemm.hip) against the
+"""Parity of the split-precision contraction kernels (csrc/convsplit.hip, the *_split kernels of csrc/igemm_split.hip) against the
 float64 CPU oracle, through the C ABI.
 
 Tolerances (relative to the output scale, as tests/test_gpu_kernels.py): the two fp32-class formats -- f16x3 (2 scaled fp16
