@@ -279,6 +279,15 @@ int ladder_up2proj_fused_wide_tile(int N, int H, int W, int Cin, int Cout);
 size_t ladder_up2proj_fused_workspace_bytes(int N, int H, int W, int Cout, int proj_cout);
 int ladder_up2proj_fused_fwd(const float* x, const float* wcatT, const float* bias, float* y, const float* proj_w, const float* proj_b, float* proj_out,
                              int proj_cout, int N, int H, int W, int Cin, int Cout, int act, void* ws, size_t ws_bytes, ladder_stream_t stream);
+/* The same call with the form of the 64-pixel kernel chosen by the caller (A/B runs, bit-identity tests).  `variant` is a bit mask: bit 0 = an MFMA wave
+ * owns one 16-pixel tile and all nine taps (the first tiling: 10 LDS fragment reads per 16-deep k-group; clear: 2 tiles x 4 taps + 1 cell, 7 reads), bit 1 = the
+ * projection's sums over a pixel's four lanes through LDS-queue lane exchanges and always four outputs wide (clear: quad-perm DPP, three wide where
+ * proj_cout == 3).  ladder_up2proj_fused_fwd runs variant 1 -- the first tiling, which measured no slower, with the DPP exchange, which measured 120 us a
+ * launch faster on conv2d_7 (profiles/fused_fwd_cells.md) -- or the mask in the environment variable LADDER_UP2FUSE_VARIANT, read once.  All four variants
+ * produce identical bits; LADDER_E_SHAPE outside 0 .. 3.  (The 128-pixel row step variant has one form.) */
+int ladder_up2proj_fused_fwd_variant(const float* x, const float* wcatT, const float* bias, float* y, const float* proj_w, const float* proj_b,
+                                     float* proj_out, int proj_cout, int N, int H, int W, int Cin, int Cout, int act, void* ws, size_t ws_bytes, int variant,
+                                     ladder_stream_t stream);
 
 /* (strict fp32, round 5: Cout may be any multiple of 64 and the low-resolution map 16 or 8 pixels wide -- decoder conv2d_5 / conv2d_4,
  * codes/models.py:544-560; the fused projection form stays at Cout = 128)

@@ -190,6 +190,7 @@ PROTOTYPES = {
     "ladder_up2proj_fused_wide_tile": (_i, [_i] * 5),
     "ladder_up2proj_fused_workspace_bytes": (_z, [_i] * 5),
     "ladder_up2proj_fused_fwd": (_i, [_p] * 7 + [_i] * 7 + [_p, _z, _p]),
+    "ladder_up2proj_fused_fwd_variant": (_i, [_p] * 7 + [_i] * 7 + [_p, _z, _i, _p]),
     "ladder_dense_small_eligible": (_i, [_i, _i, _i]),
     "ladder_dense_fwd_small": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _p]),
     "ladder_dense_bwd_data_small": (_i, [_p, _p, _p, _i, _i, _i, _p, _i, _p]),

@@ -517,7 +517,8 @@ __global__ __launch_bounds__(256) void up2proj_part_reduce_kernel(const float* _
 // (L2-resident: 9 x 16 x Cin floats) and y.  No halo in either direction: the MFMA work is exactly the projection GEMM's (9 of 36 products).
 //
 // ROLES (one workgroup per CU, 12 waves).  Waves 0-3 = one per SIMD -- do nothing but LDS fragment reads and MFMAs: wave w owns pixel tile w (16 px) and
-// all nine taps (one x fragment feeds 9 MFMAs per k-step; 9 independent accumulators keep the matrix pipe issuing back to back; the fragments of the
+// all nine taps -- the default; CELLS below deals the cells otherwise and measured the same -- (one x fragment feeds 9 MFMAs per k-step; 9 independent
+// accumulators keep the matrix pipe issuing back to back; the fragments of the
 // next 16-deep group -- across chunk and row boundaries -- are requested before the 36 MFMAs of the current one).  Waves 4-7 stage the x / weight chunks
 // (global -> registers three chunks ahead -> LDS, three stages); waves 8-11 combine.  The three sides never meet at an s_barrier: they hand stages over
 // through LDS counters (full / empty per stage, row written / row read for the plane row).  Measured on the way (profiles/r06_fused_*.txt, conv2d_7):
@@ -574,7 +575,36 @@ __device__ __forceinline__ void uf_wait(const int* words, const int target) {
   }
 }
 
-template <bool PROJ, bool WRES>
+// CELLS: how the 4 x 9 grid of (16-pixel tile, tap) cells of a row step is dealt to the four MFMA waves.  A wave's LDS reads per 16-deep k-group are
+// (distinct tiles) + (distinct taps) of its nine cells: a whole row of the grid (one tile x nine taps, the first form of this kernel) costs 1 + 9 = 10,
+// two tiles x four taps + one cell costs 2 + 5 = 7.  Wave w owns tiles 2 (w >> 1), 2 (w >> 1) + 1 with taps 4 (w & 1) .. + 3, and tap 8 of tile
+// 2 (w >> 1) + (w & 1).  Cell i of a wave (= accumulator i): i < 4 and i = 8 sit on the wave's FIRST tile -- the one that also takes tap 8 -- so that which
+// x fragment a cell uses never depends on the wave; 4 <= i < 8 on its second.  Every accumulator still sums its k-steps in the same order.
+constexpr int uf_cell_tile(const int w, const int i) { return 2 * (w >> 1) + ((i < 4 || i == 8) ? (w & 1) : 1 - (w & 1)); }
+constexpr int uf_cell_tap(const int w, const int i) { return i == 8 ? 8 : 4 * (w & 1) + (i & 3); }
+constexpr bool uf_cells_cover_once() {
+  for (int tile = 0; tile < 4; ++tile)
+    for (int tap = 0; tap < 9; ++tap) {
+      int owners = 0;
+      for (int w = 0; w < 4; ++w)
+        for (int i = 0; i < 9; ++i) owners += (uf_cell_tile(w, i) == tile && uf_cell_tap(w, i) == tap) ? 1 : 0;
+      if (owners != 1) return false;
+    }
+  return true;
+}
+static_assert(uf_cells_cover_once(), "every (pixel tile, tap) cell of a row step has exactly one owning MFMA wave");
+
+// the sum over the four lanes of an aligned quad, in every lane of it, as (a + a^1) + (a^2 + a^3): two quad-perm DPP moves that the compiler folds into
+// the additions (v_add_f32_dpp) -- the LDS-queue permutes of __shfl_xor wait in the same queue as the MFMA waves' fragment reads
+__device__ __forceinline__ float uf_quad_sum(float v) {
+  v += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0xB1, 0xF, 0xF, false));   // quad_perm [1, 0, 3, 2]
+  v += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x4E, 0xF, 0xF, false));   // quad_perm [2, 3, 0, 1]
+  return v;
+}
+
+// CELLS / DPPX: the wave tiling and the quad exchange above, or (false) the first forms of both: the same bits either way.  PCO: 3 = the projection has
+// exactly three outputs (the model's RGB), 4 = any pco <= 4 (the outputs beyond pco are computed as zeros and dropped).
+template <bool PROJ, bool WRES, bool CELLS, bool DPPX, int PCO>
 __global__ __launch_bounds__(UF_THREADS, 3) void up2proj_fused_fwd_kernel(const float* __restrict__ x, const float* __restrict__ wT, const float* __restrict__ bias,
                                                                           float* __restrict__ y, const float* __restrict__ pw, float* __restrict__ ppart,
                                                                           const int pco, const int N, const int H, const int W, const int wshift, const int Cin,
@@ -606,35 +636,42 @@ __global__ __launch_bounds__(UF_THREADS, 3) void up2proj_fused_fwd_kernel(const 
   if (wid < UF_MW) {
     // ------------------------------------------------------------------------------------------------ MFMA waves
     __builtin_amdgcn_s_setprio(2);                                                    // their LDS reads and MFMAs win the issue arbitration of their SIMD
-    const int pt = wid;
+    // the wave's cells (see uf_cell_tile / uf_cell_tap): NX pixel tiles pt[], taps tb .. tb + NW - 1 (CELLS: tb .. tb + 3 and tap 8 as fragment 4)
+    constexpr int NX = CELLS ? 2 : 1, NW = CELLS ? 5 : 9;
+    const int pt[2] = {CELLS ? uf_cell_tile(wid, 0) : wid, CELLS ? uf_cell_tile(wid, 4) : wid}, tb = CELLS ? uf_cell_tap(wid, 0) : 0;
     f32x4_t acc[9];
 #pragma unroll
     for (int t = 0; t < 9; ++t)
 #pragma unroll
       for (int e = 0; e < 4; ++e) acc[t][e] = 0.f;
-    float4 fx0, fx1, fw0[9], fw1[9];
-    const int x_off = (pt * 16 + r16) * UF_LD + 4 * kq, w_off = r16 * UF_LD + 4 * kq;
+    float4 fx0[NX], fx1[NX], fw0[NW], fw1[NW];
+    // fragment t of the weights is tap wtap(t); the x / weight / plane-row offsets below are one base per (tile, first tap) + compile-time steps
+    auto wtap = [&](const int t) __attribute__((always_inline)) { return (CELLS && t == 4) ? 8 : tb + t; };
+    const int x_off[2] = {(pt[0] * 16 + r16) * UF_LD + 4 * kq, (pt[1] * 16 + r16) * UF_LD + 4 * kq}, w_off = r16 * UF_LD + 4 * kq;
     // plane row: pixel p, channel quad q at float offset 16 p + 4 (q ^ ((p >> 1) & 3)).  ds_write_b128 is serviced in groups of 8 lanes = 8 consecutive
     // pixels of ONE quad here: unswizzled they start on two bank groups only (4-way conflicts: 875 conflict cycles per row, profiles/r06_fused_pmc_v7*.txt);
     // the swizzle spreads them over all eight, and a pixel's four quads stay inside its own 64 bytes (the combination's reads do not change banks)
-    const int z_px = pt * 16 + r16, z_off = z_px * UF_CS + 4 * (kq ^ ((z_px >> 1) & 3));
+    const int z_off[2] = {(pt[0] * 16 + r16) * UF_CS + 4 * (kq ^ ((r16 >> 1) & 3)), (pt[1] * 16 + r16) * UF_CS + 4 * (kq ^ ((r16 >> 1) & 3))};
     const int ldw = Cin + UF_WRES_PAD, w_off_res = r16 * ldw + 4 * kq;
-    auto rd = [&](float4& fx, float4 (&fw)[9], const int sg, const int u, const int cc) __attribute__((always_inline)) {   // cc: the chunk's index in its row (WRES)
-      fx = *reinterpret_cast<const float4*>(&Xs[sg][x_off + 16 * u]);
+    auto rd = [&](float4 (&fx)[NX], float4 (&fw)[NW], const int sg, const int u, const int cc) __attribute__((always_inline)) {   // cc: the chunk's index in its row (WRES)
+#pragma unroll
+      for (int i = 0; i < NX; ++i) fx[i] = *reinterpret_cast<const float4*>(&Xs[sg][x_off[i] + 16 * u]);
       if (WRES) {
         const float* wp = &Ws[w_off_res + cc * UF_K + 16 * u];
 #pragma unroll
-        for (int t = 0; t < 9; ++t) fw[t] = *reinterpret_cast<const float4*>(wp + t * 16 * ldw);
+        for (int t = 0; t < NW; ++t) fw[t] = *reinterpret_cast<const float4*>(wp + wtap(t) * 16 * ldw);
       } else {
 #pragma unroll
-        for (int t = 0; t < 9; ++t) fw[t] = *reinterpret_cast<const float4*>(&Ws[sg * UF_N * UF_LD + w_off + t * 16 * UF_LD + 16 * u]);
+        for (int t = 0; t < NW; ++t) fw[t] = *reinterpret_cast<const float4*>(&Ws[sg * UF_N * UF_LD + w_off + wtap(t) * 16 * UF_LD + 16 * u]);
       }
     };
-    auto mmj = [&](const float4& fx, const float4 (&fw)[9], const int j) __attribute__((always_inline)) {   // one k-step: 9 independent MFMAs
-      const float b = j == 0 ? fx.x : (j == 1 ? fx.y : (j == 2 ? fx.z : fx.w));
+    auto mmj = [&](const float4 (&fx)[NX], const float4 (&fw)[NW], const int j) __attribute__((always_inline)) {   // one k-step: 9 independent MFMAs
 #pragma unroll
       for (int t = 0; t < 9; ++t) {
-        const float a = j == 0 ? fw[t].x : (j == 1 ? fw[t].y : (j == 2 ? fw[t].z : fw[t].w));
+        const float4& xf = fx[CELLS ? (t >= 4 && t < 8 ? 1 : 0) : 0];
+        const float4& wf = fw[CELLS ? (t == 8 ? 4 : (t & 3)) : t];
+        const float b = j == 0 ? xf.x : (j == 1 ? xf.y : (j == 2 ? xf.z : xf.w));
+        const float a = j == 0 ? wf.x : (j == 1 ? wf.y : (j == 2 ? wf.z : wf.w));
         acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, acc[t], 0, 0, 0);
       }
     };
@@ -661,16 +698,17 @@ __global__ __launch_bounds__(UF_THREADS, 3) void up2proj_fused_fwd_kernel(const 
       mmj(fx1, fw1, 0); mmj(fx1, fw1, 1); mmj(fx1, fw1, 2); mmj(fx1, fw1, 3);
       round = round_n;
       if (c == cpt - 1) {
-        // row k of the nine planes -> LDS (lane: pixel pt 16 + r16, channels 4 kq .. + 3 of tap t) once the combination waves have read row k - 1
+        // row k of the nine planes -> LDS (lane: pixel 16 tile + r16, channels 4 kq .. + 3 of the cell's tap) once the combination waves have read row k - 1
         if (k >= 1) uf_wait(&flags[UF_CDONE], k);
 #pragma unroll
         for (int t = 0; t < 9; ++t) {
-          *reinterpret_cast<float4*>(&Zr[t * UF_PLANE + z_off]) = make_float4(acc[t][0], acc[t][1], acc[t][2], acc[t][3]);
+          const int zo = CELLS ? (t == 8 ? 8 : tb + (t & 3)) * UF_PLANE + z_off[t >= 4 && t < 8 ? 1 : 0] : t * UF_PLANE + z_off[0];
+          *reinterpret_cast<float4*>(&Zr[zo]) = make_float4(acc[t][0], acc[t][1], acc[t][2], acc[t][3]);
 #pragma unroll
           for (int e = 0; e < 4; ++e) acc[t][e] = 0.f;
         }
         ++k;
-        uf_publish(&flags[UF_ZFULL + wid], k);                                        // rows 0 .. k - 1 of this wave's pixel tile are written
+        uf_publish(&flags[UF_ZFULL + wid], k);                                        // rows 0 .. k - 1 of this wave's cells are written
         c = 0;
       } else {
         ++c;
@@ -846,14 +884,19 @@ __global__ __launch_bounds__(UF_THREADS, 3) void up2proj_fused_fwd_kernel(const 
         float pv[8] = {p0.x, p0.y, p0.z, p0.w, p1.x, p1.y, p1.z, p1.w};
 #pragma unroll
         for (int e = 0; e < 8; ++e) {                                                 // the 4 quads of a pixel are 4 consecutive lanes: fixed-order sum
-          pv[e] += __shfl_xor(pv[e], 1, 64);
-          pv[e] += __shfl_xor(pv[e], 2, 64);
+          if ((e & 3) >= PCO) continue;                                               // (PCO = 3: output 3 is never stored, so neither summed nor exchanged)
+          if (DPPX) {
+            pv[e] = uf_quad_sum(pv[e]);
+          } else {
+            pv[e] += __shfl_xor(pv[e], 1, 64);
+            pv[e] += __shfl_xor(pv[e], 2, 64);
+          }
         }
         // every lane of the quad holds all sums: lane cq = o stores output channel o of the pixel pair (columns 2j, 2j + 1) as ONE 8-byte piece into
         // the partial plane [slab][o][pixel] -- 16 pixels of a wave make 128 contiguous bytes (12-byte pieces per pixel cost 250 us on conv2d_7)
         if (cq < pco) {
-          const float a0 = cq == 0 ? pv[0] : (cq == 1 ? pv[1] : (cq == 2 ? pv[2] : pv[3]));
-          const float a1 = cq == 0 ? pv[4] : (cq == 1 ? pv[5] : (cq == 2 ? pv[6] : pv[7]));
+          const float a0 = cq == 0 ? pv[0] : (cq == 1 ? pv[1] : (PCO == 3 || cq == 2 ? pv[2] : pv[3]));
+          const float a1 = cq == 0 ? pv[4] : (cq == 1 ? pv[5] : (PCO == 3 || cq == 2 ? pv[6] : pv[7]));
           *reinterpret_cast<float2*>(ppart + ((long)slab * pco + cq) * ((long)N * 4 * H * W) + opix) = make_float2(a0, a1);
         }
       }
@@ -1476,8 +1519,17 @@ size_t ladder_up2proj_fused_workspace_bytes(int N, int H, int W, int Cout, int p
   return proj_cout > 0 ? (size_t)(Cout / UF_CS) * N * 4 * H * W * proj_cout * sizeof(float) : 0;
 }
 
-int ladder_up2proj_fused_fwd(const float* x, const float* wcatT, const float* bias, float* y, const float* proj_w, const float* proj_b, float* proj_out,
-                             int proj_cout, int N, int H, int W, int Cin, int Cout, int act, void* ws, size_t ws_bytes, ladder_stream_t stream) {
+// `variant` (a bit mask) keeps the first forms of the 64-pixel kernel reachable for A/B runs and bit-identity tests: bit 0 = an MFMA wave owns one pixel tile and all
+// nine taps (10 fragment reads per k-group instead of 7), bit 1 = the projection's quad sums through LDS-queue lane exchanges, always four outputs wide.  Every
+// variant gives the same bits.  ladder_up2proj_fused_fwd runs UF_VARIANT_DEFAULT, or LADDER_UP2FUSE_VARIANT (read once) for whole-process comparisons.
+// Measured inside the CelebA step (profiles/fused_fwd_cells.md, conv2d_7 + RGB, us per launch): variant 3 1 662 / 1 646, the DPP exchange alone (1) 1 535, the
+// cell tiling alone (2) 1 657, both (0) 1 528; conv2d_4 208 with either exchange, 210 with the cell tiling.  The exchange is worth 120 us a launch; 30 % fewer
+// fragment reads buy nothing measurable -- the LDS queue is not what holds this kernel back -- so the cell tiling stays selectable and off.
+constexpr int UF_VARIANT_DEFAULT = 1;
+int ladder_up2proj_fused_fwd_variant(const float* x, const float* wcatT, const float* bias, float* y, const float* proj_w, const float* proj_b, float* proj_out,
+                                     int proj_cout, int N, int H, int W, int Cin, int Cout, int act, void* ws, size_t ws_bytes, int variant,
+                                     ladder_stream_t stream) {
+  if (variant < 0 || variant > 3) return LADDER_E_SHAPE;
   if (!ladder_up2proj_fused_eligible(N, H, W, Cin, Cout) || x == nullptr || wcatT == nullptr || (y == nullptr && proj_out == nullptr)) return LADDER_E_SHAPE;
   if (proj_out != nullptr && (proj_w == nullptr || proj_cout < 1 || proj_cout > 4)) return LADDER_E_SHAPE;
   if (!ladder_aligned16(x) || !ladder_aligned16(wcatT) || !ladder_aligned16(y) || (bias != nullptr && !ladder_aligned16(bias))) return LADDER_E_ALIGN;
@@ -1499,9 +1551,12 @@ int ladder_up2proj_fused_fwd(const float* x, const float* wcatT, const float* bi
   float* pp = proj_out != nullptr ? (float*)ws : nullptr;
   const float* pwp = proj_out != nullptr ? proj_w : nullptr;
   const int pco = proj_out != nullptr ? proj_cout : 0;
-#define UF_LAUNCH(P, R) hipLaunchKernelGGL((up2proj_fused_fwd_kernel<P, R>), dim3(grid), dim3(UF_THREADS), 0, stream, x, wcatT, bias, y, pwp, pp, pco, N, H, W, wshift, Cin, Cout, act, dbg)
+  const bool cells = !(variant & 1), dppx = !(variant & 2);
+#define UF_LAUNCH(P, R, C_, D_, O_) hipLaunchKernelGGL((up2proj_fused_fwd_kernel<P, R, C_, D_, O_>), dim3(grid), dim3(UF_THREADS), 0, stream, x, wcatT, bias, y, pwp, pp, pco, N, H, W, wshift, Cin, Cout, act, dbg)
+#define UF_LAUNCH_TILING(P, R, D_, O_) do { if (cells) UF_LAUNCH(P, R, true, D_, O_); else UF_LAUNCH(P, R, false, D_, O_); } while (0)
+#define UF_LAUNCH_PROJ(R) do { if (!dppx) UF_LAUNCH_TILING(true, R, false, 4); else if (pco == 3) UF_LAUNCH_TILING(true, R, true, 3); else UF_LAUNCH_TILING(true, R, true, 4); } while (0)
   if (proj_out != nullptr) {
-    if (wres) UF_LAUNCH(true, true); else UF_LAUNCH(true, false);
+    if (wres) UF_LAUNCH_PROJ(true); else UF_LAUNCH_PROJ(false);
     const long P = (long)N * 4 * H * W;
     if ((P & 3) == 0 && ladder_aligned16(ws) && ladder_aligned16(proj_out)) {
       const unsigned rb = (unsigned)((P / 4 + 255) / 256);
@@ -1513,11 +1568,19 @@ int ladder_up2proj_fused_fwd(const float* x, const float* wcatT, const float* bi
                          Cout / UF_CS);
     }
   } else {
-    if (wres) UF_LAUNCH(false, true); else UF_LAUNCH(false, false);
+    if (wres) UF_LAUNCH_TILING(false, true, false, 4); else UF_LAUNCH_TILING(false, false, false, 4);
   }
+#undef UF_LAUNCH_PROJ
+#undef UF_LAUNCH_TILING
 #undef UF_LAUNCH
   LADDER_CHECK_LAUNCH();
   return LADDER_OK;
+}
+
+int ladder_up2proj_fused_fwd(const float* x, const float* wcatT, const float* bias, float* y, const float* proj_w, const float* proj_b, float* proj_out,
+                             int proj_cout, int N, int H, int W, int Cin, int Cout, int act, void* ws, size_t ws_bytes, ladder_stream_t stream) {
+  static const int variant = getenv("LADDER_UP2FUSE_VARIANT") != nullptr ? atoi(getenv("LADDER_UP2FUSE_VARIANT")) & 3 : UF_VARIANT_DEFAULT;
+  return ladder_up2proj_fused_fwd_variant(x, wcatT, bias, y, proj_w, proj_b, proj_out, proj_cout, N, H, W, Cin, Cout, act, ws, ws_bytes, variant, stream);
 }
 
 }  // extern "C"
