@@ -188,6 +188,21 @@ int ladder_conv3x3_split_eligible(int N, int H, int W, int Cin, int Cout);
  * sub-patches, 64- or 128-channel tiles, >= 256 workgroups; H % 8 == 0, W % 8 == 0, Cin % 16 == 0, Cout % 4 == 0) -- decoder conv2d_3
  * and the backward-data of the encoder's deep layers (codes/models.py:420-460, 539-543).  1 when ladder_conv3x3_split(prec F32) takes the call. */
 int ladder_conv3x3_f32_eligible(int N, int H, int W, int Cin, int Cout);
+/* Pure-host query: which strict-fp32 halo kernel a ladder_conv3x3_*_split* / ladder_conv3x3_s2_fwd_f32 call with prec = LADDER_PREC_F32 runs, answered
+ * by the functions the launch itself calls.  The arguments are the INTERNAL geometry of the launch (the map the workgroups tile and the bank's [Cin][Cout]):
+ *   s2_out 0  ladder_conv3x3_split                   (N, H, W, Cin, Cout)
+ *          1  ladder_conv3x3_s2_bwd_data_split       (N, Ho, Wo, Cout_layer, 4 * Cin_layer): the dy map, four output-parity classes
+ *          2  ladder_conv3x3_up2_split               (N, H, W, Cin, 4 * Cout_layer): x low-resolution;  3: the same with x_upsampled = 1
+ *          4  ladder_conv3x3_up2_bwd_data_split      (N, H, W, 4 * C, Cout): the four pixel-parity classes of dy as input groups
+ *          5  ladder_conv3x3_s2_fwd_f32              (N, Ho, Wo, 4 * Cin_layer, Cout)
+ * Returns 0 (no strict-fp32 route: the call answers LADDER_E_SHAPE), 1 (the 8x32-pixel x 128-channel kernel of csrc/convf32.hip) or 2 (a small-map tiling
+ * of csrc/convf32s.hip) and fills plan[8] (may be NULL; all 0 for a 0 answer) =
+ *   { family (the return value), geo, ni, fks, pair_or_class_loop, tiles_m, tiles_n, grid }
+ * geo: sub-patch geometry 0 = one 16x16, 1 = one 8x16, 2 = four 8x8 images, 3 = two 8x8 images per workgroup (-1 for family 1); ni: 64-channel tiles per
+ * workgroup; fks: channels per input slab; pair_or_class_loop: family 2, class pairs per workgroup (every class launch) / family 1, all four class tiles of a
+ * patch in one workgroup (class launches with tiles_m >= 512, or as LADDER_CLASS_LOOP says); tiles_m: patches; tiles_n: channel tiles a patch is split
+ * into; grid: workgroups launched.  The eligibility queries of the entry points add their own conditions (switches, Cin % 16). */
+int ladder_conv3x3_f32_plan(int N, int H, int W, int Cin, int Cout, int s2_out, int* plan);
 /* y = act(conv3x3_same(x, F) + bias) with F as packed above (bias may be NULL; x_absmax is read only for LADDER_PREC_F16X3 and may
  * hold any upper bound of max |x|: a looser bound only raises the absolute representation floor 2^-38 * bound).  y_absmax (may be
  * NULL): record of the output, produced in the epilogue. */

@@ -10,6 +10,10 @@ bool conv3x3_f32_halo_ok(int N, int H, int W, int Cin, int Cout);
 // ... or one of the small-map tilings of convf32s.hip does (16- / 8-pixel-wide maps, class widths other than 128).  s2_out as below.
 bool conv3x3_f32s_ok(int N, int H, int W, int Cin, int Cout, int s2_out);
 bool conv3x3_f32_any_ok(int N, int H, int W, int Cin, int Cout, int s2_out);
+// what conv3x3_f32_launch does with a call on the 8x32-pixel tiling (ok = false: the call goes to convf32s.hip): channels per input slab and per
+// tile, the class-loop mapping (class launches with tiles_m >= 512, or as LADDER_CLASS_LOOP says), patches, channel tiles, workgroups
+struct F32BigPlan { bool ok; int fks, bn, cls_loop, tiles_m, tiles_n, grid; };
+F32BigPlan conv3x3_f32_big_plan(int N, int H, int W, int Cin, int Cout, int s2_out);
 int conv3x3_f32s_launch(const float* x, const float* bank, const float* bias, float* y, int N, int H, int W, int Cin, int Cout, int act,
                         hipStream_t stream, unsigned long long tap_masks, int s2_out);
 

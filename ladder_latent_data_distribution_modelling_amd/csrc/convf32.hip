@@ -426,10 +426,26 @@ bool conv3x3_f32_any_ok(int N, int H, int W, int Cin, int Cout, int s2_out) {
   return conv3x3_f32_big_ok(N, H, W, Cin, Cout, s2_out) || conv3x3_f32s_ok(N, H, W, Cin, Cout, s2_out);
 }
 
+F32BigPlan conv3x3_f32_big_plan(int N, int H, int W, int Cin, int Cout, int s2_out) {
+  F32BigPlan p{};
+  p.ok = conv3x3_f32_big_ok(N, H, W, Cin, Cout, s2_out);
+  if (!p.ok) return p;
+  p.fks = FK;
+  p.bn = FH_BN;
+  p.tiles_n = (Cout + FH_BN - 1) / FH_BN;
+  p.tiles_m = N * (H / FH_H) * (W / FH_W);
+  // class launches: all four class tiles of a patch in one workgroup when the patches alone fill whole rounds of the chip
+  static const int cls_env = getenv("LADDER_CLASS_LOOP") ? atoi(getenv("LADDER_CLASS_LOOP")) : -1;
+  p.cls_loop = ((s2_out >= 1 && s2_out <= 3) && (cls_env >= 0 ? cls_env != 0 : p.tiles_m >= 512)) ? 1 : 0;
+  p.grid = p.cls_loop ? p.tiles_m : p.tiles_m * p.tiles_n;
+  return p;
+}
+
 int conv3x3_f32_launch(const float* x, const float* bank, const float* bias, float* y, const float* pw, const float* pb, float* pout,
                        int pco, int N, int H, int W, int Cin, int Cout, int act, hipStream_t stream, unsigned long long tap_masks,
                        int s2_out) {
-  if (!conv3x3_f32_big_ok(N, H, W, Cin, Cout, s2_out)) {     // small maps / wide classes: convf32s.hip (no fused projection there)
+  const F32BigPlan plan = conv3x3_f32_big_plan(N, H, W, Cin, Cout, s2_out);
+  if (!plan.ok) {                                            // small maps / wide classes: convf32s.hip (no fused projection there)
     if (pout != nullptr || pw != nullptr) return LADDER_E_SHAPE;        // (no fused projection / gate there)
     return conv3x3_f32s_launch(x, bank, bias, y, N, H, W, Cin, Cout, act, stream, tap_masks, s2_out);
   }
@@ -438,13 +454,9 @@ int conv3x3_f32_launch(const float* x, const float* bank, const float* bias, flo
   if ((s2_out == 4 || s2_out == 5) && pout != nullptr) return LADDER_E_SHAPE;
   if (!ladder_aligned16(x) || !ladder_aligned16(bank) || !ladder_aligned16(y) || (bias != nullptr && !ladder_aligned16(bias)))
     return LADDER_E_ALIGN;
-  const int tiles_n = (Cout + FH_BN - 1) / FH_BN;
-  const int tiles_m = N * (H / FH_H) * (W / FH_W);
-  // class launches: all four class tiles of a patch in one workgroup when the patches alone fill whole rounds of the chip
-  static const int cls_env = getenv("LADDER_CLASS_LOOP") ? atoi(getenv("LADDER_CLASS_LOOP")) : -1;
-  const bool cls_loop = (s2_out >= 1 && s2_out <= 3) && (cls_env >= 0 ? cls_env != 0 : tiles_m >= 512);
-  const dim3 grid(cls_loop ? tiles_m : tiles_m * tiles_n), block(FH_THREADS);
-  const int s2x = s2_out | (cls_loop ? 0x100 : 0);
+  const int tiles_n = plan.tiles_n;
+  const dim3 grid(plan.grid), block(FH_THREADS);
+  const int s2x = s2_out | (plan.cls_loop ? 0x100 : 0);
 #define LADDER_F32_LAUNCH(PROJ_, UPM_) \
   hipLaunchKernelGGL((conv3x3_halo_f32_kernel<PROJ_, UPM_>), grid, block, 0, stream, x, bank, bias, y, N, H, W, Cin, Cout, act, tiles_n, pw, pb, pout, pco, tap_masks, s2x)
   if (s2_out == 4 || s2_out == 5) LADDER_F32_LAUNCH(false, 2);

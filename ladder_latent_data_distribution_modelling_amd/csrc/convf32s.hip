@@ -499,6 +499,23 @@ extern "C" {
 
 int ladder_conv3x3_f32_eligible(int N, int H, int W, int Cin, int Cout) { return conv3x3_f32_any_ok(N, H, W, Cin, Cout, 0) ? 1 : 0; }
 
+// The decision of conv3x3_f32_launch, from the functions it calls itself: conv3x3_f32_big_plan first, else conv3x3_f32s_ok + plan_f32s.
+int ladder_conv3x3_f32_plan(int N, int H, int W, int Cin, int Cout, int s2_out, int* plan) {
+  int out[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  const F32BigPlan b = conv3x3_f32_big_plan(N, H, W, Cin, Cout, s2_out);
+  if (b.ok) {
+    const int v[8] = {1, -1, b.bn / 64, b.fks, b.cls_loop, b.tiles_m, b.tiles_n, b.grid};
+    for (int i = 0; i < 8; ++i) out[i] = v[i];
+  } else if (conv3x3_f32s_ok(N, H, W, Cin, Cout, s2_out)) {
+    const F32sPlan p = plan_f32s(N, H, W, Cin, Cout, s2_out);
+    const int v[8] = {2, p.geo, p.ni, p.fks, p.pair, p.tiles_m, p.tiles_n, p.grid};
+    for (int i = 0; i < 8; ++i) out[i] = v[i];
+  }
+  if (plan != nullptr)
+    for (int i = 0; i < 8; ++i) plan[i] = out[i];
+  return out[0];
+}
+
 int ladder_conv3x3_s2_bwd_data_f32_eligible(int N, int H, int W, int Cin, int Ho, int Wo, int Cout) {
   static const bool off = getenv("LADDER_DISABLE_S2HALO") != nullptr;
   return (!off && H == 2 * Ho && W == 2 * Wo && Cin > 0 && conv3x3_f32_any_ok(N, Ho, Wo, Cout, 4 * Cin, 1)) ? 1 : 0;

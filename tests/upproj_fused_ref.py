@@ -22,9 +22,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
+from guarded import GUARD, GUARD_BITS, _FF_BITS, _Guarded, _NAN_BITS  # noqa: E402,F401  (tests/guarded.py: shared with tests/convf32_cases.py)
+
 TOL32 = 3e-6                # of the reference's scale: the bar of tests/test_gpu_upproj.py (fp32 accumulation of K = Cin <= 512 products + <= 16 additions)
-GUARD = 2048                # floats on each side of an interior: 8 KiB, so 4 KiB remain where the interior starts one float later
-GUARD_BITS = 0x5A5AA5A5     # (as a float: 1.5e16, finite)
 MASKS = (3, 2, 1, 0, None)  # ladder_up2proj_fused_fwd_variant: bit 0 = first wave tiling, bit 1 = first quad exchange (3 gives the reference bits); None = ladder_up2proj_fused_fwd
 
 # (N, H, W, Cin, Cout) -> total
@@ -111,25 +111,6 @@ def reference(case):
         if has_pb:
             pref = pref + pb_.astype(np.float64)
     return (x, w, b if has_bias else None, pw_, pb_), ref, pref
-
-
-class _Guarded:
-    """`n` floats, 16-byte aligned (or, `shift` = 1, one float past that), inside a larger buffer whose GUARD floats on each side hold GUARD_BITS."""
-
-    def __init__(self, n, fill_bits, shift=0):
-        import torch
-        self.n, self.lo = n, GUARD + shift
-        self.bits = torch.full((2 * GUARD + n + 4,), GUARD_BITS, dtype=torch.int32, device="cuda")
-        assert self.bits.data_ptr() % 16 == 0
-        self.bits[self.lo:self.lo + n] = fill_bits
-        self.t = self.bits.view(torch.float32)[self.lo:self.lo + n]
-        assert self.t.data_ptr() % 16 == 4 * shift and self.t.data_ptr() == self.bits.data_ptr() + 4 * self.lo
-
-    def guards_intact(self):
-        return bool((self.bits[:self.lo] == GUARD_BITS).all().item()) and bool((self.bits[self.lo + self.n:] == GUARD_BITS).all().item())
-
-
-_NAN_BITS, _FF_BITS = 0x7FC00000, -1                  # a quiet NaN for the outputs; 0xFF bytes (also a NaN) for the workspace
 
 
 def launch(L, case, inputs, stream, variant):
