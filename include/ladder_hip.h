@@ -950,6 +950,52 @@ int ladder_vbgmm_wide_mstep(const double* stats, const double* moments, int K, i
                             double mean_prec_prior, double reg_covar, double tol, int max_iter, int it, float* weights, float* means, float* covs,
                             ladder_stream_t stream);
 
+/* ---------------------------------------------------------------- N21: the fitted mixture and the samplers on a WIDE latent (csrc/mixture_wide.hip,
+ * csrc/chol_wide.h, csrc/sample.hip).  64 < R <= 256, R % 16 == 0: the reference's shipped codes/celeba_config.json has code_size 256.  Prior "GMM" puts
+ * the K-component full-covariance mixture on z itself (codes/base.py:101-106 the fit, :322-329 the ELBO term, :927-930 the feed), and generation draws
+ * z ~ N(0, I_Z) or z ~ the fitted mixture (codes/base.py:1065-1122).  The entry points of N9 / N15 keep their limits (R <= 64); these refuse R <= 64, so
+ * every width has exactly one form.
+ *
+ * The prepared mixture: ladder_gmm_wide_param_bytes(K, R) bytes (0 outside 1 <= K <= 1024 and the widths above), 16-byte aligned:
+ *   int32 status | K | R | 0,  then fp32: logc [K, padded to a multiple of 4],  means [K,R],  Linv_k = L_k^-1 as its R/16 (R/16 + 1) / 2 lower 16 x 16
+ *   blocks,  P_k = Linv_k^T Linv_k as its (R/16)^2 blocks; block order and the order inside a block (the operand order of v_mfma_f32_16x16x4_f32):
+ *   head of csrc/mixture_wide.hip.  logc_k = log w_k - log sum w - sum log diag L_k - R/2 log 2 pi.  Everything is computed in float64 (one workgroup
+ *   per component, the working matrix in `ws` >= ladder_gmm_wide_prepare_workspace_bytes(K, R), a 16-column panel in LDS) and rounded once.
+ *   status = -1: usable; k >= 0: first component whose factorisation met a non-positive or NaN pivot; -2: the weights have no positive finite sum --
+ *   the caller reads it once after prepare.
+ * ladder_gmm_wide_logprob_fwd_bwd has the contract of ladder_gmm_dense_logprob_fwd_bwd (outputs, dmu = dsd = NULL for the log-prob only, no
+ * allocation, no synchronisation, argument checks before any launch), in strict fp32 whatever the engine's matmul precision:
+ *   t = mu + sd * eps,  d = t - m_k,  y = Linv_k d (the all-zero blocks right of the diagonal skipped),  q = |y|^2 from the accumulators,
+ *   lp_k = logc_k - q / 2, max-subtracted logsumexp, sum_logp = the per-sample values summed in double in a fixed order;
+ *   g_s = -sum_k r_sk P_k (t_s - m_k),  dmu[b] = sum_l g[l,b],  dsd[b] = sum_l g[l,b] eps[l,b], l ascending.
+ * Its workspace holds q [S,K], at most five partial g [S,R] and the block partials (S = L*B): it grows with S (R + K), never with S K R.  The forward-only
+ * call gives the same sum_logp bits as the training call, and two calls on the same inputs the same bits.  The kernels compare the header with
+ * their own (K, R) on the device before reading anything else: an unusable or foreign buffer gives NaN outputs.
+ * LADDER_E_SHAPE for K, R outside the limits, L or B < 1 (n < 1), L*B > 2^30, a NULL array or only one of dmu / dsd; LADDER_E_ALIGN for arrays off 16
+ * bytes; LADDER_E_WORKSPACE for a NULL or short workspace. */
+size_t ladder_gmm_wide_param_bytes(int K, int R);
+size_t ladder_gmm_wide_prepare_workspace_bytes(int K, int R);
+int ladder_gmm_wide_prepare(const float* weights, const float* means, const float* covs, int K, int R, void* params, void* ws, size_t ws_bytes,
+                            ladder_stream_t stream);
+size_t ladder_gmm_wide_workspace_bytes(int L, int B, int R, int K);
+int ladder_gmm_wide_logprob_fwd_bwd(const float* mu, const float* sd, const float* eps, const void* params, int L, int B, int R, int K,
+                                    float* sum_logp, float* dmu, float* dsd, void* ws, size_t ws_bytes, ladder_stream_t stream);
+/* per-point log p(t_i), t [n,R] (demo/demo_tools.py prior.log_prob); ws >= ladder_gmm_wide_workspace_bytes(1, n, R, K). */
+int ladder_gmm_wide_logprob_rows(const float* t, const void* params, int n, int R, int K, float* logp, void* ws, size_t ws_bytes,
+                                 ladder_stream_t stream);
+/* The samplers of N15 for the same widths (K >= 1): the SAME buffer layout (header, float64 cdf, fp32 means, packed lower-triangular fp32 factors;
+ * ladder_mixture_sample_wide_param_bytes equals N15's formula), output definition (out = m_k + L_k eps as an fp32 FMA chain, j ascending from m_k),
+ * comp / NULL-noise / header-mismatch behaviour and Philox counter layout (generator block 2 + j / 4 <= 65 fits its 8 bits); sample i depends on
+ * (seed, offset, i) only.  The factorisation is the float64 panel one above: ws >= ladder_mixture_sample_wide_prepare_workspace_bytes(K, R).
+ * _prepare_diag (K equally weighted diagonal components; K = 1, mean 0, sd 1: the N(0, I) of "standard_gaussian" / "hierarchical") needs none. */
+size_t ladder_mixture_sample_wide_param_bytes(int K, int R);
+size_t ladder_mixture_sample_wide_prepare_workspace_bytes(int K, int R);
+int ladder_mixture_sample_wide_prepare(const float* weights, const float* means, const float* covs, int K, int R, void* params, void* ws,
+                                       size_t ws_bytes, ladder_stream_t stream);
+int ladder_mixture_sample_wide_prepare_diag(const float* comp_mean, const float* comp_sd, int K, int R, void* params, ladder_stream_t stream);
+int ladder_mixture_sample_wide(const void* params, int K, int R, int n, int64_t first, const float* u, const float* eps, uint64_t seed,
+                               uint64_t offset, float* out, int* comp, ladder_stream_t stream);
+
 /* ---------------------------------------------------------------- helpers */
 /* HOST function (no device work): CRC-32C (Castagnoli) of host memory, crc = 0 to start, chainable.  Used by the
  * tf.train.Saver checkpoint-v2 reader/writer (codes/base.py:37-85: saver_ae / saver_prior) for block and tensor checksums. */

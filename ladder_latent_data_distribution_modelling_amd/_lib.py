@@ -248,6 +248,17 @@ PROTOTYPES = {
     "ladder_moments_state_doubles": (_z, [_i]),
     "ladder_moments_workspace_bytes": (_z, [_i, _i]),
     "ladder_moments_accumulate": (_i, [_p, _i, _i, _p, _p, _z, _p]),
+    "ladder_gmm_wide_param_bytes": (_z, [_i, _i]),
+    "ladder_gmm_wide_prepare_workspace_bytes": (_z, [_i, _i]),
+    "ladder_gmm_wide_prepare": (_i, [_p, _p, _p, _i, _i, _p, _p, _z, _p]),
+    "ladder_gmm_wide_workspace_bytes": (_z, [_i, _i, _i, _i]),
+    "ladder_gmm_wide_logprob_fwd_bwd": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _p, _p, _p, _p, _z, _p]),
+    "ladder_gmm_wide_logprob_rows": (_i, [_p, _p, _i, _i, _i, _p, _p, _z, _p]),
+    "ladder_mixture_sample_wide_param_bytes": (_z, [_i, _i]),
+    "ladder_mixture_sample_wide_prepare_workspace_bytes": (_z, [_i, _i]),
+    "ladder_mixture_sample_wide_prepare": (_i, [_p, _p, _p, _i, _i, _p, _p, _z, _p]),
+    "ladder_mixture_sample_wide_prepare_diag": (_i, [_p, _p, _i, _i, _p, _p]),
+    "ladder_mixture_sample_wide": (_i, [_p, _i, _i, _i, C.c_int64, _p, _p, _u64, _u64, _p, _p, _p]),
 }
 
 _lib = None

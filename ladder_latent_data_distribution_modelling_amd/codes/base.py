@@ -14,6 +14,8 @@ from .models import BaseModel  # noqa: F401  (re-export, reference exposes BaseM
 class BaseTrain:
     def __init__(self, sess, model, data, config):
         self.model, self.config, self.sess, self.data = model, config, sess, data
+        from .mixture_fit import check_device_fit_width
+        check_device_fit_width(config)          # a device fit of a mixture on more than 64 dimensions cannot work: say so before the first epoch
         self.engine = model.engine
         # replay each run as one captured hipGraph after two eager warm-ups (config key `use_hip_graphs`, default on)
         # (default: on for the MNIST nets, whose ~350 short launches per iteration are host-bound in eager mode; off for CelebA, where

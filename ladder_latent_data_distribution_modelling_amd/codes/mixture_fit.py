@@ -78,6 +78,20 @@ def check_kmeans_backend(backend):
     return backend
 
 
+DEVICE_FIT_MAX_R = 64        # csrc/emgmm.hip, csrc/vbgmm.hip and csrc/kmeans.hip end here; the mixture term and the samplers go on to 256
+
+
+def check_device_fit_width(config):
+    """prior "GMM" fits its mixture on z, so the mixture dimension is code_size: beyond 64 only the host fits exist (the defaults: sklearn's EM and
+    sklearn's k-means).  Raises ValueError naming the config key that asks for a device fit.  (prior "ours": codes/vbgmm.py checks its own.)"""
+    if config.get("prior") != "GMM" or int(config["code_size"]) <= DEVICE_FIT_MAX_R:
+        return
+    for key in ("gm_fit_backend", "kmeans_backend"):
+        if config.get(key) == "hip":
+            raise ValueError('%s: "hip" fits mixtures on at most %d dimensions, prior "GMM" with code_size = %d needs the host fit '
+                             '(leave %s out or set it to "sklearn")' % (key, DEVICE_FIT_MAX_R, int(config["code_size"]), key))
+
+
 def _gather_ragged(parts, x, comm):
     for r, p_ in enumerate(parts):                                               # ranks with different sample counts: one broadcast each
         if r == comm.rank:

@@ -58,6 +58,8 @@ class BaseModel:
         elif self.config["prior"] == "GMM":          # base.py:101-106: plain EM mixture on z (R = code_size)
             # The host fit unless the config EXPLICITLY asks for the device one (codes/emgmm.py -> csrc/emgmm.hip): an absent key keeps sklearn here,
             # unlike "ours" above.
+            from .mixture_fit import check_device_fit_width
+            check_device_fit_width(self.config)
             kw = dict(n_components=int(self.config["n_mixtures"]), covariance_type="full", max_iter=1000, n_init=1, warm_start=True)
             if self.config.get("gm_fit_backend") == "hip":
                 from .emgmm import DeviceGaussianMixture

@@ -18,7 +18,12 @@
 //   b = 2 + j / 4:    eps_i[4 (b-2) .. 4 (b-2) + 3] = the four Box-Muller normals of the block (philox.h)
 // so the draws of sample i depend on (seed, offset, i) only -- not on n, first or the launch grid.  ladder_randn uses b = 0 of the same
 // counter space (its block index stays below 2^56), so the two never share a block under one (seed, offset).
+//
+// WIDE samplers (ladder_mixture_sample_wide*: 64 < R <= 256, R % 16 == 0) keep this buffer layout, this output definition and this counter
+// layout (b = 2 + j / 4 reaches 65 at R = 256, inside its 8 bits); their factorisation is the panel one of chol_wide.h in a caller-provided
+// workspace, and a sample's rows r = lane, lane + 64, ... are spread over the lanes of one wavefront with eps staged in LDS.
 #include "common.h"
+#include "chol_wide.h"
 #include "philox.h"
 
 namespace {
@@ -243,6 +248,80 @@ __global__ __launch_bounds__(256) void sample_wave_kernel(const unsigned char* _
   if (comp != nullptr && lane == 0) comp[row] = k;
 }
 
+// ---- wide samplers -------------------------------------------------------------------------------------------------------------
+// Workgroup b factors the components b, b + gridDim.x, ... in its slot of the workspace and rounds the lower triangle into the buffer.
+__global__ __launch_bounds__(CW_THREADS) void sample_chol_wide_kernel(const float* __restrict__ covs, int K, int R, unsigned char* params, double* ws) {
+  __shared__ CwShared sh;
+  const int tid = threadIdx.x;
+  const int T = (int)sample_tri(R);
+  double* W = ws + (size_t)blockIdx.x * R * R;
+  for (int k = blockIdx.x; k < K; k += gridDim.x) {
+    __syncthreads();                                     // (the previous component's W is no longer read)
+    const bool failed = chol_wide_factor<false>(covs + (size_t)k * R * R, R, W, sh);
+    float* Lk = reinterpret_cast<float*>(params + sample_off_means(K)) + (size_t)K * R + (size_t)k * T;
+    for (int e = tid; e < R * R; e += CW_THREADS) {
+      const int i = e / R, j = e - i * R;
+      if (j <= i) Lk[i * (i + 1) / 2 + j] = failed ? 0.f : (float)W[e];
+    }
+    if (failed && tid == 0) atomicMin(reinterpret_cast<unsigned*>(params), (unsigned)k);
+  }
+}
+
+// One wavefront per sample, 4 per workgroup; lane l owns the rows l, l + 64, l + 128, l + 192 below R.
+__global__ __launch_bounds__(256) void sample_wide_kernel(const unsigned char* __restrict__ params, int K, int R, int n, long long first,
+                                                          const float* __restrict__ u_in, const float* __restrict__ eps_in, uint64_t seed,
+                                                          uint64_t offset, float* __restrict__ out, int* __restrict__ comp) {
+  __shared__ float s_eps[4][CW_MAXR];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int row = blockIdx.x * 4 + wv;
+  const bool live = row < n;                             // (whole wavefronts; they stay for the barrier)
+  const bool ok = sample_header_ok(params, K, R);
+  float u = 0.f;
+  if (live && ok) {
+    const long long i = first + row;
+    if (u_in != nullptr) {
+      u = u_in[row];
+      for (int j = lane; j < R; j += 64) s_eps[wv][j] = eps_in[(size_t)row * R + j];
+    } else {
+      u = sample_uniform(i, seed, offset);
+      if (4 * lane < R) {                                // generator block 2 + lane: eps[4 lane .. 4 lane + 3]  (R % 4 == 0)
+        uint32_t c[4];
+        float o[4];
+        sample_block(c, i, 2u + (uint32_t)lane, seed, offset);
+        philox_box_muller4(c, o);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) s_eps[wv][4 * lane + j] = o[j];
+      }
+    }
+  }
+  __syncthreads();
+  if (!live) return;
+  if (!ok) {
+    for (int r = lane; r < R; r += 64) out[(size_t)row * R + r] = sample_nan();
+    if (comp != nullptr && lane == 0) comp[row] = -1;
+    return;
+  }
+  const double* cdf = reinterpret_cast<const double*>(params + 16);
+  const float* means = reinterpret_cast<const float*>(params + sample_off_means(K));
+  const float* Ls = means + (size_t)K * R;
+  const int k = sample_component(cdf, K, (double)u);
+  const float* Lk = Ls + (size_t)k * sample_tri(R);
+  const float* e = s_eps[wv];
+  for (int r = lane; r < R; r += 64) {
+    const float* Lr = Lk + (size_t)r * (r + 1) / 2;
+    float acc = means[(size_t)k * R + r];
+    for (int j = 0; j <= r; ++j) acc = fmaf(Lr[j], e[j], acc);
+    out[(size_t)row * R + r] = acc;
+  }
+  if (comp != nullptr && lane == 0) comp[row] = k;
+}
+
+int wide_prepare_checks(const void* a, const void* b, int K, int R, const void* params) {
+  if (K < 1 || !cw_width_ok(R) || a == nullptr || b == nullptr || params == nullptr) return LADDER_E_SHAPE;
+  if (!ladder_aligned16(a) || !ladder_aligned16(b) || !ladder_aligned16(params)) return LADDER_E_ALIGN;
+  return LADDER_OK;
+}
+
 __device__ __forceinline__ unsigned u8_of(float v) { return (unsigned)rintf(255.f * fminf(fmaxf(v, 0.f), 1.f)); }   // (fmaxf(NaN, 0) = 0)
 __device__ __forceinline__ unsigned u8_pack(float4 v) { return u8_of(v.x) | (u8_of(v.y) << 8) | (u8_of(v.z) << 16) | (u8_of(v.w) << 24); }
 
@@ -328,6 +407,47 @@ int ladder_mixture_sample(const void* params, int K, int R, int n, int64_t first
     hipLaunchKernelGGL(sample_wave_kernel, dim3((unsigned)(((size_t)n + 3) / 4)), dim3(256), 0, stream, p, K, R, n, first, u, eps, seed, offset, out,
                        comp);
   }
+  LADDER_CHECK_LAUNCH();
+  return LADDER_OK;
+}
+
+size_t ladder_mixture_sample_wide_param_bytes(int K, int R) {
+  if (K < 1 || !cw_width_ok(R)) return 0;
+  return sample_bytes(K, R);
+}
+
+size_t ladder_mixture_sample_wide_prepare_workspace_bytes(int K, int R) { return cw_workspace_bytes(K, R); }
+
+int ladder_mixture_sample_wide_prepare(const float* weights, const float* means, const float* covs, int K, int R, void* params, void* ws,
+                                       size_t ws_bytes, ladder_stream_t stream) {
+  if (weights == nullptr) return LADDER_E_SHAPE;
+  if (const int rc = wide_prepare_checks(means, covs, K, R, params)) return rc;
+  if (!ladder_aligned16(weights)) return LADDER_E_ALIGN;
+  if (ws == nullptr || ws_bytes < cw_workspace_bytes(K, R)) return LADDER_E_WORKSPACE;
+  hipLaunchKernelGGL(sample_header_kernel, dim3(1), dim3(256), 0, stream, weights, means, K, R, (unsigned char*)params);
+  hipLaunchKernelGGL(sample_chol_wide_kernel, dim3(cw_slots(K)), dim3(CW_THREADS), 0, stream, covs, K, R, (unsigned char*)params, cw_workspace_base(ws));
+  LADDER_CHECK_LAUNCH();
+  return LADDER_OK;
+}
+
+int ladder_mixture_sample_wide_prepare_diag(const float* comp_mean, const float* comp_sd, int K, int R, void* params, ladder_stream_t stream) {
+  if (const int rc = wide_prepare_checks(comp_mean, comp_sd, K, R, params)) return rc;
+  hipLaunchKernelGGL(sample_header_kernel, dim3(1), dim3(256), 0, stream, (const float*)nullptr, comp_mean, K, R, (unsigned char*)params);
+  hipLaunchKernelGGL(sample_diag_kernel, dim3(K), dim3(64), 0, stream, comp_sd, K, R, (unsigned char*)params);
+  LADDER_CHECK_LAUNCH();
+  return LADDER_OK;
+}
+
+int ladder_mixture_sample_wide(const void* params, int K, int R, int n, int64_t first, const float* u, const float* eps, uint64_t seed,
+                               uint64_t offset, float* out, int* comp, ladder_stream_t stream) {
+  if (K < 1 || !cw_width_ok(R) || n < 0 || first < 0 || first > SAMPLE_MAX_INDEX - n) return LADDER_E_SHAPE;
+  if ((u == nullptr) != (eps == nullptr)) return LADDER_E_SHAPE;          // both fed or both drawn
+  if (n == 0) return LADDER_OK;
+  if (params == nullptr || out == nullptr) return LADDER_E_SHAPE;
+  if (!ladder_aligned16(params) || !ladder_aligned16(out) || !ladder_aligned16(u) || !ladder_aligned16(eps) || !ladder_aligned16(comp))
+    return LADDER_E_ALIGN;
+  hipLaunchKernelGGL(sample_wide_kernel, dim3((unsigned)(((size_t)n + 3) / 4)), dim3(256), 0, stream, (const unsigned char*)params, K, R, n,
+                     (long long)first, u, eps, seed, offset, out, comp);
   LADDER_CHECK_LAUNCH();
   return LADDER_OK;
 }

@@ -276,8 +276,8 @@ PRIOR_METHODS = arch.PRIOR_METHODS
 class PriorSampler:
     """Handle of LadderEngine.prior_sampler(): ancestral samples of one prior, drawn on the device (reference codes/base.py:1065-1122).
 
-    Owns the prepared parameter buffer of csrc/sample.hip.  Its Philox stream is its own -- (seed, offset) of this object, never the
-    engine's training noise position -- and sample index i draws the same values whatever the chunking: sample(n, first) returns samples
+    Owns the prepared parameter buffer of csrc/sample.hip (R <= 64, or its wide sampler for 64 < R <= 256 with R % 16 == 0: one layout).
+    Its Philox stream is its own -- (seed, offset) of this object, never the engine's training noise position -- and sample index i draws the same values whatever the chunking: sample(n, first) returns samples
     first .. first+n-1 of ONE stream, so a bulk run may be cut into chunks (or, later, sharded over ranks) freely."""
 
     def __init__(self, eng, method, K, R, params, seed=0, offset=0):
@@ -296,7 +296,7 @@ class PriorSampler:
             u, eps = eng._dev(noise["u"]).reshape(-1), eng._dev(noise["eps"])
             if tuple(u.shape) != (n,) or tuple(eps.shape) != (n, self.R):
                 raise ValueError("noise: u %s, eps %s; expected (%d,) and (%d, %d)" % (tuple(u.shape), tuple(eps.shape), n, n, self.R))
-        L.call("ladder_mixture_sample", _p(self.params), self.K, self.R, n, int(first), _p(u), _p(eps),
+        L.call("ladder_mixture_sample_wide" if self.R > 64 else "ladder_mixture_sample", _p(self.params), self.K, self.R, n, int(first), _p(u), _p(eps),
                self.seed if seed is None else int(seed), self.offset, _p(latent), _p(comp), ctx.stream)
         code = eng.decode_representation(latent) if self.to_code else latent
         return code, latent, comp
@@ -905,11 +905,17 @@ class LadderEngine:
         else:
             K, R = 1, int(self.Z if method == "standard_gaussian" else self.cfg["representation_size"])
             prep, keep = "ladder_mixture_sample_prepare_diag", (ctx.zeros(1, R), torch.ones(1, R, dtype=torch.float32, device=ctx.device))
-        nbytes = L.query("ladder_mixture_sample_param_bytes", K, R)
+        wide = R > 64                                            # the wide sampler: same buffer, same draws (csrc/sample.hip)
+        if wide:
+            prep = prep.replace("ladder_mixture_sample_", "ladder_mixture_sample_wide_")
+        nbytes = L.query("ladder_mixture_sample_wide_param_bytes" if wide else "ladder_mixture_sample_param_bytes", K, R)
         if nbytes == 0:
-            raise ValueError("the device sampler takes 1 <= R <= 64 and K >= 1 (got K = %d, R = %d)" % (K, R))
+            raise ValueError("the device sampler takes K >= 1 and 1 <= R <= 64, or 64 < R <= 256 with R %% 16 == 0 (got K = %d, R = %d)" % (K, R))
         params = torch.empty(nbytes, dtype=torch.uint8, device=ctx.device)
-        if len(keep) == 3:
+        if len(keep) == 3 and wide:
+            fws = torch.empty(L.query("ladder_mixture_sample_wide_prepare_workspace_bytes", K, R), dtype=torch.uint8, device=ctx.device)
+            L.call(prep, _p(keep[0]), _p(keep[1]), _p(keep[2]), K, R, _p(params), _p(fws), fws.numel(), st)
+        elif len(keep) == 3:
             L.call(prep, _p(keep[0]), _p(keep[1]), _p(keep[2]), K, R, _p(params), st)
         else:
             L.call(prep, _p(keep[0]), _p(keep[1]), K, R, _p(params), st)
