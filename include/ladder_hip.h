@@ -996,6 +996,31 @@ int ladder_mixture_sample_wide_prepare_diag(const float* comp_mean, const float*
 int ladder_mixture_sample_wide(const void* params, int K, int R, int n, int64_t first, const float* u, const float* eps, uint64_t seed,
                                uint64_t offset, float* out, int* comp, ladder_stream_t stream);
 
+/* ---------------------------------------------------------------- N22: the EM mixture fit of the "GMM" prior on a WIDE code (csrc/emgmm_wide.hip)
+ * The fit of N18 -- same algorithm, state and stats layout, moments, labels, feed copies, protocol and status codes -- for the widths of N21:
+ * 64 < R <= 256, R % 16 == 0, and 1 <= K <= 64 (the reference's shipped codes/celeba_config.json: code_size 256, n_mixtures 50).  The entry points of
+ * N18 keep refusing R > 64; these refuse R <= 64, so every width has exactly one fit.
+ *   E-step: grid (64-sample slice, component); precisions_cholesky_[k] passes through LDS one 16-column panel at a time (rows 0 .. 16 jb + 15 of column
+ *   block jb, the all-zero blocks below the diagonal skipped), the log terms go to the responsibilities [N,K], a second pass normalises each row.
+ *   Statistics: grid (component, row split, 16-row band of the second moment).  M-step: one workgroup per component; the float64 covariance itself
+ *   (not its fp32 feed copy) is factored in a working matrix of `ws` (ladder_emgmm_wide_mstep_workspace_bytes(K, R), the panel factorisation of N21).
+ *   ws of ladder_emgmm_wide_estep >= ladder_emgmm_wide_workspace_bytes(N_local, K, R), as in N18.
+ * ladder_emgmm_wide_prepare: as ladder_emgmm_prepare, with the M-step's workspace.  A non-positive or NaN pivot is component status -1, state[-2] = -1,
+ * state[-1] = 1; that component's precisions_cholesky_ is left as it was.
+ * Size queries return 0 for an unsupported (K, R).  LADDER_E_SHAPE (nothing launched) for R <= 64, R > 256, R % 16 != 0, K < 1, K > 64, N < 1 or a
+ * NULL array; LADDER_E_ALIGN for double arrays off 8 bytes; LADDER_E_WORKSPACE for a NULL or short workspace. */
+size_t ladder_emgmm_wide_state_doubles(int K, int R);
+size_t ladder_emgmm_wide_stats_doubles(int K, int R);
+size_t ladder_emgmm_wide_shift_doubles(int R);
+size_t ladder_emgmm_wide_workspace_bytes(int N, int K, int R);
+size_t ladder_emgmm_wide_mstep_workspace_bytes(int K, int R);
+int ladder_emgmm_wide_shift(const float* X, int N, int R, double* moments, ladder_stream_t stream);
+int ladder_emgmm_wide_estep(const float* X, int N, int K, int R, const int* labels, const double* state, const double* moments, double* stats,
+                            void* ws, size_t ws_bytes, ladder_stream_t stream);
+int ladder_emgmm_wide_mstep(const double* stats, const double* moments, int K, int R, double* state, void* ws, size_t ws_bytes, double reg_covar,
+                            double tol, int max_iter, int it, float* weights, float* means, float* covs, ladder_stream_t stream);
+int ladder_emgmm_wide_prepare(double* state, int K, int R, void* ws, size_t ws_bytes, ladder_stream_t stream);
+
 /* ---------------------------------------------------------------- helpers */
 /* HOST function (no device work): CRC-32C (Castagnoli) of host memory, crc = 0 to start, chainable.  Used by the
  * tf.train.Saver checkpoint-v2 reader/writer (codes/base.py:37-85: saver_ae / saver_prior) for block and tensor checksums. */

@@ -120,6 +120,15 @@ PROTOTYPES = {
     "ladder_emgmm_estep": (_i, [_p, _i, _i, _i, _p, _p, _p, _p, _p, _z, _p]),
     "ladder_emgmm_mstep": (_i, [_p, _p, _i, _i, _p, _d, _d, _i, _i, _p, _p, _p, _p]),
     "ladder_emgmm_prepare": (_i, [_p, _i, _i, _p]),
+    "ladder_emgmm_wide_state_doubles": (_z, [_i, _i]),
+    "ladder_emgmm_wide_stats_doubles": (_z, [_i, _i]),
+    "ladder_emgmm_wide_shift_doubles": (_z, [_i]),
+    "ladder_emgmm_wide_workspace_bytes": (_z, [_i, _i, _i]),
+    "ladder_emgmm_wide_mstep_workspace_bytes": (_z, [_i, _i]),
+    "ladder_emgmm_wide_shift": (_i, [_p, _i, _i, _p, _p]),
+    "ladder_emgmm_wide_estep": (_i, [_p, _i, _i, _i, _p, _p, _p, _p, _p, _z, _p]),
+    "ladder_emgmm_wide_mstep": (_i, [_p, _p, _i, _i, _p, _p, _z, _d, _d, _i, _i, _p, _p, _p, _p]),
+    "ladder_emgmm_wide_prepare": (_i, [_p, _i, _i, _p, _z, _p]),
     "ladder_kmeans_state_doubles": (_z, [_i, _i]),
     "ladder_kmeans_draws_doubles": (_z, [_i]),
     "ladder_kmeans_workspace_bytes": (_z, [_i, _i, _i]),

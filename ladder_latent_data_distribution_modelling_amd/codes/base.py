@@ -15,7 +15,7 @@ class BaseTrain:
     def __init__(self, sess, model, data, config):
         self.model, self.config, self.sess, self.data = model, config, sess, data
         from .mixture_fit import check_device_fit_width
-        check_device_fit_width(config)          # a device fit of a mixture on more than 64 dimensions cannot work: say so before the first epoch
+        check_device_fit_width(config)          # a device fit at a width no kernel takes cannot work: say so before the first epoch
         self.engine = model.engine
         # replay each run as one captured hipGraph after two eager warm-ups (config key `use_hip_graphs`, default on)
         # (default: on for the MNIST nets, whose ~350 short launches per iteration are host-bound in eager mode; off for CelebA, where
@@ -313,7 +313,8 @@ class BaseTrain:
 
     def _fit_GMM_z(self, iterator, mode):
         """prior "GMM" (base.py:699-710, 749-789): EM mixture on z samples.  sklearn backend (the default for this prior): host fit on rank 0 +
-        broadcast.  Device backend (`gm_fit_backend: "hip"` set explicitly): codes/emgmm.py through _fit, sharded under data parallelism
+        broadcast.  Device backend (`gm_fit_backend: "hip"`, or "hip_wide" for code sizes up to 256, set explicitly): codes/emgmm.py through _fit,
+        which picks the kernel family from the samples' width; sharded under data parallelism
         unless `gm_fit_mode` says "replicated"; the parameters stay on the device."""
         comm = self.engine.ctx.comm
         bs_global = int(self.config["batch_size"]) * comm.world

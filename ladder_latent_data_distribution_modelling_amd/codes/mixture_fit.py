@@ -79,17 +79,39 @@ def check_kmeans_backend(backend):
 
 
 DEVICE_FIT_MAX_R = 64        # csrc/emgmm.hip, csrc/vbgmm.hip and csrc/kmeans.hip end here; the mixture term and the samplers go on to 256
+DEVICE_FIT_WIDE_MIN_R, DEVICE_FIT_WIDE_MAX_R, DEVICE_FIT_WIDE_STEP = 80, 256, 16      # csrc/emgmm_wide.hip: the widths of csrc/chol_wide.h
+DEVICE_FIT_WIDTH_RULE = "1 .. %d dimensions, or %d .. %d in steps of %d" % (DEVICE_FIT_MAX_R, DEVICE_FIT_WIDE_MIN_R, DEVICE_FIT_WIDE_MAX_R,
+                                                                            DEVICE_FIT_WIDE_STEP)
+GM_FIT_DEVICE_BACKENDS = ("hip", "hip_wide")     # "hip": the narrow kernels alone; "hip_wide" (prior "GMM"): whichever family takes the width
+
+
+def device_fit_width_ok(R, wide):
+    """Whether a device EM fit exists for R dimensions: the narrow kernels, and with `wide` those of csrc/emgmm_wide.hip."""
+    if 1 <= R <= DEVICE_FIT_MAX_R:
+        return True
+    return bool(wide) and DEVICE_FIT_WIDE_MIN_R <= R <= DEVICE_FIT_WIDE_MAX_R and R % DEVICE_FIT_WIDE_STEP == 0
 
 
 def check_device_fit_width(config):
-    """prior "GMM" fits its mixture on z, so the mixture dimension is code_size: beyond 64 only the host fits exist (the defaults: sklearn's EM and
-    sklearn's k-means).  Raises ValueError naming the config key that asks for a device fit.  (prior "ours": codes/vbgmm.py checks its own.)"""
+    """prior "GMM" fits its mixture on z, so the mixture dimension is code_size.  gm_fit_backend "hip" and kmeans_backend "hip" end at 64 dimensions
+    (beyond: the host fits, which are the defaults, or for the EM fit gm_fit_backend "hip_wide"); "hip_wide" is the device EM fit of prior "GMM" at
+    every width a kernel family takes (DEVICE_FIT_WIDTH_RULE).  Raises ValueError naming the config key that asks for what does not exist.
+    (prior "ours": codes/vbgmm.py checks its own width.)"""
+    if config.get("gm_fit_backend") == "hip_wide":
+        if config.get("prior") != "GMM":
+            raise ValueError('gm_fit_backend: "hip_wide" is the device EM fit of prior "GMM", not of prior %r (use "hip" or "sklearn" there)'
+                             % (config.get("prior"),))
+        if not device_fit_width_ok(int(config["code_size"]), wide=True):
+            raise ValueError('gm_fit_backend: "hip_wide" fits mixtures on %s, prior "GMM" with code_size = %d needs the host fit '
+                             '(leave gm_fit_backend out or set it to "sklearn")' % (DEVICE_FIT_WIDTH_RULE, int(config["code_size"])))
     if config.get("prior") != "GMM" or int(config["code_size"]) <= DEVICE_FIT_MAX_R:
         return
     for key in ("gm_fit_backend", "kmeans_backend"):
         if config.get(key) == "hip":
+            hint = ' or, for a device fit on %d .. %d dimensions in steps of %d, to "hip_wide"' % (
+                DEVICE_FIT_WIDE_MIN_R, DEVICE_FIT_WIDE_MAX_R, DEVICE_FIT_WIDE_STEP) if key == "gm_fit_backend" else ""
             raise ValueError('%s: "hip" fits mixtures on at most %d dimensions, prior "GMM" with code_size = %d needs the host fit '
-                             '(leave %s out or set it to "sklearn")' % (key, DEVICE_FIT_MAX_R, int(config["code_size"]), key))
+                             '(leave %s out or set it to "sklearn"%s)' % (key, DEVICE_FIT_MAX_R, int(config["code_size"]), key, hint))
 
 
 def _gather_ragged(parts, x, comm):

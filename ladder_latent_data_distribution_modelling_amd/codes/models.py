@@ -41,6 +41,8 @@ class BaseModel:
     # the same algorithm on the device (codes/kmeans.py); it has no effect on the host objects.
     def define_GM_prior(self):
         self.GM_prior_training = None
+        from .mixture_fit import GM_FIT_DEVICE_BACKENDS, check_device_fit_width
+        check_device_fit_width(self.config)          # (every prior: gm_fit_backend "hip_wide" belongs to prior "GMM" alone)
         if self.config["prior"] == "ours":
             # (config key `gm_random_state`, optional: seeds the k-means initialisation of a cold fit; None = sklearn's default, as the reference)
             kw = dict(n_components=int(self.config["n_mixtures"]), covariance_type="full", max_iter=1000, n_init=1,
@@ -56,12 +58,10 @@ class BaseModel:
                 from sklearn.mixture import BayesianGaussianMixture
                 self.GM_prior_training = BayesianGaussianMixture(**kw)
         elif self.config["prior"] == "GMM":          # base.py:101-106: plain EM mixture on z (R = code_size)
-            # The host fit unless the config EXPLICITLY asks for the device one (codes/emgmm.py -> csrc/emgmm.hip): an absent key keeps sklearn here,
-            # unlike "ours" above.
-            from .mixture_fit import check_device_fit_width
-            check_device_fit_width(self.config)
+            # The host fit unless the config EXPLICITLY asks for the device one (codes/emgmm.py): "hip" -> csrc/emgmm.hip, code_size <= 64;
+            # "hip_wide" -> that or csrc/emgmm_wide.hip, code_size 80 .. 256 in steps of 16.  An absent key keeps sklearn here, unlike "ours" above.
             kw = dict(n_components=int(self.config["n_mixtures"]), covariance_type="full", max_iter=1000, n_init=1, warm_start=True)
-            if self.config.get("gm_fit_backend") == "hip":
+            if self.config.get("gm_fit_backend") in GM_FIT_DEVICE_BACKENDS:
                 from .emgmm import DeviceGaussianMixture
                 comm = self.engine.ctx.comm
                 self.GM_prior_training = DeviceGaussianMixture(

@@ -1,5 +1,7 @@
 // The float64 factorisation of a WIDE covariance (64 < R <= 256, R % 16 == 0), shared by the prepare paths of the wide mixture
-// (csrc/mixture_wide.hip) and of the wide sampler (csrc/sample.hip).  One workgroup of CW_THREADS = 256 threads per component, thread i = row i.
+// (csrc/mixture_wide.hip) and of the wide sampler (csrc/sample.hip), which factor the fp32 feed copy (chol_wide_factor), and by the M-step of the
+// wide EM fit (csrc/emgmm_wide.hip), which factors its float64 covariance where it stands (chol_wide_factor_in_place).
+// One workgroup of CW_THREADS = 256 threads per component, thread i = row i.
 //
 // The working matrix W [R][R] (float64, row-major) lives in a caller-provided slot of global memory -- a 256 x 256 float64 matrix is 512 KB,
 // a workgroup has 160 KB of LDS -- and only a 16-column panel of it sits in LDS at a time:
@@ -34,11 +36,10 @@ struct CwShared {
 // Linv[i][c] of a factored W (INVERSE), i >= c
 __device__ __forceinline__ double cw_linv(const double* W, int R, int i, int c) { return i == c ? 1.0 / W[(size_t)c * R + c] : W[(size_t)c * R + i]; }
 
+// The factorisation of a W already filled in place (the lower triangle and the diagonal blocks are read), after the barrier that publishes it.
 template <bool INVERSE>
-__device__ __forceinline__ bool chol_wide_factor(const float* __restrict__ cov, int R, double* W, CwShared& sh) {
+__device__ __forceinline__ bool chol_wide_factor_in_place(int R, double* W, CwShared& sh) {
   const int tid = threadIdx.x, i = tid;
-  for (int e = tid; e < R * R; e += CW_THREADS) W[e] = (double)cov[e];
-  __syncthreads();
   bool failed = false;
   for (int j0 = 0; j0 < R && !failed; j0 += CW_PANEL) {
     const bool mine = i >= j0 && i < R;
@@ -111,6 +112,14 @@ __device__ __forceinline__ bool chol_wide_factor(const float* __restrict__ cov, 
     __syncthreads();
   }
   return false;
+}
+
+// W = the float64 copy of an fp32 covariance [R,R], then the factorisation above.
+template <bool INVERSE>
+__device__ __forceinline__ bool chol_wide_factor(const float* __restrict__ cov, int R, double* W, CwShared& sh) {
+  for (int e = threadIdx.x; e < R * R; e += CW_THREADS) W[e] = (double)cov[e];
+  __syncthreads();
+  return chol_wide_factor_in_place<INVERSE>(R, W, sh);
 }
 
 // sum_j log L[j][j] of a factored W, the terms added in index order; the same value in every thread.  `scratch`: CW_MAXR doubles of LDS.

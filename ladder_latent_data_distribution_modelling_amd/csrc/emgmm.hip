@@ -21,30 +21,15 @@
 // Every kernel returns at once when `done` is set, so the host may enqueue iterations ahead and read the flag every few iterations (the contract of
 // ladder_vbgmm_shard_*).  No atomics: every sum has one fixed order, so a fit gives the same bits on every run and for every `check_every`.
 //
-// state (doubles): weights [K] | means [K,R] | covariances [K,R,R] | precisions_cholesky [K,R,R] | log_det [K] | component status [K] |
-//                  the tail of csrc/fit_util.h: lower_bound_, n_iter_, converged_, done
+// The state layout (EmState) and emgmm_finish_kernel are csrc/em_state.h's, shared with the fit for 80 <= R <= 256 (csrc/emgmm_wide.hip).
 //
 // All but the policy, the M-step's own arithmetic and the state layout is shared with the wide variational fit of csrc/vbgmm.hip: the E-step body,
 // the column-sum / statistics / reduce kernels, the host side of the E-step, the centring and the factorisation in csrc/fit_mfma.h, the `done`
 // test and the end of an iteration in csrc/fit_util.h.
+#include "em_state.h"
 #include "fit_mfma.h"
 
 namespace {
-
-struct EmState {
-  double *w, *means, *cov, *pchol, *logdet, *cstat, *tail;
-  __host__ __device__ EmState(double* s, int K, int R) {
-    w = s;
-    means = w + K;
-    cov = means + (size_t)K * R;
-    pchol = cov + (size_t)K * R * R;
-    logdet = pchol + (size_t)K * R * R;
-    cstat = logdet + K;
-    tail = cstat + K;
-  }
-};
-
-__host__ __device__ inline size_t em_state_doubles(int K, int R) { return (size_t)K * (3 + R + 2 * (size_t)R * R) + 4; }
 
 // ------------------------------------------------------------------------------------------------ E-step
 // _estimate_weighted_log_prob and _estimate_log_prob_resp as the policy of fit_estep_slice: constants log|P_k| and log w_k, the slice scalar is
@@ -137,18 +122,6 @@ __global__ __launch_bounds__(64) void emgmm_prepare_kernel(double* state, int K,
   for (int e = tid; e < R * R; e += 64) s_A[(e / R) * FIT_LDC + (e % R)] = C[e];
   __syncthreads();
   em_prepare_component(s_A, R, k, S, tid);
-}
-
-// The end of iteration `it`, one thread: component status, lower bound of this iteration's E-step, convergence test, n_iter_.
-// it < 0: after emgmm_prepare_kernel -- only the status is folded into the tail.
-__global__ void emgmm_finish_kernel(const double* __restrict__ stats, const double* __restrict__ mom, double* state, int K, int R, double tol, int max_iter,
-                                    int it) {
-  EmState S(state, K, R);
-  if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  if (it >= 0 && fit_done(S.tail)) return;
-  bool bad = false;
-  for (int k = 0; k < K; ++k) bad = bad || (S.cstat[k] < 0.0);
-  fit_end_iteration(S.tail, bad, it, tol, max_iter, [&] { return stats[0] / mom[R]; });      // np.mean(log_prob_norm) over ALL samples
 }
 
 }  // namespace

@@ -1,0 +1,132 @@
+"""The EM fit of the "GMM" prior on 80 .. 256 dimensions (csrc/emgmm_wide.hip, codes/emgmm.py) without a GPU: every parity case is decidable and
+gives the iteration counts written beside it, the algorithm the kernels implement (tests/emgmm_ref.py: NumpyEM) holds the project's bars against
+sklearn on each, the new exports answer their size queries, and the config rules of gm_fit_backend "hip_wide" hold."""
+import os
+import sys
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import emgmm_wide_ref as W  # noqa: E402
+
+
+@pytest.fixture(scope="module")
+def lib():
+    from ladder_latent_data_distribution_modelling_amd import _lib
+    from ladder_latent_data_distribution_modelling_amd.csrc import build
+    return _lib.load(build.build(verbose=False))
+
+
+@pytest.mark.parametrize("i", range(len(W.CASES)), ids=W.IDS)
+def test_case_is_decidable_and_the_restatement_holds_the_bars(i):
+    """W.reference asserts the decidability precondition and the iteration counts of the case on sklearn's own fits.  The device algorithm in numpy
+    (WideNumpyEM: NumpyEM with its sums cut for these widths) then reproduces n_iter_ / converged_ and sits inside BAR_LB and BARS on the cold fit and
+    the warm refit -- but for precisions_cholesky_ of the rank-deficient case's warm refit, whose bar comes from NumpyEM's own error (W.bars_for)."""
+    N, R, K, max_iter, centres, spread, seed, n_iters = W.CASES[i]
+    snaps = W.reference(i)
+    assert len(snaps) == sum(n is not None for n in n_iters)
+    X1, X2 = W.data(N, R, centres, spread, seed)
+    mine = W.WideNumpyEM(K, tol=W.KW["tol"], reg_covar=W.KW["reg_covar"], max_iter=max_iter)
+    for f, (X, lab, snap) in enumerate(zip((X1, X2), (W.kmeans_labels(X1, K), None), snaps)):
+        mine.fit(X, lab)
+        assert (mine.n_iter_, mine.converged_) == (snap["n_iter_"], snap["converged_"])
+        assert snap["warned"] == (0 if snap["converged_"] else 1)
+        W.assert_close_case(i, f, mine, W.Snap(snap))
+
+
+def test_rank_deficient_case_bar_is_what_numpy_em_measures():
+    """NumpyEM itself (tests/emgmm_ref.py, unchanged) on the rank-deficient case: inside BARS on the cold fit; on the warm refit everything but
+    precisions_cholesky_ is (W.numpy_pchol_ratio asserts it), and that array misses its bar -- by the factor recorded in W.NUMPY_PCHOL_RATIO
+    (0.57 cold, 14.33 warm when the bar was derived), from which W.bars_for takes the one widened bar."""
+    N, R, K = W.CASES[W.RANK_DEFICIENT][:3]
+    assert N // K < R
+    cold, warm = W.numpy_pchol_ratio()
+    print("NumpyEM precisions_cholesky_ error / bar: cold %.4g, warm %.4g (recorded %r)" % (cold, warm, W.NUMPY_PCHOL_RATIO))
+    assert cold <= 1.0 < warm <= W.OTHER_ORDER * W.NUMPY_PCHOL_RATIO[1]
+    assert W.NUMPY_PCHOL_RATIO[0] <= 1.0 < W.NUMPY_PCHOL_RATIO[1]
+    assert W.bars_for(W.RANK_DEFICIENT, 0) == W.BARS and W.bars_for(0, 1) == W.BARS
+    wide = W.bars_for(W.RANK_DEFICIENT, 1)
+    assert {n: b for n, b in wide.items() if n != "precisions_cholesky_"} == {n: b for n, b in W.BARS.items() if n != "precisions_cholesky_"}
+    np.testing.assert_allclose(wide["precisions_cholesky_"], (1.433e-4, 1.433e-7), rtol=1e-12)
+
+
+def test_first_case_has_a_soft_e_step():
+    """The R = 80 case is there for the soft E-step: a good part of its rows carry a responsibility strictly between 1e-6 and 1 - 1e-6."""
+    from sklearn.mixture import GaussianMixture
+    N, R, K, max_iter, centres, spread, seed, _ = W.CASES[0]
+    X1 = W.data(N, R, centres, spread, seed)[0].astype(np.float64)
+    r = GaussianMixture(n_components=K, max_iter=max_iter, **W.KW).fit(X1).predict_proba(X1)
+    soft = ((r > 1e-6) & (r < 1 - 1e-6)).any(1).mean()
+    print("rows with a soft responsibility: %.3f" % soft)
+    assert soft >= 0.25
+
+
+def test_size_queries_of_the_wide_family(lib):
+    for K, R in [(1, 80), (3, 96), (50, 256), (64, 128)]:
+        assert lib.ladder_emgmm_wide_state_doubles(K, R) == K * (3 + R + 2 * R * R) + 4 == lib.ladder_emgmm_state_doubles(K, R), (K, R)
+        assert lib.ladder_emgmm_wide_stats_doubles(K, R) == 1 + K * (1 + R + R * R) == lib.ladder_emgmm_stats_doubles(K, R), (K, R)
+        assert lib.ladder_emgmm_wide_shift_doubles(R) == R + 1
+        assert lib.ladder_emgmm_wide_workspace_bytes(2048, K, R) >= 2048 * K * 8
+        assert lib.ladder_emgmm_wide_workspace_bytes(0, K, R) == 0
+        assert lib.ladder_emgmm_wide_mstep_workspace_bytes(K, R) >= 8 * K * R * R
+    for K, R in [(3, 64), (3, 16), (3, 72), (3, 250), (3, 272), (0, 80), (65, 80), (-1, 256)]:
+        assert lib.ladder_emgmm_wide_state_doubles(K, R) == 0, (K, R)
+        assert lib.ladder_emgmm_wide_stats_doubles(K, R) == 0, (K, R)
+        assert lib.ladder_emgmm_wide_workspace_bytes(2048, K, R) == 0, (K, R)
+        assert lib.ladder_emgmm_wide_mstep_workspace_bytes(K, R) == 0, (K, R)
+    for R in (64, 72, 272, 0):
+        assert lib.ladder_emgmm_wide_shift_doubles(R) == 0, R
+    # the narrow family keeps its own answers: its launches refuse R > 64 (tests/test_gpu_emgmm.py)
+    assert lib.ladder_emgmm_shift_doubles(64) == 65
+
+
+def test_shape_rejections_before_launch(lib):
+    """Host buffers: every refusal below returns before a pointer is touched or a kernel launched."""
+    import ctypes
+    buf = ctypes.create_string_buffer(4096 + 16)
+    p = (ctypes.addressof(buf) + 15) // 16 * 16
+    big = 1 << 40
+    for K, R in ((3, 64), (3, 72), (3, 272), (65, 80), (0, 80)):
+        assert lib.ladder_emgmm_wide_estep(p, 8, K, R, None, p, p, p, p, big, None) == -1, (K, R)
+        assert lib.ladder_emgmm_wide_mstep(p, p, K, R, p, p, big, 1e-6, 1e-3, 10, 1, p, p, p, None) == -1, (K, R)
+        assert lib.ladder_emgmm_wide_prepare(p, K, R, p, big, None) == -1, (K, R)
+    for R in (64, 72, 272):
+        assert lib.ladder_emgmm_wide_shift(p, 8, R, p, None) == -1, R
+    assert lib.ladder_emgmm_wide_shift(p, 0, 80, p, None) == -1
+    assert lib.ladder_emgmm_wide_estep(p, 0, 3, 80, None, p, p, p, p, big, None) == -1
+    assert lib.ladder_emgmm_wide_estep(p, 8, 3, 80, None, p + 4, p, p, p, big, None) == -2
+    assert lib.ladder_emgmm_wide_mstep(p, p + 4, 3, 80, p, p, big, 1e-6, 1e-3, 10, 1, p, p, p, None) == -2
+    assert lib.ladder_emgmm_wide_prepare(p + 4, 3, 80, p, big, None) == -2
+    assert lib.ladder_emgmm_wide_estep(p, 8, 3, 80, None, p, p, p, p, lib.ladder_emgmm_wide_workspace_bytes(8, 3, 80) - 1, None) == -3
+    short = lib.ladder_emgmm_wide_mstep_workspace_bytes(3, 80) - 1
+    assert lib.ladder_emgmm_wide_mstep(p, p, 3, 80, p, p, short, 1e-6, 1e-3, 10, 1, p, p, p, None) == -3
+    assert lib.ladder_emgmm_wide_mstep(p, p, 3, 80, p, None, big, 1e-6, 1e-3, 10, 1, p, p, p, None) == -3
+    assert lib.ladder_emgmm_wide_prepare(p, 3, 80, p, short, None) == -3
+
+
+def test_config_rules_of_hip_wide():
+    from ladder_latent_data_distribution_modelling_amd.codes.emgmm import family_prefix
+    from ladder_latent_data_distribution_modelling_amd.codes.mixture_fit import check_device_fit_width
+    cfg = dict(prior="GMM", n_mixtures=6)
+    for size in (80, 256, 16, 64, 1, 144):
+        check_device_fit_width(dict(cfg, code_size=size, gm_fit_backend="hip_wide"))
+    for size in (72, 272, 65, 250):
+        with pytest.raises(ValueError, match=r"gm_fit_backend.*hip_wide.*80 \.\. 256 in steps of 16"):
+            check_device_fit_width(dict(cfg, code_size=size, gm_fit_backend="hip_wide"))
+    for prior in ("ours", "standard_gaussian", "hierarchical", "vampPrior"):
+        with pytest.raises(ValueError, match=r"gm_fit_backend.*hip_wide.*GMM"):
+            check_device_fit_width(dict(cfg, prior=prior, code_size=16, representation_size=8, gm_fit_backend="hip_wide"))
+    with pytest.raises(ValueError, match="gm_fit_backend.*64"):                       # "hip" keeps ending at 64 dimensions ...
+        check_device_fit_width(dict(cfg, code_size=128, gm_fit_backend="hip"))
+    with pytest.raises(ValueError, match="hip_wide"):                                 # ... and now says where to go
+        check_device_fit_width(dict(cfg, code_size=128, gm_fit_backend="hip"))
+    with pytest.raises(ValueError, match="kmeans_backend.*64"):                       # device k-means beyond 64 dimensions stays refused
+        check_device_fit_width(dict(cfg, code_size=128, gm_fit_backend="hip_wide", kmeans_backend="hip"))
+    check_device_fit_width(dict(cfg, code_size=64, gm_fit_backend="hip_wide", kmeans_backend="hip"))
+    # the mixture object picks its entry points from the width, and says which widths exist
+    assert family_prefix(64) == "ladder_emgmm_" and family_prefix(1) == "ladder_emgmm_"
+    assert family_prefix(80) == family_prefix(256) == "ladder_emgmm_wide_"
+    for R in (72, 272, 0):
+        with pytest.raises(ValueError, match=r"80 \.\. 256 in steps of 16"):
+            family_prefix(R)
