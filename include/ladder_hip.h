@@ -74,6 +74,27 @@ int ladder_conv2d_fwd(const float* x, const float* w, const float* bias, float* 
                       int N, int H, int W, int Cin, int Ho, int Wo, int Cout,
                       int KH, int KW, int stride, int pad_t, int pad_l, int act,
                       void* ws, size_t ws_bytes, ladder_stream_t stream);
+/* The forms of the gather kernel behind ladder_conv2d_fwd / ladder_conv2d_bwd_data / ladder_dense_fwd, for A/B runs and tests: `variant` bit 0 =
+ * small maps (at most 16 output positions, more than one tap, a tile of images) run position-major rows and skip the chunks whose tap lies in
+ * the padding for a whole tile; bits 1-2 = prefetch depth - 1 (global loads of 1 ... 4 chunks in flight) of the 64x64 and 32x128 tiles.  Every
+ * variant gives the same bits; 0 is the first form.  The plain entry points run the default (1), or LADDER_IGEMM_VARIANT from the environment,
+ * read once.  LADDER_E_SHAPE for a variant outside 0 ... 7. */
+int ladder_conv2d_fwd_variant(const float* x, const float* w, const float* bias, float* y,
+                              int N, int H, int W, int Cin, int Ho, int Wo, int Cout,
+                              int KH, int KW, int stride, int pad_t, int pad_l, int act,
+                              void* ws, size_t ws_bytes, int variant, ladder_stream_t stream);
+int ladder_conv2d_bwd_data_variant(const float* dy, const float* wT, float* dx,
+                                   int N, int H, int W, int Cin, int Ho, int Wo, int Cout,
+                                   int KH, int KW, int stride, int pad_t, int pad_l,
+                                   const float* gate_y, int gate_act,
+                                   void* ws, size_t ws_bytes, int variant, ladder_stream_t stream);
+int ladder_dense_fwd_variant(const float* x, const float* w, const float* bias, float* y,
+                             int M, int K, int N, int act, void* ws, size_t ws_bytes, int variant, ladder_stream_t stream);
+/* Host arithmetic: the 16-deep K chunks the gather kernel issues for this convolution's forward (bwd_data == 0) or backward-data (arguments as
+ * for ladder_conv2d_bwd_data), over all tiles and launches, under `variant` (-1 = the default; 0 = the full tap walk).  One chunk of a
+ * BM x BN tile is 2 * BM * BN * 16 FLOP.  -1 when another kernel runs the call. */
+long ladder_igemm_fwd_live_chunks(int N, int H, int W, int Cin, int Ho, int Wo, int Cout, int KH, int KW, int stride, int pad_t, int pad_l,
+                                  int bwd_data, int variant);
 /* Optional scratch of the forward-type calls (conv fwd / bwd_data, dense fwd / bwd_data): when the output tiling cannot
  * fill the 256 CUs (small M*Cout, long K) the contraction is split over K into `ws` and summed in a fixed order by a
  * second kernel (bias/activation applied there).  ws == NULL or too small => single-pass kernel.  M, K, Cout = GEMM extents. */

@@ -41,6 +41,22 @@ inline bool set_conv_taps(IgemmDesc& d) {
   return true;
 }
 
+// The tap table of a descriptor as the gather kernel's K loop reads it: 32-bit entries, so that a wave-uniform tap index is a scalar load.
+// coff = element offset of the tap's input pixel from the row's base, kbase = first row of the tap in the [K x Cout] filter matrix,
+// dhw = (tap_dh << 16) | (tap_dw & 0xffff).
+struct TapTab {
+  int coff[28], kbase[28], dhw[28];
+};
+inline TapTab make_taptab(const IgemmDesc& d) {
+  TapTab t{};
+  for (int i = 0; i < d.ntaps; ++i) {
+    t.coff[i] = (d.tap_dh[i] * d.W + d.tap_dw[i]) * d.Cin;
+    t.kbase[i] = d.tap_w[i] * d.Cin;
+    t.dhw[i] = (int)(((unsigned)(int)d.tap_dh[i] << 16) | ((unsigned)(int)d.tap_dw[i] & 0xffffu));
+  }
+  return t;
+}
+
 namespace {
 
 constexpr int kThreads = 256;
@@ -167,9 +183,16 @@ SplitPlan plan_splitk(long M, int K, int Cout, int bm, int bn);
 bool halo_eligible(const IgemmDesc& d);
 int dispatch_fwd(const float* x, const float* w, const float* bias, float* y, const IgemmDesc& d, void* ws, size_t ws_bytes, hipStream_t st,
                  const float* gate = nullptr, int gate_act = 0);
+// igemm_fwd_kernel variants: bit 0 = position-major rows and padding-tap skipping on small maps, bits 1-2 = prefetch depth - 1; -1 = the default
+// (default: the skipping on, one chunk ahead -- deeper prefetch measured within the run-to-run spread of the step, profiles/gather_small_maps.md)
+constexpr int IGEMM_VARIANT_DEFAULT = 1;
+int igemm_default_variant();                                 // IGEMM_VARIANT_DEFAULT, or LADDER_IGEMM_VARIANT from the environment (read once)
+int dispatch_fwd(const float* x, const float* w, const float* bias, float* y, const IgemmDesc& d, void* ws, size_t ws_bytes, hipStream_t st,
+                 const float* gate, int gate_act, int variant);
 // second pass of a split-K launch: y = act(sum of the `splits` partials [M][Cout] + bias) (* act'(gate)), dense or through d's output mapping
+// (posmajor: the partial rows are ordered (position, image) -- the first pass ran over position-major rows)
 void launch_splitk_epilogue(const float* part, const float* bias, float* y, int splits, const IgemmDesc& d, const float* gate, int gate_act,
-                            hipStream_t st);
+                            hipStream_t st, bool posmajor = false);
 
 // igemm_wgrad.hip: the fp32 filter gradients
 struct WgradPlan { int bm, bn, tiles_k, tiles_n, splits, m_per_split; };

@@ -15,17 +15,24 @@
 // Common structure: 16-deep K chunks staged through double-buffered LDS (global -> registers issued before the MFMA block of
 // the current chunk, registers -> LDS after it, one barrier per chunk); NHWC keeps ci contiguous, so every global load is a
 // 16-byte access; padding lanes read a 16-byte zero buffer so loads stay unconditional.
+// The small tiles of igemm_fwd_kernel (64x64, 32x128) come in variants (ladder_*_variant, LADDER_IGEMM_VARIANT; profiles/gather_small_maps.md):
+// on maps of at most 16 positions the rows run position-major and a tile walks only the chunks whose tap is inside the image for one of its
+// rows (on by default); the global loads can run 1 ... 4 chunks ahead in as many register sets (default 1).  Every variant gives the same bits.
 #include "igemm.h"
 
 namespace {
 
-template <int BM, int BN, int WM, int WN, bool VECA, bool VECB>
+// D: prefetch depth = register sets of global loads in flight (the loads of chunk j + D are issued before the MFMA block of chunk j;
+// D = 1 is one chunk ahead).  SKIPPABLE: the instantiation can walk a compacted chunk list (`skip`: drop the chunks whose tap lies in
+// the padding for every row of the tile) over position-major rows (`posmajor`: row m = (position m / N, image m % N)).
+template <int BM, int BN, int WM, int WN, bool VECA, bool VECB, int D = 1, bool SKIPPABLE = false>
 __global__ __launch_bounds__(kThreads, (BM * BN >= 128 * 128) ? IGEMM_FWD_MINW : IGEMM_MINW) void igemm_fwd_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                              const float* __restrict__ bias, float* __restrict__ y,
                                                              const IgemmDesc d, const int tiles_n, const bool fast,
                                                              float* __restrict__ part, const int chunks_per_split,
                                                              const float* __restrict__ gate, const int gate_act,
-                                                             float* __restrict__ stats_part) {
+                                                             float* __restrict__ stats_part, const bool skip, const bool posmajor,
+                                                             const FastDiv div_n, const TapTab tt) {
   constexpr int LDA = BK + 1;  // odd row stride: conflict-free ds_read_b32 of A fragments
   constexpr int TM = BM / WM, TN = BN / WN, MI = TM / 32, NI = TN / 32;
   constexpr int A_UNITS = BM * (BK / 4), B_UNITS = BK * (BN / 4);
@@ -58,7 +65,11 @@ __global__ __launch_bounds__(kThreads, (BM * BN >= 128 * 128) ? IGEMM_FWD_MINW :
     const int m = m0 + a_row[i];
     a_ok[i] = (u < A_UNITS) && (m < d.M);
     const uint32_t mm = a_ok[i] ? m : 0;
-    const uint32_t n_img = fdiv(mm, d.div_howo), rem = mm - n_img * HoWo;
+    uint32_t n_img = fdiv(mm, d.div_howo), rem = mm - n_img * HoWo;
+    if (SKIPPABLE && posmajor) {   // all images of one output position together: a tile's rows share their padding taps
+      rem = fdiv(mm, div_n);
+      n_img = mm - rem * d.N;
+    }
     const uint32_t ho = fdiv(rem, d.div_wo), wo = rem - ho * d.Wo;
     a_bh[i] = (int)ho * d.stride - d.pad_t;
     a_bw[i] = (int)wo * d.stride - d.pad_l;
@@ -67,7 +78,7 @@ __global__ __launch_bounds__(kThreads, (BM * BN >= 128 * 128) ? IGEMM_FWD_MINW :
     uint32_t msk = 0;
     if (FASTA && fast && a_ok[i]) {
       for (int t = 0; t < d.ntaps; ++t) {
-        const int nh = a_bh[i] + d.tap_dh[t], nw = a_bw[i] + d.tap_dw[t];
+        const int nh = a_bh[i] + (tt.dhw[t] >> 16), nw = a_bw[i] + (int)(short)(tt.dhw[t] & 0xffff);
         if (nh >= 0 && nh < d.H && nw >= 0 && nw < d.W) msk |= 1u << t;
       }
     }
@@ -81,24 +92,31 @@ __global__ __launch_bounds__(kThreads, (BM * BN >= 128 * 128) ? IGEMM_FWD_MINW :
     b_nq[i] = u % (BN / 4);
   }
 
-  float4 ra0[AU], rb0[BU];
-  auto load_chunk = [&](int c, float4 (&ra)[AU], float4 (&rb)[BU]) {
+  float4 ra[D][AU], rb[D][BU];     // (indexed by unrolled constants only)
+  // the address of the zero buffer, taken once: left to itself the compiler fetches it again from the global offset table for every chunk,
+  // a scalar load and a full wait in front of each chunk's loads
+  typedef const float __attribute__((address_space(1)))* global_cptr;     // (kept a global-memory pointer: a flat load would count on both wait counters)
+  global_cptr zero16_g = (global_cptr)g_zero16;
+  asm volatile("" : "+s"(zero16_g));
+  const float* zero16 = (const float*)zero16_g;
+  // chunk c = tap t of channel slab `slab` on the fast path (c = slab * ntaps + t); t_coff / t_kbase = the tap's table entries
+  auto load_chunk = [&](int c, int t, int slab, int t_coff, int t_kbase, float4 (&ra)[AU], float4 (&rb)[BU]) {
     // K order on the fast path: channel slab outer, taps inner -> the taps of one 16-channel slab re-read the same cache lines
     int k0 = c * BK;     // row of the [K x Cout] filter matrix this chunk starts at
     if (VECA) {  // Cin % BK == 0: the whole chunk lies inside one filter tap (wave-uniform tap, ci0)
       if (fast) {
-        const int t = c % d.ntaps, ci0 = (c / d.ntaps) * BK;
-        k0 = (int)d.tap_w[t] * d.Cin + ci0;
-        const long coff = ((long)d.tap_dh[t] * d.W + d.tap_dw[t]) * d.Cin + ci0;
+        const int ci0 = slab * BK;
+        k0 = t_kbase + ci0;
+        const long coff = (long)t_coff + ci0;
 #pragma unroll
-        for (int i = 0; i < AU; ++i) ra[i] = ld4(((a_mask[i] >> t) & 1u) ? a_ptr[i] + coff : g_zero16);
+        for (int i = 0; i < AU; ++i) ra[i] = ld4(((a_mask[i] >> t) & 1u) ? a_ptr[i] + coff : zero16);
       } else {
         const int rs = k0 / d.Cin, ci0 = k0 - rs * d.Cin;
         const int r = rs / d.KW, s = rs - r * d.KW;
 #pragma unroll
         for (int i = 0; i < AU; ++i) {
           long off = a_ok[i] ? gather_off(d, a_img[i], a_bh[i], a_bw[i], r, s, ci0 + a_kq[i] * 4) : -1;
-          ra[i] = ld4(off >= 0 ? x + off : g_zero16);
+          ra[i] = ld4(off >= 0 ? x + off : zero16);
         }
       }
     } else {
@@ -124,7 +142,7 @@ __global__ __launch_bounds__(kThreads, (BM * BN >= 128 * 128) ? IGEMM_FWD_MINW :
       const int k = k0 + b_kr[i], n = n0 + b_nq[i] * 4;
       const bool inb = (tid + i * kThreads < B_UNITS) && k < d.KH * d.KW * d.Cin;
       if (VECB) {
-        rb[i] = ld4((inb && n < d.Cout) ? w + (long)k * d.Cout + n : g_zero16);
+        rb[i] = ld4((inb && n < d.Cout) ? w + (long)k * d.Cout + n : zero16);
       } else {
         float v[4];
 #pragma unroll
@@ -136,14 +154,14 @@ __global__ __launch_bounds__(kThreads, (BM * BN >= 128 * 128) ? IGEMM_FWD_MINW :
   auto store_chunk = [&](int buf, const float4 (&ra)[AU], const float4 (&rb)[BU]) {
 #pragma unroll
     for (int i = 0; i < AU; ++i) {
-      if (tid + i * kThreads < A_UNITS) {
+      if (A_UNITS % kThreads == 0 || tid + i * kThreads < A_UNITS) {   // (a whole number of rounds: no branch, so the wait for the loads stands on every path)
         float* p = &As[buf][a_row[i] * LDA + a_kq[i] * 4];
         p[0] = ra[i].x; p[1] = ra[i].y; p[2] = ra[i].z; p[3] = ra[i].w;
       }
     }
 #pragma unroll
     for (int i = 0; i < BU; ++i) {
-      if (tid + i * kThreads < B_UNITS)
+      if (B_UNITS % kThreads == 0 || tid + i * kThreads < B_UNITS)
         *reinterpret_cast<float4*>(&Bs[buf][b_kr[i] * BN + b_nq[i] * 4]) = rb[i];
     }
   };
@@ -181,16 +199,69 @@ __global__ __launch_bounds__(kThreads, (BM * BN >= 128 * 128) ? IGEMM_FWD_MINW :
           acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[ks][mi], bf[ks][ni], acc[mi][ni], 0, 0, 0);
   };
 
-  load_chunk(c_begin, ra0, rb0);
-  store_chunk(0, ra0, rb0);
-  __syncthreads();
-  for (int c = c_begin; c < nchunks; ++c) {
-    const int buf = (c - c_begin) & 1;
-    if (c + 1 < nchunks) load_chunk(c + 1, ra0, rb0);
-    mma_chunk(buf);
-    if (c + 1 < nchunks) store_chunk(buf ^ 1, ra0, rb0);
+  // the taps some row of this tile reads inside the image; a chunk of any other tap multiplies zeros and is not walked
+  uint32_t tmask = 0xffffffffu;
+  if (SKIPPABLE && FASTA && skip) {
+    uint32_t wmask = 0;
+    for (int t = 0; t < d.ntaps; ++t) {
+      bool any = false;
+#pragma unroll
+      for (int i = 0; i < AU; ++i) any |= ((a_mask[i] >> t) & 1u) != 0;
+      if (__ballot(any) != 0) wmask |= 1u << t;
+    }
+    uint32_t* wm4 = reinterpret_cast<uint32_t*>(&As[0][0]);
+    if (lane == 0) wm4[wid] = wmask;
+    __syncthreads();
+    tmask = __builtin_amdgcn_readfirstlane(wm4[0] | wm4[1] | wm4[2] | wm4[3]);
     __syncthreads();
   }
+  const bool walk = SKIPPABLE && FASTA && skip;
+  // live chunks of [c_begin, nchunks): the pipeline below runs over this compacted list, split ranges keep the original numbering
+  int nlive = nchunks - c_begin;
+  // load cursor: the next chunk to fetch, its tap and channel slab, and the tap's table entries.  The entries come from 32-bit tables (a byte
+  // of the descriptor indexed by the tap is a vector load, and waiting for it would drain every prefetch in flight), and the cursor moves
+  // right after a chunk's loads are issued, so these scalar loads are back long before the next chunk needs them.
+  int lc = c_begin, lt = 0, ls = 0, lcoff = 0, lkb = 0;
+  if (VECA && fast) { ls = c_begin / d.ntaps; lt = c_begin - ls * d.ntaps; }
+  if (walk) {
+    const int pc = __popc(tmask), se = nchunks / d.ntaps, te = nchunks - se * d.ntaps;
+    nlive = (se * pc + __popc(tmask & ((1u << te) - 1u))) - (ls * pc + __popc(tmask & ((1u << lt) - 1u)));
+  }
+  auto next_chunk = [&]() {
+    do {
+      ++lc;
+      if (++lt == d.ntaps) { lt = 0; ++ls; }
+    } while (walk && ((tmask >> lt) & 1u) == 0);
+    if (VECA && fast) { lcoff = tt.coff[lt]; lkb = tt.kbase[lt]; }
+  };
+  // Every step issues its loads unconditionally (past the end it fetches the last chunk once more, into a register set nobody stores), and
+  // the loop leaves through its one exit: the count of loads in flight is then the same on every path, and the wait before a
+  // registers -> LDS store lets the D - 1 younger chunks stay in flight.
+  if (nlive > 0) {
+    if (walk && ((tmask >> lt) & 1u) == 0) next_chunk();
+    else if (VECA && fast) { lcoff = tt.coff[lt]; lkb = tt.kbase[lt]; }
+    // (the cursor stands at live chunk min(j + D, nlive - 1) when step j issues its loads)
+#pragma unroll
+    for (int r = 0; r < D; ++r) {
+      load_chunk(lc, lt, ls, lcoff, lkb, ra[r], rb[r]);
+      if (r + 1 < nlive) next_chunk();
+    }
+    store_chunk(0, ra[0], rb[0]);
+    __syncthreads();
+    for (int j0 = 0;; j0 += D) {
+#pragma unroll
+      for (int r = 0; r < D; ++r) {
+        const int j = j0 + r;
+        load_chunk(lc, lt, ls, lcoff, lkb, ra[r], rb[r]);
+        if (j + D + 1 < nlive) next_chunk();
+        mma_chunk(j & 1);
+        if (j + 1 >= nlive) goto k_done;
+        store_chunk((j + 1) & 1, ra[(r + 1) % D], rb[(r + 1) % D]);
+        __syncthreads();
+      }
+    }
+  }
+k_done:
 
   if (part != nullptr) {   // split-K partial: raw accumulators, bias/activation applied by splitk_epilogue_kernel
     float* o = part + (size_t)blockIdx.y * d.M * d.Cout;
@@ -226,8 +297,12 @@ __global__ __launch_bounds__(kThreads, (BM * BN >= 128 * 128) ? IGEMM_FWD_MINW :
         const int m = m0 + wm * TM + mi * 32 + (e & 3) + 8 * (e >> 2) + 4 * lh;
         if (m < d.M && n < d.Cout) {
           long row = m;
-          if (!dense_out) {   // phased backward-data: the M space is one parity class of the output map
-            const uint32_t n_img = fdiv((uint32_t)m, d.div_howo), rem = (uint32_t)m - n_img * HoWo;
+          if (!dense_out || (SKIPPABLE && posmajor)) {   // phased backward-data: the M space is one parity class of the output map
+            uint32_t n_img = fdiv((uint32_t)m, d.div_howo), rem = (uint32_t)m - n_img * HoWo;
+            if (SKIPPABLE && posmajor) {
+              rem = fdiv((uint32_t)m, div_n);
+              n_img = (uint32_t)m - rem * d.N;
+            }
             const uint32_t ho = fdiv(rem, d.div_wo), wo = rem - ho * d.Wo;
             row = ((long)n_img * d.OH + d.out_h0 + (long)ho * d.out_sh) * d.OW + d.out_w0 + (long)wo * d.out_sw;
           }
@@ -286,13 +361,18 @@ __global__ void splitk_epilogue_kernel(const float* __restrict__ part, const flo
 // The same second pass for a call whose M space is a strided subset of the output map (one parity class of a stride-2 backward-data):
 // partials are dense in the class-local pixel index m, the result goes to y[n, out_h0 + ho*out_sh, out_w0 + wo*out_sw, :].
 __global__ void splitk_epilogue_strided_kernel(const float* __restrict__ part, const float* __restrict__ bias, float* __restrict__ y,
-                                               int S, size_t MN, int act, const float* __restrict__ gate, int gate_act, const IgemmDesc d) {
+                                               int S, size_t MN, int act, const float* __restrict__ gate, int gate_act, const IgemmDesc d,
+                                               const bool posmajor, const FastDiv div_n) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= MN) return;
   float s = 0.f;
   for (int z = 0; z < S; ++z) s += part[(size_t)z * MN + i];   // fixed order
   const uint32_t m = (uint32_t)(i / d.Cout), n = (uint32_t)(i - (size_t)m * d.Cout);
-  const uint32_t n_img = fdiv(m, d.div_howo), rem = m - n_img * (uint32_t)(d.Ho * d.Wo);
+  uint32_t n_img = fdiv(m, d.div_howo), rem = m - n_img * (uint32_t)(d.Ho * d.Wo);
+  if (posmajor) {   // the partials keep the first pass's row order: row m = (position m / N, image m % N)
+    rem = fdiv(m, div_n);
+    n_img = m - rem * (uint32_t)d.N;
+  }
   const uint32_t ho = fdiv(rem, d.div_wo), wo = rem - ho * d.Wo;
   const size_t o = ((((size_t)n_img * d.OH + d.out_h0 + (size_t)ho * d.out_sh) * d.OW + d.out_w0 + (size_t)wo * d.out_sw)) * d.Cout + n;
   if (bias != nullptr) s += bias[n];
@@ -484,21 +564,65 @@ SplitPlan plan_splitk(long M, int K, int Cout, int bm, int bn) {
 }
 
 void launch_splitk_epilogue(const float* part, const float* bias, float* y, int splits, const IgemmDesc& d, const float* gate, int gate_act,
-                            hipStream_t st) {
+                            hipStream_t st, bool posmajor) {
   const size_t mn = (size_t)d.M * d.Cout;
-  if (d.out_sh == 1 && d.out_sw == 1 && d.OH == d.Ho && d.OW == d.Wo)
+  if (!posmajor && d.out_sh == 1 && d.out_sw == 1 && d.OH == d.Ho && d.OW == d.Wo)
     hipLaunchKernelGGL(splitk_epilogue_kernel, dim3((unsigned)((mn + 255) / 256)), dim3(256), 0, st, part, bias, y, splits, mn, d.Cout, d.act,
                        gate, gate_act);
   else
     hipLaunchKernelGGL(splitk_epilogue_strided_kernel, dim3((unsigned)((mn + 255) / 256)), dim3(256), 0, st, part, bias, y, splits, mn, d.act,
-                       gate, gate_act, d);
+                       gate, gate_act, d, posmajor, make_fastdiv((uint32_t)d.N));
+}
+
+// Small maps (at most 16 output positions, more than one tap): a tile of the small-tile kernels walks only the chunks whose tap is inside the
+// image for one of its rows; with at least a tile of images the rows run position-major, so a tile's rows share their padding taps.
+// Geometry only, never data.  (variant bit 0)
+struct SmallMapMode { bool skip, posmajor; };
+static SmallMapMode small_map_mode(const IgemmDesc& d, int bm, int bn, int variant) {
+  const bool small_tile = (bm == 64 && bn == 64) || (bm == 32 && bn == 128);
+  const bool skip = (variant & 1) != 0 && small_tile && (d.Cin % BK) == 0 && d.ntaps > 1 && d.Ho * d.Wo <= 16;
+  return SmallMapMode{skip, skip && d.N >= bm};
+}
+
+int igemm_default_variant() {
+  static const int variant = getenv("LADDER_IGEMM_VARIANT") != nullptr ? atoi(getenv("LADDER_IGEMM_VARIANT")) & 7 : IGEMM_VARIANT_DEFAULT;
+  return variant;
+}
+
+struct FwdArgs {
+  const float *x, *w, *bias;
+  float* y;
+  const IgemmDesc& d;
+  int tiles_n;
+  bool fast;
+  float* part;
+  int cps;
+  const float* gate;
+  int gate_act;
+  float* stats_part;
+  SmallMapMode mode;
+};
+
+template <int BM, int BN, int WM, int WN, int D, bool SK>
+static void launch_fwd_vec(dim3 grid, hipStream_t st, const FwdArgs& a) {
+  const bool veca = (a.d.Cin % BK) == 0, vecb = (a.d.Cout % 4) == 0;
+  const FastDiv div_n = make_fastdiv((uint32_t)a.d.N);
+  const TapTab tt = make_taptab(a.d);
+  const dim3 block(kThreads);
+#define LADDER_FWD_GO(VA, VB)                                                                                                                  \
+  hipLaunchKernelGGL((igemm_fwd_kernel<BM, BN, WM, WN, VA, VB, D, SK>), grid, block, 0, st, a.x, a.w, a.bias, a.y, a.d, a.tiles_n, a.fast, a.part, \
+                     a.cps, a.gate, a.gate_act, a.stats_part, a.mode.skip, a.mode.posmajor, div_n, tt)
+  if (veca && vecb) LADDER_FWD_GO(true, true);
+  else if (veca) LADDER_FWD_GO(true, false);
+  else if (vecb) LADDER_FWD_GO(false, true);
+  else LADDER_FWD_GO(false, false);
+#undef LADDER_FWD_GO
 }
 
 template <int BM, int BN, int WM, int WN>
 static int launch_fwd(const float* x, const float* w, const float* bias, float* y, const IgemmDesc& d, void* ws, size_t ws_bytes,
-               hipStream_t st, const float* gate = nullptr, int gate_act = 0, float* stats_part = nullptr) {
+               hipStream_t st, const float* gate = nullptr, int gate_act = 0, float* stats_part = nullptr, int variant = 0) {
   const int tiles_m = (d.M + BM - 1) / BM, tiles_n = (d.Cout + BN - 1) / BN;
-  const bool veca = (d.Cin % BK) == 0, vecb = (d.Cout % 4) == 0;
   const bool fast = d.ntaps > 0;
   const bool dense_out = d.out_sh == 1 && d.out_sw == 1 && d.OH == d.Ho && d.OW == d.Wo;
   // (round 4: also the parity classes of a stride-2 backward-data -- a quarter of the pixels, 1 ... 4 of the 9 taps: 32 tiles on 256 CUs
@@ -509,12 +633,21 @@ static int launch_fwd(const float* x, const float* w, const float* bias, float* 
   if (sp.splits > 1 && (ws == nullptr || ws_bytes < need)) sp = SplitPlan{1, (d.K + BK - 1) / BK};
   float* part = sp.splits > 1 ? (float*)ws : nullptr;
   if (stats_part != nullptr && (part != nullptr || !dense_out || BM != 128 || BN != 128)) return LADDER_E_SHAPE;   // statistics come from the single-pass 128x128 epilogue
-  dim3 grid(tiles_m * tiles_n, sp.splits), block(kThreads);
-  if (veca && vecb) hipLaunchKernelGGL((igemm_fwd_kernel<BM, BN, WM, WN, true, true>), grid, block, 0, st, x, w, bias, y, d, tiles_n, fast, part, sp.cps, part ? nullptr : gate, gate_act, stats_part);
-  else if (veca) hipLaunchKernelGGL((igemm_fwd_kernel<BM, BN, WM, WN, true, false>), grid, block, 0, st, x, w, bias, y, d, tiles_n, fast, part, sp.cps, part ? nullptr : gate, gate_act, stats_part);
-  else if (vecb) hipLaunchKernelGGL((igemm_fwd_kernel<BM, BN, WM, WN, false, true>), grid, block, 0, st, x, w, bias, y, d, tiles_n, fast, part, sp.cps, part ? nullptr : gate, gate_act, stats_part);
-  else hipLaunchKernelGGL((igemm_fwd_kernel<BM, BN, WM, WN, false, false>), grid, block, 0, st, x, w, bias, y, d, tiles_n, fast, part, sp.cps, part ? nullptr : gate, gate_act, stats_part);
-  if (part != nullptr) launch_splitk_epilogue(part, bias, y, sp.splits, d, gate, gate_act, st);
+  const dim3 grid(tiles_m * tiles_n, sp.splits);
+  const FwdArgs a{x, w, bias, y, d, tiles_n, fast, part, sp.cps, part ? nullptr : gate, gate_act, stats_part, small_map_mode(d, BM, BN, variant)};
+  // the prefetch depth (variant bits 1-2) exists for the small tiles; the large ones stay one chunk ahead
+  constexpr bool SMALL = (BM == 64 && BN == 64) || (BM == 32 && BN == 128);
+  if constexpr (SMALL) {
+    switch ((variant >> 1) & 3) {
+      case 0: launch_fwd_vec<BM, BN, WM, WN, 1, true>(grid, st, a); break;
+      case 1: launch_fwd_vec<BM, BN, WM, WN, 2, true>(grid, st, a); break;
+      case 2: launch_fwd_vec<BM, BN, WM, WN, 3, true>(grid, st, a); break;
+      default: launch_fwd_vec<BM, BN, WM, WN, 4, true>(grid, st, a); break;
+    }
+  } else {
+    launch_fwd_vec<BM, BN, WM, WN, 1, false>(grid, st, a);
+  }
+  if (part != nullptr) launch_splitk_epilogue(part, bias, y, sp.splits, d, gate, gate_act, st, a.mode.posmajor);
   LADDER_CHECK_LAUNCH();
   return LADDER_OK;
 }
@@ -532,17 +665,22 @@ int select_fwd_tile(long M, int Cout) {
 }
 
 int dispatch_fwd(const float* x, const float* w, const float* bias, float* y, const IgemmDesc& d, void* ws, size_t ws_bytes,
-                 hipStream_t st, const float* gate, int gate_act) {
+                 hipStream_t st, const float* gate, int gate_act, int variant) {
   if (d.M <= 0 || d.K <= 0 || d.Cout <= 0) return LADDER_E_SHAPE;
   if (!ladder_aligned16(x) || !ladder_aligned16(w) || !ladder_aligned16(y)) return LADDER_E_ALIGN;
   if (gate == nullptr && halo_eligible(d)) return launch_halo(x, w, bias, y, d, st);
   switch (select_fwd_tile(d.M, d.Cout)) {
-    case 128128: return launch_fwd<128, 128, 2, 2>(x, w, bias, y, d, ws, ws_bytes, st, gate, gate_act);
-    case 64064: return launch_fwd<64, 64, 2, 2>(x, w, bias, y, d, ws, ws_bytes, st, gate, gate_act);
-    case 32128: return launch_fwd<32, 128, 1, 4>(x, w, bias, y, d, ws, ws_bytes, st, gate, gate_act);
-    case 128064: return launch_fwd<128, 64, 4, 1>(x, w, bias, y, d, ws, ws_bytes, st, gate, gate_act);
-    default: return launch_fwd<128, 32, 4, 1>(x, w, bias, y, d, ws, ws_bytes, st, gate, gate_act);
+    case 128128: return launch_fwd<128, 128, 2, 2>(x, w, bias, y, d, ws, ws_bytes, st, gate, gate_act, nullptr, variant);
+    case 64064: return launch_fwd<64, 64, 2, 2>(x, w, bias, y, d, ws, ws_bytes, st, gate, gate_act, nullptr, variant);
+    case 32128: return launch_fwd<32, 128, 1, 4>(x, w, bias, y, d, ws, ws_bytes, st, gate, gate_act, nullptr, variant);
+    case 128064: return launch_fwd<128, 64, 4, 1>(x, w, bias, y, d, ws, ws_bytes, st, gate, gate_act, nullptr, variant);
+    default: return launch_fwd<128, 32, 4, 1>(x, w, bias, y, d, ws, ws_bytes, st, gate, gate_act, nullptr, variant);
   }
+}
+
+int dispatch_fwd(const float* x, const float* w, const float* bias, float* y, const IgemmDesc& d, void* ws, size_t ws_bytes,
+                 hipStream_t st, const float* gate, int gate_act) {
+  return dispatch_fwd(x, w, bias, y, d, ws, ws_bytes, st, gate, gate_act, igemm_default_variant());
 }
 
 static size_t fwd_ws_bytes(long M, int K, int Cout) {
@@ -574,9 +712,13 @@ int ladder_igemm_fwd_tile(long M, int Cin, int Cout) {
   return ((Cin % BK) == 0 && (Cout % 4) == 0) ? t : -t;   // (the 3x3 halo kernel is reported by ladder_conv3x3_uses_halo)
 }
 
-int ladder_conv2d_fwd(const float* x, const float* w, const float* bias, float* y, int N, int H, int W, int Cin,
-                      int Ho, int Wo, int Cout, int KH, int KW, int stride, int pad_t, int pad_l, int act,
-                      void* ws, size_t ws_bytes, ladder_stream_t stream) {
+// The *_variant entry points run one form of igemm_fwd_kernel (bit 0: position-major rows and padding-tap skipping on small maps; bits 1-2:
+// prefetch depth - 1); every variant gives the same bits, variant 0 is the first form of the kernel.  The plain entry points run
+// IGEMM_VARIANT_DEFAULT, or LADDER_IGEMM_VARIANT (read once) for whole-process comparisons.
+int ladder_conv2d_fwd_variant(const float* x, const float* w, const float* bias, float* y, int N, int H, int W, int Cin,
+                              int Ho, int Wo, int Cout, int KH, int KW, int stride, int pad_t, int pad_l, int act,
+                              void* ws, size_t ws_bytes, int variant, ladder_stream_t stream) {
+  if (variant < 0 || variant > 7) return LADDER_E_SHAPE;
   if (!conv_shape_ok(N, H, W, Cin, Ho, Wo, KH, KW, stride)) return LADDER_E_SHAPE;
   if (smallcout_eligible(Cin, Cout, KH, KW, stride, (long)N * Ho * Wo) && ladder_aligned16(x)) {
     const int M = N * Ho * Wo;
@@ -589,7 +731,13 @@ int ladder_conv2d_fwd(const float* x, const float* w, const float* bias, float* 
     LADDER_CHECK_LAUNCH();
     return LADDER_OK;
   }
-  return dispatch_fwd(x, w, bias, y, conv_desc(N, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, 1, pad_t, pad_l, act), ws, ws_bytes, stream);
+  return dispatch_fwd(x, w, bias, y, conv_desc(N, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, 1, pad_t, pad_l, act), ws, ws_bytes, stream, nullptr, 0, variant);
+}
+
+int ladder_conv2d_fwd(const float* x, const float* w, const float* bias, float* y, int N, int H, int W, int Cin,
+                      int Ho, int Wo, int Cout, int KH, int KW, int stride, int pad_t, int pad_l, int act,
+                      void* ws, size_t ws_bytes, ladder_stream_t stream) {
+  return ladder_conv2d_fwd_variant(x, w, bias, y, N, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, pad_t, pad_l, act, ws, ws_bytes, igemm_default_variant(), stream);
 }
 
 size_t ladder_igemm_fwd_workspace_bytes(long M, int K, int Cout) { return fwd_ws_bytes(M, K, Cout); }
@@ -646,32 +794,99 @@ int ladder_filter_flip_transpose(const float* w, float* wT, int KH, int KW, int 
   return LADDER_OK;
 }
 
-int ladder_conv2d_bwd_data(const float* dy, const float* wT, float* dx, int N, int H, int W, int Cin, int Ho, int Wo,
-                           int Cout, int KH, int KW, int stride, int pad_t, int pad_l, const float* gate_y, int gate_act,
-                           void* ws, size_t ws_bytes, ladder_stream_t stream) {
+int ladder_conv2d_bwd_data_variant(const float* dy, const float* wT, float* dx, int N, int H, int W, int Cin, int Ho, int Wo,
+                                   int Cout, int KH, int KW, int stride, int pad_t, int pad_l, const float* gate_y, int gate_act,
+                                   void* ws, size_t ws_bytes, int variant, ladder_stream_t stream) {
+  if (variant < 0 || variant > 7) return LADDER_E_SHAPE;
   if (!conv_shape_ok(N, H, W, Cin, Ho, Wo, KH, KW, stride)) return LADDER_E_SHAPE;
   const IgemmDesc d = bwd_data_desc(N, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, pad_t, pad_l);
   if (stride == 1 && smallcin_eligible(Cout, Cin, KH, KW))             // 1x1 from a 3-channel dy (CelebA output conv), gate fused
     return launch_smallcin(dy, wT, nullptr, dx, gate_y, N, Ho, Wo, Cout, H, W, Cin, KH, 1, 0, 0, gate_y != nullptr ? gate_act : 0, stream);
-  if (stride == 1) return dispatch_fwd(dy, wT, nullptr, dx, d, ws, ws_bytes, stream, gate_y, gate_act);
+  if (stride == 1) return dispatch_fwd(dy, wT, nullptr, dx, d, ws, ws_bytes, stream, gate_y, gate_act, variant);
   if (stride == 2 && (Cout % BK) == 0 && KH * KW <= 28) {
     IgemmDesc cls[4];
     parity_classes(d, cls);
     for (const IgemmDesc& c : cls) {
       if (c.M == 0) continue;
-      if (c.ntaps == 0) return dispatch_fwd(dy, wT, nullptr, dx, d, ws, ws_bytes, stream, gate_y, gate_act);   // degenerate: legacy path writes the zeros
-      const int rc = dispatch_fwd(dy, wT, nullptr, dx, c, ws, ws_bytes, stream, gate_y, gate_act);   // (the classes run one after another: one workspace)
+      if (c.ntaps == 0) return dispatch_fwd(dy, wT, nullptr, dx, d, ws, ws_bytes, stream, gate_y, gate_act, variant);   // degenerate: legacy path writes the zeros
+      const int rc = dispatch_fwd(dy, wT, nullptr, dx, c, ws, ws_bytes, stream, gate_y, gate_act, variant);   // (the classes run one after another: one workspace)
       if (rc != LADDER_OK) return rc;
     }
     return LADDER_OK;
   }
-  return dispatch_fwd(dy, wT, nullptr, dx, d, ws, ws_bytes, stream, gate_y, gate_act);   // generic strided gather (ups > 1)
+  return dispatch_fwd(dy, wT, nullptr, dx, d, ws, ws_bytes, stream, gate_y, gate_act, variant);   // generic strided gather (ups > 1)
+}
+
+int ladder_conv2d_bwd_data(const float* dy, const float* wT, float* dx, int N, int H, int W, int Cin, int Ho, int Wo,
+                           int Cout, int KH, int KW, int stride, int pad_t, int pad_l, const float* gate_y, int gate_act,
+                           void* ws, size_t ws_bytes, ladder_stream_t stream) {
+  return ladder_conv2d_bwd_data_variant(dy, wT, dx, N, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, pad_t, pad_l, gate_y, gate_act, ws, ws_bytes,
+                                        igemm_default_variant(), stream);
+}
+
+int ladder_dense_fwd_variant(const float* x, const float* w, const float* bias, float* y, int M, int K, int N, int act,
+                             void* ws, size_t ws_bytes, int variant, ladder_stream_t stream) {
+  if (variant < 0 || variant > 7) return LADDER_E_SHAPE;
+  if (dense_f32_big_ok(M, K, N)) return dense_f32_big_launch(x, w, bias, y, nullptr, 0, M, K, N, act, stream);     // (csrc/densef32.hip)
+  return dispatch_fwd(x, w, bias, y, dense_desc(M, K, N, act), ws, ws_bytes, stream, nullptr, 0, variant);
 }
 
 int ladder_dense_fwd(const float* x, const float* w, const float* bias, float* y, int M, int K, int N, int act,
                      void* ws, size_t ws_bytes, ladder_stream_t stream) {
-  if (dense_f32_big_ok(M, K, N)) return dense_f32_big_launch(x, w, bias, y, nullptr, 0, M, K, N, act, stream);     // (csrc/densef32.hip)
-  return dispatch_fwd(x, w, bias, y, dense_desc(M, K, N, act), ws, ws_bytes, stream);
+  return ladder_dense_fwd_variant(x, w, bias, y, M, K, N, act, ws, ws_bytes, igemm_default_variant(), stream);
+}
+
+// Chunks (16-deep K steps of one output tile) that the gather kernel issues for a convolution forward (bwd_data == 0) or its backward-data
+// (bwd_data != 0, same geometry arguments as ladder_conv2d_bwd_data), summed over all tiles and launches, under `variant` (-1: the default).
+// variant 0 gives the chunks of the full tap walk.  -1 when the call does not run igemm_fwd_kernel.  Pure host arithmetic.
+static long desc_live_chunks(const IgemmDesc& d, int variant) {
+  const int t = select_fwd_tile(d.M, d.Cout), bm = t / 1000, bn = t % 1000;
+  const long tiles_m = (d.M + bm - 1) / bm, tiles_n = (d.Cout + bn - 1) / bn;
+  const int nchunks = (d.K + BK - 1) / BK;
+  const SmallMapMode mode = small_map_mode(d, bm, bn, variant);
+  if (!mode.skip) return tiles_m * tiles_n * nchunks;
+  const int howo = d.Ho * d.Wo, slabs = d.Cin / BK;
+  long live = 0;
+  for (long tm = 0; tm < tiles_m; ++tm) {
+    uint32_t mask = 0;
+    for (long m = tm * bm; m < (tm + 1) * bm && m < d.M; ++m) {
+      const int rem = (int)(mode.posmajor ? m / d.N : m % howo);
+      const int bh = (rem / d.Wo) * d.stride - d.pad_t, bw = (rem % d.Wo) * d.stride - d.pad_l;
+      for (int tp = 0; tp < d.ntaps; ++tp) {
+        const int nh = bh + d.tap_dh[tp], nw = bw + d.tap_dw[tp];
+        if (nh >= 0 && nh < d.H && nw >= 0 && nw < d.W) mask |= 1u << tp;
+      }
+    }
+    live += (long)__builtin_popcount(mask) * slabs;
+  }
+  return live * tiles_n;
+}
+
+long ladder_igemm_fwd_live_chunks(int N, int H, int W, int Cin, int Ho, int Wo, int Cout, int KH, int KW, int stride, int pad_t, int pad_l,
+                                  int bwd_data, int variant) {
+  if (!conv_shape_ok(N, H, W, Cin, Ho, Wo, KH, KW, stride) || variant > 7) return -1;
+  if (variant < 0) variant = igemm_default_variant();
+  if (bwd_data == 0) {
+    const IgemmDesc d = conv_desc(N, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, 1, pad_t, pad_l, 0);
+    if (smallcout_eligible(Cin, Cout, KH, KW, stride, (long)N * Ho * Wo) || cout1_eligible(Cin, Cout, KH, KW, stride, pad_t, pad_l, H, W, Ho, Wo) ||
+        halo_eligible(d))
+      return -1;
+    return desc_live_chunks(d, variant);
+  }
+  const IgemmDesc d = bwd_data_desc(N, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, pad_t, pad_l);
+  if (stride == 1) return (smallcin_eligible(Cout, Cin, KH, KW) || halo_eligible(d)) ? -1 : desc_live_chunks(d, variant);
+  if (stride == 2 && (Cout % BK) == 0 && KH * KW <= 28) {
+    IgemmDesc cls[4];
+    parity_classes(d, cls);
+    long live = 0;
+    for (const IgemmDesc& c : cls) {
+      if (c.M == 0) continue;
+      if (c.ntaps == 0) return desc_live_chunks(d, variant);
+      live += desc_live_chunks(c, variant);
+    }
+    return live;
+  }
+  return desc_live_chunks(d, variant);
 }
 
 int ladder_dense_fwd_nt(const float* x, const float* wT, const float* bias, float* y, int M, int K, int N, int act, ladder_stream_t stream) {

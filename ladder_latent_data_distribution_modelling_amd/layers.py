@@ -62,6 +62,16 @@ def _timed(kid, flops, name, args, executed=None):
     PROF.add(kid, s, e, flops, executed)
 
 
+def _gather_executed(kid, flops, geo, bwd_data):
+    """The FLOPs a gather-kernel launch issues when its tiles skip the padding taps of a small map (ladder_igemm_fwd_live_chunks over the twelve
+    geometry arguments `geo`), for `_timed`'s `executed`; None when nothing is skipped, another kernel runs the call or no profiler is installed."""
+    if PROF is None or not kid:
+        return None
+    live = L.query("ladder_igemm_fwd_live_chunks", *geo, int(bwd_data), -1)
+    full = L.query("ladder_igemm_fwd_live_chunks", *geo, int(bwd_data), 0)
+    return flops * live / full if 0 < live < full else None
+
+
 class PlanesOnly:
     """Stand-in for an activation that exists ONLY as its fp16 plane images (registered with Ctx.set_planes / set_amax): the batch-norm
     apply of an encoder layer whose consumer is a split gather convolution never writes the fp32 tensor.  Any fp32 use raises."""
@@ -734,7 +744,8 @@ class Conv2D:
 
     def _fwd_gather(self, r, x, y):
         wsp, wsn = self.ctx.ws(r.fwd.ws)
-        _timed(r.fwd.kid, r.flops, r.fwd.fn, (_p(x), *self._wb(), _p(y), *r.geo, L.ACT[self.act], *self._sums(r), wsp, wsn, self.ctx.stream))
+        _timed(r.fwd.kid, r.flops, r.fwd.fn, (_p(x), *self._wb(), _p(y), *r.geo, L.ACT[self.act], *self._sums(r), wsp, wsn, self.ctx.stream),
+               _gather_executed(r.fwd.kid, r.flops, r.geo, False))
 
     def _backward_proj(self, dy, need_dx, wgrad, gate, proj_grad=None):
         """Backward of the project-then-upsample form from the low-resolution x: D [M, 9 cout] = (shift o up)^T dy once (elementwise), then
@@ -969,8 +980,10 @@ class Conv2D:
         if dl.bank is None:
             L.call("ladder_filter_flip_transpose", self._wb()[0], _p(wT), self.k, self.k, self.cin, self.cout, ctx.stream)
         wsp, wsn = ctx.ws(dl.ws)
-        _timed(dl.kid, 2.0 * r.N * r.H * r.W * self.k * self.k * self.cin * self.cout, dl.fn,
-               (_p(dy), _p(wT), _p(dx), *r.geo, _p(x) if gate else None, L.ACT[gate] if gate else 0, wsp, wsn, ctx.stream))
+        flops = 2.0 * r.N * r.H * r.W * self.k * self.k * self.cin * self.cout
+        _timed(dl.kid, flops, dl.fn,
+               (_p(dy), _p(wT), _p(dx), *r.geo, _p(x) if gate else None, L.ACT[gate] if gate else 0, wsp, wsn, ctx.stream),
+               _gather_executed(dl.kid, flops, r.geo, True))
 
 
 # How one block of the CelebA decoder (resize in front -> 3x3 conv -> [instance norm] -> resize behind) runs, forward and backward:
