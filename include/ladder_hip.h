@@ -1042,6 +1042,28 @@ int ladder_emgmm_wide_mstep(const double* stats, const double* moments, int K, i
                             double tol, int max_iter, int it, float* weights, float* means, float* covs, ladder_stream_t stream);
 int ladder_emgmm_wide_prepare(double* state, int K, int R, void* ws, size_t ws_bytes, ladder_stream_t stream);
 
+/* ---------------------------------------------------------------- N23: k-means on a WIDE code, the labels of a cold fit of N22 (csrc/kmeans_wide.hip)
+ * The k-means of N19 -- same algorithm, state and draws layout (ladder_kmeans_draws_doubles does not depend on the width and serves both), order rules,
+ * protocol and status codes, the signatures of the N19 entries -- for the widths of N22: 64 < R <= 256, R % 16 == 0, 1 <= K <= 64, N >= K.  The entry
+ * points of N19 keep refusing R > 64; these refuse R <= 64, so every width has exactly one k-means.
+ *   ladder_kmeans_wide_assign(it): a workgroup per 64 samples walks the columns in panels of 64 (that panel of the centres in LDS), the x.c accumulators
+ *   carried across the panels on v_mfma_f64_16x16x4_f64; argmin after the last panel, lowest index wins.
+ *   ladder_kmeans_wide_update(it): cluster sums over (row split, 64-column group), the splits added grid-wide in split order, then ONE workgroup for
+ *   relocation, the new centres and the convergence test of N19.
+ *   ws >= ladder_kmeans_wide_workspace_bytes(N, K, R), the SAME buffer from seed / set_centres to the last update.
+ * Size queries return 0 for an unsupported shape.  LADDER_E_SHAPE (nothing launched) for R <= 64, R > 256, R % 16 != 0, K < 1, K > 64, N < K, it < 1,
+ * max_iter < 1, a NULL array or a workspace shorter than the query's answer; LADDER_E_ALIGN for double arrays off 8 bytes. */
+size_t ladder_kmeans_wide_state_doubles(int K, int R);
+size_t ladder_kmeans_wide_workspace_bytes(int N, int K, int R);
+int ladder_kmeans_wide_seed(const float* X, int N, int K, int R, const double* draws, double* state, void* ws, size_t ws_bytes,
+                            ladder_stream_t stream);
+int ladder_kmeans_wide_set_centres(const float* X, int N, int K, int R, const double* centres, double* state, void* ws, size_t ws_bytes,
+                                   ladder_stream_t stream);
+int ladder_kmeans_wide_assign(const float* X, int N, int K, int R, int it, const double* state, int* labels, void* ws, size_t ws_bytes,
+                              ladder_stream_t stream);
+int ladder_kmeans_wide_update(const float* X, int N, int K, int R, const int* labels, double* state, double tol, int max_iter, int it, void* ws,
+                              size_t ws_bytes, ladder_stream_t stream);
+
 /* ---------------------------------------------------------------- helpers */
 /* HOST function (no device work): CRC-32C (Castagnoli) of host memory, crc = 0 to start, chainable.  Used by the
  * tf.train.Saver checkpoint-v2 reader/writer (codes/base.py:37-85: saver_ae / saver_prior) for block and tensor checksums. */

@@ -140,6 +140,12 @@ PROTOTYPES = {
     "ladder_kmeans_set_centres": (_i, [_p, _i, _i, _i, _p, _p, _p, _z, _p]),
     "ladder_kmeans_assign": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _z, _p]),
     "ladder_kmeans_update": (_i, [_p, _i, _i, _i, _p, _p, _d, _i, _i, _p, _z, _p]),
+    "ladder_kmeans_wide_state_doubles": (_z, [_i, _i]),
+    "ladder_kmeans_wide_workspace_bytes": (_z, [_i, _i, _i]),
+    "ladder_kmeans_wide_seed": (_i, [_p, _i, _i, _i, _p, _p, _p, _z, _p]),
+    "ladder_kmeans_wide_set_centres": (_i, [_p, _i, _i, _i, _p, _p, _p, _z, _p]),
+    "ladder_kmeans_wide_assign": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _z, _p]),
+    "ladder_kmeans_wide_update": (_i, [_p, _i, _i, _i, _p, _p, _d, _i, _i, _p, _z, _p]),
     "ladder_vbgmm_wide_state_doubles": (_z, [_i, _i]),
     "ladder_vbgmm_wide_stats_doubles": (_z, [_i, _i]),
     "ladder_vbgmm_wide_moments_doubles": (_z, [_i]),

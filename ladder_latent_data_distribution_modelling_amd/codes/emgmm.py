@@ -6,7 +6,8 @@
 leave the GPU (csrc/emgmm.hip: 1 <= R <= 64; csrc/emgmm_wide.hip: 80 <= R <= 256 in steps of 16; both 1 <= K <= 64 -- the family of entry points is
 picked from the samples' width at fit time), on one GPU or with the samples sharded over the data-parallel ranks.  The k-means
 initialisation of a cold fit (codes/mixture_fit.py, shared with codes/vbgmm.py) is sklearn's on the host with kmeans_backend="sklearn" (the
-default) and the same algorithm on the device with kmeans_backend="hip" (codes/kmeans.py: the same labels, tests/test_gpu_kmeans.py); either way a
+default) and the same algorithm on the device with kmeans_backend="hip" or "hip_wide" (codes/kmeans.py picks csrc/kmeans.hip or
+csrc/kmeans_wide.hip by the width whatever word was used: the same labels, tests/test_gpu_kmeans.py, tests/test_gpu_kmeans_wide.py); either way a
 fit with the same `random_state` reproduces sklearn's to float64 round-off (tests/test_gpu_emgmm.py).
 """
 import numpy as np

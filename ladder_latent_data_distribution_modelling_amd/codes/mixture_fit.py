@@ -1,6 +1,6 @@
 """What the two device mixture fits share (codes/vbgmm.py: variational Bayes on t, codes/emgmm.py: EM on z): the single-process
 communicator, the k-means labels of a cold start (on the gathered samples of rank 0: sklearn.cluster.KMeans on the host, exactly the call
-BaseMixture._initialize_parameters makes, or with kmeans_backend="hip" the same algorithm on the device, codes/kmeans.py), fit_sliced -- the one
+BaseMixture._initialize_parameters makes, or with kmeans_backend="hip" / "hip_wide" the same algorithm on the device, codes/kmeans.py), fit_sliced -- the one
 driver of the EM, the narrow sharded and the wide variational fit -- with the loop that drives its E-step / all-reduce / M-step launches against
 the device-side `done` flag, the choice among `n_init` restarts and sklearn's messages.
 """
@@ -69,7 +69,8 @@ def device_kmeans_labels(X_dev, K, rs):
     return DeviceKMeans(n_clusters=K, n_init=1, random_state=rs, device=X_dev.device).fit(X_dev).labels_dev
 
 
-KMEANS_BACKENDS = ("sklearn", "hip")
+KMEANS_BACKENDS = ("sklearn", "hip", "hip_wide")     # both device words mean DeviceKMeans, which picks its kernel family by the samples' width
+DEVICE_KMEANS_BACKENDS = ("hip", "hip_wide")
 
 
 def check_kmeans_backend(backend):
@@ -79,7 +80,8 @@ def check_kmeans_backend(backend):
 
 
 DEVICE_FIT_MAX_R = 64        # csrc/emgmm.hip, csrc/vbgmm.hip and csrc/kmeans.hip end here; the mixture term and the samplers go on to 256
-DEVICE_FIT_WIDE_MIN_R, DEVICE_FIT_WIDE_MAX_R, DEVICE_FIT_WIDE_STEP = 80, 256, 16      # csrc/emgmm_wide.hip: the widths of csrc/chol_wide.h
+# csrc/emgmm_wide.hip and csrc/kmeans_wide.hip: the widths of csrc/chol_wide.h (the variational fit has no wide family)
+DEVICE_FIT_WIDE_MIN_R, DEVICE_FIT_WIDE_MAX_R, DEVICE_FIT_WIDE_STEP = 80, 256, 16
 DEVICE_FIT_WIDTH_RULE = "1 .. %d dimensions, or %d .. %d in steps of %d" % (DEVICE_FIT_MAX_R, DEVICE_FIT_WIDE_MIN_R, DEVICE_FIT_WIDE_MAX_R,
                                                                             DEVICE_FIT_WIDE_STEP)
 GM_FIT_DEVICE_BACKENDS = ("hip", "hip_wide")     # "hip": the narrow kernels alone; "hip_wide" (prior "GMM"): whichever family takes the width
@@ -94,9 +96,13 @@ def device_fit_width_ok(R, wide):
 
 def check_device_fit_width(config):
     """prior "GMM" fits its mixture on z, so the mixture dimension is code_size.  gm_fit_backend "hip" and kmeans_backend "hip" end at 64 dimensions
-    (beyond: the host fits, which are the defaults, or for the EM fit gm_fit_backend "hip_wide"); "hip_wide" is the device EM fit of prior "GMM" at
-    every width a kernel family takes (DEVICE_FIT_WIDTH_RULE).  Raises ValueError naming the config key that asks for what does not exist.
-    (prior "ours": codes/vbgmm.py checks its own width.)"""
+    (beyond: the host fits, which are the defaults, or "hip_wide"); "hip_wide" is the device EM fit, and as kmeans_backend the device k-means, of prior
+    "GMM" at every width a kernel family takes (DEVICE_FIT_WIDTH_RULE).  For the other priors kmeans_backend "hip_wide" means "hip".  Raises
+    ValueError naming the config key that asks for what does not exist.  (prior "ours": codes/vbgmm.py checks its own width.)"""
+    if (config.get("kmeans_backend") == "hip_wide" and config.get("prior") == "GMM"
+            and not device_fit_width_ok(int(config["code_size"]), wide=True)):
+        raise ValueError('kmeans_backend: "hip_wide" clusters samples of %s, prior "GMM" with code_size = %d needs the host k-means '
+                         '(leave kmeans_backend out or set it to "sklearn")' % (DEVICE_FIT_WIDTH_RULE, int(config["code_size"])))
     if config.get("gm_fit_backend") == "hip_wide":
         if config.get("prior") != "GMM":
             raise ValueError('gm_fit_backend: "hip_wide" is the device EM fit of prior "GMM", not of prior %r (use "hip" or "sklearn" there)'
@@ -108,8 +114,8 @@ def check_device_fit_width(config):
         return
     for key in ("gm_fit_backend", "kmeans_backend"):
         if config.get(key) == "hip":
-            hint = ' or, for a device fit on %d .. %d dimensions in steps of %d, to "hip_wide"' % (
-                DEVICE_FIT_WIDE_MIN_R, DEVICE_FIT_WIDE_MAX_R, DEVICE_FIT_WIDE_STEP) if key == "gm_fit_backend" else ""
+            hint = ' or, for a device %s on %d .. %d dimensions in steps of %d, to "hip_wide"' % (
+                "fit" if key == "gm_fit_backend" else "k-means", DEVICE_FIT_WIDE_MIN_R, DEVICE_FIT_WIDE_MAX_R, DEVICE_FIT_WIDE_STEP)
             raise ValueError('%s: "hip" fits mixtures on at most %d dimensions, prior "GMM" with code_size = %d needs the host fit '
                              '(leave %s out or set it to "sklearn"%s)' % (key, DEVICE_FIT_MAX_R, int(config["code_size"]), key, hint))
 
@@ -138,10 +144,11 @@ def gather_samples(Xd, comm):
 def initial_labels_for(backend, Xd, comm, K, rs, label_broadcast=None):
     """The hard labels of THIS rank's samples for a cold start: k-means needs every sample -- gathered once (rank order), labelled on
     rank 0, this rank keeps its slice.  `label_broadcast`: the hook of replicated fits inside a data-parallel job (rank 0's labels).
-    `backend` = kmeans_backend: "hip" labels the gathered DEVICE tensor (device_kmeans_labels, no copy to the host), "sklearn" a host copy."""
+    `backend` = kmeans_backend: "hip" and "hip_wide" label the gathered DEVICE tensor (device_kmeans_labels, no copy to the host; DeviceKMeans picks
+    the kernel family by the width), "sklearn" a host copy."""
     allx, off = gather_samples(Xd, comm)
     lab = torch.empty(allx.shape[0], dtype=torch.int32, device=Xd.device)
-    if comm.rank == 0 and backend == "hip":
+    if comm.rank == 0 and backend in DEVICE_KMEANS_BACKENDS:
         lab.copy_(device_kmeans_labels(allx, K, rs))
     elif comm.rank == 0:
         lab.copy_(torch.as_tensor(kmeans_labels(allx.cpu().numpy().astype(np.float64), K, rs)))

@@ -38,7 +38,8 @@ class BaseModel:
     # codes/base.py:88-106 -- the producer of (prior_weight, prior_mean, prior_cov).  config["gm_fit_backend"]: "hip" (default)
     # runs the variational fit on the device (codes/vbgmm.py -> csrc/vbgmm.hip, sklearn-parity tested; representation_size up to 64: past 8
     # the float64 MFMA kernels, picked by the fit itself); "sklearn" keeps the reference's host object.  config["kmeans_backend"]: "sklearn" (default) labels a cold device fit with sklearn's k-means on the host, "hip" with
-    # the same algorithm on the device (codes/kmeans.py); it has no effect on the host objects.
+    # the same algorithm on the device (codes/kmeans.py; "hip_wide": also prior "GMM" with code_size 80 .. 256 in steps of 16, csrc/kmeans_wide.hip);
+    # it has no effect on the host objects.
     def define_GM_prior(self):
         self.GM_prior_training = None
         from .mixture_fit import GM_FIT_DEVICE_BACKENDS, check_device_fit_width

@@ -6,7 +6,8 @@ uses (covariance_type='full'; dirichlet_distribution for the per-epoch "fast" fi
 "accurate" fit; warm_start; n_init restarts), but runs the variational loop as one persistent-workgroup HIP launch
 (`ladder_vbgmm_fit`, csrc/vbgmm.hip) on samples that never leave the GPU.  The k-means initialisation of a cold fit is
 sklearn.cluster.KMeans on the host (exactly the call BaseMixture._initialize_parameters makes) with kmeans_backend="sklearn", the
-default, and the same algorithm on the device with kmeans_backend="hip" (codes/kmeans.py: the same labels); either way a fit with the
+default, and the same algorithm on the device with kmeans_backend="hip" (codes/kmeans.py: the same labels; "hip_wide", the word of the wide
+"GMM" prior, is accepted and means the same here, since this fit ends at 64 dimensions); either way a fit with the
 same `random_state` reproduces sklearn's to float64 round-off (tests/test_gpu_vbgmm.py, tests/test_gpu_kmeans.py).
 
 Width of the representation: R <= 8 runs the thread-per-sample kernels (`ladder_vbgmm_fit` below SLICED_FIT_MIN_SAMPLES samples,
