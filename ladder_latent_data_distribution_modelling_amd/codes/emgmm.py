@@ -3,33 +3,18 @@
 `DeviceGaussianMixture` keeps sklearn.mixture.GaussianMixture's constructor arguments and fitted attributes (`weights_`, `means_`,
 `covariances_`, `precisions_cholesky_`, `n_iter_`, `lower_bound_`, `converged_`) for the options the reference uses
 (covariance_type='full', init_params='kmeans'; warm_start; n_init restarts), but runs the EM loop in float64 on samples that never
-leave the GPU (csrc/emgmm.hip: 1 <= R <= 64; csrc/emgmm_wide.hip: 80 <= R <= 256 in steps of 16; both 1 <= K <= 64 -- the family of entry points is
-picked from the samples' width at fit time), on one GPU or with the samples sharded over the data-parallel ranks.  The k-means
+leave the GPU (csrc/emgmm.hip or csrc/emgmm_wide.hip, both 1 <= K <= 64: the family is looked up by the samples' width at fit time, operation "em" of
+mixture_forms.py), on one GPU or with the samples sharded over the data-parallel ranks.  The k-means
 initialisation of a cold fit (codes/mixture_fit.py, shared with codes/vbgmm.py) is sklearn's on the host with kmeans_backend="sklearn" (the
-default) and the same algorithm on the device with kmeans_backend="hip" or "hip_wide" (codes/kmeans.py picks csrc/kmeans.hip or
-csrc/kmeans_wide.hip by the width whatever word was used: the same labels, tests/test_gpu_kmeans.py, tests/test_gpu_kmeans_wide.py); either way a
-fit with the same `random_state` reproduces sklearn's to float64 round-off (tests/test_gpu_emgmm.py).
+default) and the same algorithm on the device with kmeans_backend="hip" or "hip_wide" (codes/kmeans.py, whatever word was used: the same labels,
+tests/test_gpu_kmeans.py, tests/test_gpu_kmeans_wide.py); either way a fit with the same `random_state` reproduces sklearn's to float64 round-off.
 """
 import numpy as np
 import torch
 
 from .. import _lib as L
+from ..mixture_forms import family, sized_workspace
 from . import mixture_fit as MF
-
-
-def family_prefix(R):
-    """The entry points that fit a mixture on R dimensions: "ladder_emgmm_" (R <= 64) or "ladder_emgmm_wide_" (MF.device_fit_width_ok)."""
-    if not MF.device_fit_width_ok(R, wide=True):
-        raise ValueError("the device EM fit takes samples of %s, got %d" % (MF.DEVICE_FIT_WIDTH_RULE, R))
-    return "ladder_emgmm_" if R <= MF.DEVICE_FIT_MAX_R else "ladder_emgmm_wide_"
-
-
-def _factor_workspace(prefix, K, R, device):
-    """-> (tensor, its (pointer, bytes) as the wide M-step / prepare take them); the narrow kernels factor in LDS: (None, ())."""
-    if prefix == "ladder_emgmm_":
-        return None, ()
-    ws = torch.empty(L.query(prefix + "mstep_workspace_bytes", K, R), dtype=torch.uint8, device=device)
-    return ws, (ws.data_ptr(), ws.numel())
 
 
 class DeviceGaussianMixture:
@@ -61,28 +46,28 @@ class DeviceGaussianMixture:
         communicator.  The loop is MF.fit_sliced's: per EM iteration E-step + local statistics, all-reduce of 1 + K (1 + R + R^2) doubles
         (the sum of log_prob_norm travels with the moments: the lower bound is a global mean), M-step + convergence test."""
         K, R = self.n_components, int(np.shape(X_local)[1])
-        prefix = family_prefix(R)
-        mws, m_mid = _factor_workspace(prefix, K, R, self.device)              # (alive until every launch of the fit is enqueued)
+        form = family("em", K, R)
+        mws, m_mid = sized_workspace(form.factor_workspace_bytes, self.device, K, R)       # (alive until every launch of the fit is enqueued)
 
         def moments(Xd, comm, f64, st, check):
             Nl, R = Xd.shape
-            mom = f64(L.query(prefix + "shift_doubles", R))                    # [ sum_n x_n | N ]: the shift vector and the global count
-            L.call(prefix + "shift", Xd.data_ptr(), Nl, R, mom.data_ptr(), st)
+            mom = f64(L.query(form.shift_doubles, R))                          # [ sum_n x_n | N ]: the shift vector and the global count
+            L.call(form.shift, Xd.data_ptr(), Nl, R, mom.data_ptr(), st)
             comm.allreduce_(mom)
             check(int(mom[-1].item()))
             self.converged_ = False                                            # (sklearn sets it before the first restart: a failed fit leaves it)
             return mom
 
-        fam = MF.Family(prefix, moments, prefix + "state_doubles", lambda mom: (mom.data_ptr(),), m_mid, "EM mixture fit")
+        fam = MF.Family(form, moments, lambda mom: (mom.data_ptr(),), m_mid, "EM mixture fit")
         MF.keep_best(self, MF.fit_sliced(self, X_local, comm, check_every, fam))
         self._R = self.means_dev.shape[1]
         return self
 
     def _prepare_state(self, state, R):
         """precisions_cholesky_ / log-determinants for the covariances already in `state`; raises sklearn's ValueError on an ill-defined one."""
-        prefix = family_prefix(R)
-        ws, mid = _factor_workspace(prefix, self.n_components, R, self.device)
-        L.call(prefix + "prepare", state.data_ptr(), self.n_components, R, *mid, torch.cuda.current_stream(self.device).cuda_stream)
+        form = family("em", self.n_components, R)
+        ws, mid = sized_workspace(form.factor_workspace_bytes, self.device, self.n_components, R)
+        L.call(form.prepare, state.data_ptr(), self.n_components, R, *mid, torch.cuda.current_stream(self.device).cuda_stream)
         MF.read_tail(state)                                                    # (synchronises: `ws` outlives the kernels)
 
     # float64 views of the fitted parameters, as sklearn exposes them (layout: csrc/em_state.h)

@@ -9,6 +9,7 @@ the notebook's `opt_interpolation` (cell 19).  The mixture term and its gradient
 of numbers and stays on the host.  `decode_path` maps the optimised path to images (t -> inner decoder -> z -> decoder), as
 demo/demo_tools.py:163-186 does through `sess.run`.
 """
+import functools
 import math
 
 import numpy as np
@@ -16,10 +17,11 @@ import torch
 
 from .. import _lib as L
 from ..mixture import DeviceMixture
+from ..mixture_forms import SLP_DENSE, family
 
 MAX_STEP = 64                   # ladder_slp_optimise: 1 <= n_step <= 64
 MAX_ITER_PER_LAUNCH = 4096      # ... and at most 4096 iterations per launch; longer runs are chained through its float64 state
-MAX_POINTS_WIDE = 2048          # ladder_slp_wide_optimise (8 < R <= 64, R % 4 == 0): n_step * R <= 2048, the float64 path state stays in LDS
+MAX_POINTS_WIDE = SLP_DENSE.max_points # the dense tier's kernel keeps the float64 path state in LDS: n_step * R <= 2048
 
 
 def path_terms(pts, start, end):
@@ -38,14 +40,15 @@ def path_terms(pts, start, end):
 
 class SLPInterpolator:
     def __init__(self, engine, weights, means, covs):
-        """`engine`: a LadderEngine (for the device / stream / decoders); (weights, means, covs): the fitted mixture, 1 <= R <= 8 (packed
-        form, csrc/slp.hip) or 8 < R <= 64 with R % 4 == 0 (dense form, csrc/slp_wide.hip)."""
+        """`engine`: a LadderEngine (for the device / stream / decoders); (weights, means, covs): the fitted mixture, of a width operation
+        "slp" of mixture_forms.py has a row for (packed: csrc/slp.hip; dense: csrc/slp_wide.hip)."""
         self.eng = engine
         self.K, self.R = (int(n) for n in np.shape(means))
-        if self.R > 8 and (self.R > 64 or self.R % 4 != 0):
-            raise ValueError("SLPInterpolator: the wide mixture (R > 8) needs R %% 4 == 0 and R <= 64 (got R = %d)" % self.R)
+        self.form = family("slp", self.K, self.R)                # (raises for a width no row takes)
         self.mixture = DeviceMixture(engine.ctx, self.K, self.R)
         self.mixture.set(weights, means, covs)
+
+    form = functools.cached_property(lambda self: family("slp", self.K, self.R))      # (for an object built without __init__: on first use)
 
     def neg_log_likelihood(self, pts):
         """-> (-sum_i log p(p_i), gradient [n, R]) from the HIP mixture kernel."""
@@ -89,21 +92,21 @@ class SLPInterpolator:
             raise ValueError("optimise_batch: the end points have R = %d, the mixture has R = %d" % (starts.shape[1], self.R))
         if not 1 <= int(n_step) <= MAX_STEP:
             raise ValueError("optimise_batch: n_step must be in 1..%d (got %r)" % (MAX_STEP, n_step))
-        if getattr(self.mixture, "dense", False) and int(n_step) * self.R > MAX_POINTS_WIDE:
+        if self.form.max_points is not None and int(n_step) * self.R > self.form.max_points:
             raise ValueError("optimise_batch: n_step * R = %d * %d = %d exceeds %d, what the wide kernel (R > 8) keeps of a path"
-                             % (int(n_step), self.R, int(n_step) * self.R, MAX_POINTS_WIDE))
+                             % (int(n_step), self.R, int(n_step) * self.R, self.form.max_points))
         return starts, ends
 
     def optimise_batch(self, starts, ends, n_step=5, n_iter=500, lr=1e-2, w_equal_length=100.0, w_path_dist=10.0, init=None, clip=1.0,
                        record=True):
-        """`optimise` for P pairs at once, the whole loop on the device (ladder_slp_optimise for R <= 8, ladder_slp_wide_optimise on the
-        dense mixture for 8 < R <= 64: one workgroup per path, one launch per 4096 iterations, chained through the float64 state; no host
+        """`optimise` for P pairs at once, the whole loop on the device (the row of operation "slp" for the mixture's tier: one workgroup per
+        path, one launch per 4096 iterations, chained through the float64 state; no host
         synchronisation in between, one copy to the host at the end).
         starts, ends [P, R]; init [P, n_step, R] (default: the notebook's linspace per pair); `clip` is the element-wise gradient bound.
         The kernel takes its inputs as fp32 and keeps points and moments in float64 from there on.
         Returns (pts [P, n_step, R]: the fp32 results as float64, rec: {loss, path_length, step_var, neg_ll} each [P, n_iter] -- None
         when `record` is False)."""
-        starts, ends = self._check_batch(starts, ends, n_step)
+        starts, ends, form = *self._check_batch(starts, ends, n_step), self.form
         n_step, n_iter = int(n_step), int(n_iter)
         if n_iter < 1:
             raise ValueError("optimise_batch: n_iter must be >= 1 (got %d)" % n_iter)
@@ -118,14 +121,12 @@ class SLPInterpolator:
         dev, st = self.eng.ctx.device, self.eng.ctx.stream
         f = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.float32)).to(dev)
         s_d, e_d, pts = f(starts), f(ends), f(init)
-        entry, state_bytes = (("ladder_slp_wide_optimise", "ladder_slp_wide_state_bytes") if self.mixture.dense
-                              else ("ladder_slp_optimise", "ladder_slp_state_bytes"))
-        state = torch.empty(L.query(state_bytes, P, n_step, R) // 8, dtype=torch.float64, device=dev)
+        state = torch.empty(L.query(form.state_bytes, P, n_step, R) // 8, dtype=torch.float64, device=dev)
         recs = []
         for t0 in range(0, n_iter, MAX_ITER_PER_LAUNCH):
             k = min(MAX_ITER_PER_LAUNCH, n_iter - t0)
             r = torch.empty(P, k, 4, dtype=torch.float64, device=dev) if record else None
-            L.call(entry, s_d.data_ptr(), e_d.data_ptr(), pts.data_ptr(), self.mixture.buf.data_ptr(), self.K, R, P, n_step, k, t0,
+            L.call(form.optimise, s_d.data_ptr(), e_d.data_ptr(), pts.data_ptr(), self.mixture.buf.data_ptr(), self.K, R, P, n_step, k, t0,
                    float(lr), 0.9, 0.95, 1e-8, float(clip), float(w_path_dist), float(w_equal_length), state.data_ptr(),
                    None if r is None else r.data_ptr(), st)
             recs.append(r)

@@ -2,8 +2,8 @@
 
 `DeviceKMeans` keeps sklearn.cluster.KMeans' constructor arguments and fitted attributes (`labels_`, `cluster_centers_`, `n_iter_`,
 `inertia_`) for the options the mixtures use (n_init=1, algorithm="lloyd", init "k-means++" or an array), but runs k-means++ seeding and
-Lloyd's iteration in float64 on samples that never leave the GPU (csrc/kmeans.hip: 1 <= R <= 64; csrc/kmeans_wide.hip: 80 <= R <= 256 in steps
-of 16; both 1 <= K <= 64 -- the family of entry points is picked from the samples' width at fit time).  The host contributes the
+Lloyd's iteration in float64 on samples that never leave the GPU (csrc/kmeans.hip or csrc/kmeans_wide.hip: the family is looked up by the samples'
+width at fit time, operation "kmeans" of mixture_forms.py).  The host contributes the
 random numbers of the seeding (codes/mixture_fit.py: kmeans_draws consumes the generator exactly as sklearn does) and reads the `done`
 flag and four scalars; with the same `random_state` a fit gives sklearn's labels and iteration count (tests/test_gpu_kmeans.py,
 tests/test_gpu_kmeans_wide.py).
@@ -12,17 +12,8 @@ import numpy as np
 import torch
 
 from .. import _lib as L
+from ..mixture_forms import family
 from . import mixture_fit as MF
-
-
-def family_prefix(K, R):
-    """The entry points that cluster R-dimensional samples into K: "ladder_kmeans_" (R <= 64) or "ladder_kmeans_wide_" (the widths of the wide EM
-    fit); their state-size queries answer 0 for a shape they do not take."""
-    for prefix in ("ladder_kmeans_", "ladder_kmeans_wide_"):
-        if L.query(prefix + "state_doubles", K, R) != 0:
-            return prefix
-    raise NotImplementedError("the HIP k-means covers 1 <= n_clusters <= 64 and 1 <= n_features <= %d or %d <= n_features <= %d in steps of %d, "
-                              "got %d and %d" % (MF.DEVICE_FIT_MAX_R, MF.DEVICE_FIT_WIDE_MIN_R, MF.DEVICE_FIT_WIDE_MAX_R, MF.DEVICE_FIT_WIDE_STEP, K, R))
 
 
 class DeviceKMeans:
@@ -47,26 +38,25 @@ class DeviceKMeans:
         N, R = Xd.shape
         if N < K:
             raise ValueError("n_samples=%d should be >= n_clusters=%d." % (N, K))
-        prefix = family_prefix(K, R)
+        form = family("kmeans", K, R)
         st = torch.cuda.current_stream(self.device).cuda_stream
-        state = torch.zeros(L.query(prefix + "state_doubles", K, R), dtype=torch.float64, device=self.device)
-        ws = torch.empty(L.query(prefix + "workspace_bytes", N, K, R), dtype=torch.uint8, device=self.device)
+        state = torch.zeros(L.query(form.state_doubles, K, R), dtype=torch.float64, device=self.device)
+        ws = torch.empty(L.query(form.workspace_bytes, N, K, R), dtype=torch.uint8, device=self.device)
         labels = torch.empty(N, dtype=torch.int32, device=self.device)
         head = (Xd.data_ptr(), N, K, R)
         if isinstance(self.init, str):
             first, u = MF.kmeans_draws(check_random_state(self.random_state), N, K)
             start = torch.as_tensor(np.concatenate([[float(first)], u.ravel()])).to(self.device)
-            assert start.numel() == L.query("ladder_kmeans_draws_doubles", K)
-            L.call(prefix + "seed", *head, start.data_ptr(), state.data_ptr(), ws.data_ptr(), ws.numel(), st)
+            assert start.numel() == L.query(form.draws_doubles, K)
         else:
             centres = np.ascontiguousarray(self.init, dtype=np.float64)
             if centres.shape != (K, R):
                 raise ValueError("The shape of the initial centers %s does not match the number of clusters %d and features %d."
                                  % (centres.shape, K, R))
             start = torch.as_tensor(centres).to(self.device)
-            L.call(prefix + "set_centres", *head, start.data_ptr(), state.data_ptr(), ws.data_ptr(), ws.numel(), st)
+        L.call(form.seed if isinstance(self.init, str) else form.set_centres, *head, start.data_ptr(), state.data_ptr(), ws.data_ptr(), ws.numel(), st)
         lib = L.load()
-        assign_fn, update_fn = getattr(lib, prefix + "assign"), getattr(lib, prefix + "update")
+        assign_fn, update_fn = getattr(lib, form.assign), getattr(lib, form.update)
         a_tail = (state.data_ptr(), labels.data_ptr(), ws.data_ptr(), ws.numel(), st)
         u_head = head + (labels.data_ptr(), state.data_ptr(), self.tol, self.max_iter)
         u_tail = (ws.data_ptr(), ws.numel(), st)

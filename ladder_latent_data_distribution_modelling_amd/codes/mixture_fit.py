@@ -10,6 +10,8 @@ import warnings
 import numpy as np
 import torch
 
+from .. import mixture_forms as FORMS
+
 ILL_DEFINED = ("Fitting the mixture model failed because some components have ill-defined empirical covariance "
                "(for instance caused by singleton or collapsed samples). Try to decrease the number of "
                "components, increase reg_covar, or scale the input data.")
@@ -79,45 +81,33 @@ def check_kmeans_backend(backend):
     return backend
 
 
-DEVICE_FIT_MAX_R = 64        # csrc/emgmm.hip, csrc/vbgmm.hip and csrc/kmeans.hip end here; the mixture term and the samplers go on to 256
-# csrc/emgmm_wide.hip and csrc/kmeans_wide.hip: the widths of csrc/chol_wide.h (the variational fit has no wide family)
-DEVICE_FIT_WIDE_MIN_R, DEVICE_FIT_WIDE_MAX_R, DEVICE_FIT_WIDE_STEP = 80, 256, 16
-DEVICE_FIT_WIDTH_RULE = "1 .. %d dimensions, or %d .. %d in steps of %d" % (DEVICE_FIT_MAX_R, DEVICE_FIT_WIDE_MIN_R, DEVICE_FIT_WIDE_MAX_R,
-                                                                            DEVICE_FIT_WIDE_STEP)
 GM_FIT_DEVICE_BACKENDS = ("hip", "hip_wide")     # "hip": the narrow kernels alone; "hip_wide" (prior "GMM"): whichever family takes the width
-
-
-def device_fit_width_ok(R, wide):
-    """Whether a device EM fit exists for R dimensions: the narrow kernels, and with `wide` those of csrc/emgmm_wide.hip."""
-    if 1 <= R <= DEVICE_FIT_MAX_R:
-        return True
-    return bool(wide) and DEVICE_FIT_WIDE_MIN_R <= R <= DEVICE_FIT_WIDE_MAX_R and R % DEVICE_FIT_WIDE_STEP == 0
 
 
 def check_device_fit_width(config):
     """prior "GMM" fits its mixture on z, so the mixture dimension is code_size.  gm_fit_backend "hip" and kmeans_backend "hip" end at 64 dimensions
     (beyond: the host fits, which are the defaults, or "hip_wide"); "hip_wide" is the device EM fit, and as kmeans_backend the device k-means, of prior
-    "GMM" at every width a kernel family takes (DEVICE_FIT_WIDTH_RULE).  For the other priors kmeans_backend "hip_wide" means "hip".  Raises
+    "GMM" at every width a kernel family takes (mixture_forms.EM_WIDTH_RULE).  For the other priors kmeans_backend "hip_wide" means "hip".  Raises
     ValueError naming the config key that asks for what does not exist.  (prior "ours": codes/vbgmm.py checks its own width.)"""
-    if (config.get("kmeans_backend") == "hip_wide" and config.get("prior") == "GMM"
-            and not device_fit_width_ok(int(config["code_size"]), wide=True)):
+    fits = lambda: FORMS.EM_NARROW.takes(int(config["code_size"])) or FORMS.EM_WIDE.takes(int(config["code_size"]))     # (the device k-means: the same widths)
+    if config.get("kmeans_backend") == "hip_wide" and config.get("prior") == "GMM" and not fits():
         raise ValueError('kmeans_backend: "hip_wide" clusters samples of %s, prior "GMM" with code_size = %d needs the host k-means '
-                         '(leave kmeans_backend out or set it to "sklearn")' % (DEVICE_FIT_WIDTH_RULE, int(config["code_size"])))
+                         '(leave kmeans_backend out or set it to "sklearn")' % (FORMS.EM_WIDTH_RULE, int(config["code_size"])))
     if config.get("gm_fit_backend") == "hip_wide":
         if config.get("prior") != "GMM":
             raise ValueError('gm_fit_backend: "hip_wide" is the device EM fit of prior "GMM", not of prior %r (use "hip" or "sklearn" there)'
                              % (config.get("prior"),))
-        if not device_fit_width_ok(int(config["code_size"]), wide=True):
+        if not fits():
             raise ValueError('gm_fit_backend: "hip_wide" fits mixtures on %s, prior "GMM" with code_size = %d needs the host fit '
-                             '(leave gm_fit_backend out or set it to "sklearn")' % (DEVICE_FIT_WIDTH_RULE, int(config["code_size"])))
-    if config.get("prior") != "GMM" or int(config["code_size"]) <= DEVICE_FIT_MAX_R:
+                             '(leave gm_fit_backend out or set it to "sklearn")' % (FORMS.EM_WIDTH_RULE, int(config["code_size"])))
+    if config.get("prior") != "GMM" or int(config["code_size"]) <= FORMS.EM_NARROW.hi:
         return
     for key in ("gm_fit_backend", "kmeans_backend"):
         if config.get(key) == "hip":
             hint = ' or, for a device %s on %d .. %d dimensions in steps of %d, to "hip_wide"' % (
-                "fit" if key == "gm_fit_backend" else "k-means", DEVICE_FIT_WIDE_MIN_R, DEVICE_FIT_WIDE_MAX_R, DEVICE_FIT_WIDE_STEP)
+                "fit" if key == "gm_fit_backend" else "k-means", FORMS.EM_WIDE.lo, FORMS.EM_WIDE.hi, FORMS.EM_WIDE.step)
             raise ValueError('%s: "hip" fits mixtures on at most %d dimensions, prior "GMM" with code_size = %d needs the host fit '
-                             '(leave %s out or set it to "sklearn"%s)' % (key, DEVICE_FIT_MAX_R, int(config["code_size"]), key, hint))
+                             '(leave %s out or set it to "sklearn"%s)' % (key, FORMS.EM_NARROW.hi, int(config["code_size"]), key, hint))
 
 
 def _gather_ragged(parts, x, comm):
@@ -190,10 +180,9 @@ def iterate_until_done(estep, mstep, exchange, stats, flag, first_it, max_iter, 
         done = bool(flag.item() != 0) or it > max_iter                         # (identical on every rank: same all-reduced statistics)
 
 
-# One family of entry points, as fit_sliced drives it.  prefix: of its stats_doubles / workspace_bytes / estep / mstep; moments(Xd, comm, f64, st,
-# check) -> the all-reduced moments, having called check(global sample count) where sklearn checks it; state_query: the size of a fresh state;
-# e_mid(mom): the E-step's arguments between `state` and `stats`; m_mid: the M-step's between `state` and reg_covar; what: names a failed launch.
-Family = collections.namedtuple("Family", "prefix moments state_query e_mid m_mid what")
+# One family as fit_sliced drives it.  form: its row of mixture_forms.FAMILIES; moments(Xd, comm, f64, st, check) -> the all-reduced moments, having called
+# check(global sample count) where sklearn checks it; e_mid(mom): the E-step's arguments between `state` and `stats`; m_mid: the M-step's between `state` and reg_covar
+Family = collections.namedtuple("Family", "form moments e_mid m_mid what")
 
 
 def fit_sliced(gm, X_local, comm, check_every, fam):
@@ -208,12 +197,13 @@ def fit_sliced(gm, X_local, comm, check_every, fam):
     st = torch.cuda.current_stream(gm.device).cuda_stream
     f64 = lambda n: torch.zeros(n, dtype=torch.float64, device=gm.device)
     mom = fam.moments(Xd, comm, f64, st, lambda n: check_sample_count(n, K))    # sklearn's check, on the GLOBAL sample count
-    stats = f64(L.query(fam.prefix + "stats_doubles", K, R))
-    ws = torch.empty(L.query(fam.prefix + "workspace_bytes", Nl, K, R), dtype=torch.uint8, device=gm.device)
+    form = fam.form
+    stats = f64(L.query(form.stats_doubles, K, R))
+    ws = torch.empty(L.query(form.workspace_bytes, Nl, K, R), dtype=torch.uint8, device=gm.device)
     do_init, rs, n_fits = fit_plan(gm)
     lib = L.load()
-    estep_fn, mstep_fn = getattr(lib, fam.prefix + "estep"), getattr(lib, fam.prefix + "mstep")
-    n_state = L.query(fam.state_query, K, R)
+    estep_fn, mstep_fn = getattr(lib, form.estep), getattr(lib, form.mstep)
+    n_state = L.query(form.state_doubles, K, R)
 
     def one_fit():
         state = f64(n_state) if do_init else gm._state

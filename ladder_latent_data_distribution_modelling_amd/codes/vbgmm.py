@@ -10,25 +10,24 @@ default, and the same algorithm on the device with kmeans_backend="hip" (codes/k
 "GMM" prior, is accepted and means the same here, since this fit ends at 64 dimensions); either way a fit with the
 same `random_state` reproduces sklearn's to float64 round-off (tests/test_gpu_vbgmm.py, tests/test_gpu_kmeans.py).
 
-Width of the representation: R <= 8 runs the thread-per-sample kernels (`ladder_vbgmm_fit` below SLICED_FIT_MIN_SAMPLES samples,
-`ladder_vbgmm_shard_*` from there on and for sharded fits); 8 < R <= 64 runs `ladder_vbgmm_wide_*` for every N -- the E-step's whitening
-and the statistics on the float64 MFMA, the passes the EM fit of codes/emgmm.py uses (csrc/fit_mfma.h) -- with the same protocol, state
-front and fitted attributes (tests/test_gpu_vbgmm_wide.py).  1 <= K <= 64 for both.  The fit is the only part of the prior "ours" with
-this limit alone: the engine's wide mixture term also needs R % 4 == 0, and so does interpolation along shortest likely paths (csrc/slp_wide.hip reads the same dense buffer; n_step * R <= 2048).
+Width of the representation (operation "vb" of mixture_forms.py): the packed tier runs the thread-per-sample kernels (the persistent launch below
+SLICED_FIT_MIN_SAMPLES samples, the sharded entries from there on and for sharded fits); the dense tier runs the float64-MFMA entries for every N
+-- the passes the EM fit of codes/emgmm.py uses (csrc/fit_mfma.h) -- with the same protocol, state front and fitted attributes
+(tests/test_gpu_vbgmm_wide.py); there is no wide family.  1 <= K <= 64 for both.  The fit takes every dense width: the engine's dense mixture term
+and SLP interpolation (csrc/slp_wide.hip: n_step * R <= 2048) also need R % 4 == 0.
 """
 import numpy as np
 import torch
 
 from .. import _lib as L
+from ..mixture_forms import VB_PACKED, family
 from . import mixture_fit as MF
 
 
 # from this many samples on, fit() runs one E-step launch over 256-sample slices (one workgroup each) + one M-step launch per variational
 # iteration instead of the single persistent workgroup: 3.8 ms -> ~30 us per iteration at the 20 096 samples of the accurate fit
 SLICED_FIT_MIN_SAMPLES = 1024
-# past this width the fit runs the MFMA kernels (ladder_vbgmm_wide_*) for every N; the persistent one-workgroup kernel stays R <= NARROW_MAX_R
-NARROW_MAX_R = 8
-WIDE_MAX_R = 64
+NARROW_MAX_R = VB_PACKED.hi              # past this width the fit runs the dense tier's entries for every N; the persistent launch is the packed tier's
 
 
 class DeviceBayesianGaussianMixture:
@@ -65,16 +64,17 @@ class DeviceBayesianGaussianMixture:
         MF.check_sample_count(N, K)
         if R > NARROW_MAX_R or N >= SLICED_FIT_MIN_SAMPLES:
             return self.fit_sharded(Xd, MF.OneRank(), check_every=16)
+        form = family("vb", K, R)
         ptype, wc, mp = self._prior_args()
-        ws = torch.empty(L.query("ladder_vbgmm_workspace_bytes", N, K), dtype=torch.uint8, device=self.device)
+        ws = torch.empty(L.query(form.fit_workspace_bytes, N, K), dtype=torch.uint8, device=self.device)
         st = torch.cuda.current_stream(self.device).cuda_stream
         do_init, rs, n_fits = MF.fit_plan(self)
 
         def one_fit():
-            state = torch.zeros(L.query("ladder_vbgmm_state_doubles", K, R), dtype=torch.float64, device=self.device) if do_init else self._state
+            state = torch.zeros(L.query(form.state_doubles, K, R), dtype=torch.float64, device=self.device) if do_init else self._state
             labels = self._initial_labels(Xd, MF.OneRank(), rs) if do_init else None
             w, m, c = MF.feed_tensors(K, R, self.device)
-            L.call("ladder_vbgmm_fit", Xd.data_ptr(), N, K, R, labels.data_ptr() if labels is not None else None, state.data_ptr(),
+            L.call(form.fit, Xd.data_ptr(), N, K, R, labels.data_ptr() if labels is not None else None, state.data_ptr(),
                    ptype, wc, mp, float(self.reg_covar), float(self.tol), self.max_iter, w.data_ptr(), m.data_ptr(), c.data_ptr(),
                    ws.data_ptr(), ws.numel(), st)
             return state, w, m, c                          # (the one host sync of the fit: the tail read of best_of_restarts)
@@ -90,35 +90,32 @@ class DeviceBayesianGaussianMixture:
         an all-reduce of the mixture's sufficient statistics): `X_local` [N_local, R] are THIS rank's samples, `comm` the engine's
         communicator (all-reduce over RCCL / xGMI).  The loop is MF.fit_sliced's: per variational iteration E-step + local statistics,
         all-reduce of 1 + K + K R + K R^2 doubles, M-step + lower bound + convergence test; the result does not depend on `check_every`.
-        R > 8 picks the ladder_vbgmm_wide_* family: same loop, the data-derived priors from two small all-reduces ([sum x | N], then the second
+        The dense tier's family runs the same loop, with the data-derived priors from two small all-reduces ([sum x | N], then the second
         moments about the shift that defines)."""
         Xd = MF.device_samples(X_local, self.device)
         R = Xd.shape[1]
-        if R > WIDE_MAX_R:
-            raise ValueError("the HIP mixture fit takes a representation of at most %d dimensions, got %d" % (WIDE_MAX_R, R))
-        wide = R > NARROW_MAX_R
-        prefix = "ladder_vbgmm_wide_" if wide else "ladder_vbgmm_shard_"
+        form = family("vb", self.n_components, R)
         ptype, wc, mp = self._prior_args()
 
         def moments(Xd, comm, f64, st, check):
             Nl = Xd.shape[0]
-            mom = f64(L.query(prefix + "moments_doubles", R))
-            if wide:
-                L.call(prefix + "moments", Xd.data_ptr(), Nl, R, mom.data_ptr(), 0, st)
+            mom = f64(L.query(form.moments_doubles, R))
+            if form.moments_by_pass:
+                L.call(form.moments, Xd.data_ptr(), Nl, R, mom.data_ptr(), 0, st)
                 comm.allreduce_(mom[:R + 1])                                   # [ sum x | N ]: the shift, mean_prior_ and the global count
                 check(int(mom[R].item()))
-                L.call(prefix + "moments", Xd.data_ptr(), Nl, R, mom.data_ptr(), 1, st)
+                L.call(form.moments, Xd.data_ptr(), Nl, R, mom.data_ptr(), 1, st)
                 comm.allreduce_(mom[R + 1:])                                   # sum x~ x~^T about that shift: covariance_prior_
             else:
-                L.call(prefix + "moments", Xd.data_ptr(), Nl, R, mom.data_ptr(), st)
+                L.call(form.moments, Xd.data_ptr(), Nl, R, mom.data_ptr(), st)
                 comm.allreduce_(mom)
                 n_glob = torch.full((1,), float(Nl), dtype=torch.float64, device=self.device)
                 comm.allreduce_(n_glob)
                 check(int(n_glob.item()))
             return mom
 
-        fam = MF.Family(prefix, moments, "ladder_vbgmm_wide_state_doubles" if wide else "ladder_vbgmm_state_doubles",
-                        (lambda mom: (ptype, mom.data_ptr())) if wide else (lambda mom: (ptype,)), (ptype, wc, mp), "sharded mixture fit")
+        fam = MF.Family(form, moments, lambda mom: (ptype, mom.data_ptr()) if form.estep_takes_moments else (ptype,), (ptype, wc, mp),
+                        "sharded mixture fit")
         return MF.keep_best(self, MF.fit_sliced(self, Xd, comm, check_every, fam))
 
     # float64 views of the fitted parameters, as sklearn exposes them

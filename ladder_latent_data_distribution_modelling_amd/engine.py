@@ -15,6 +15,7 @@ from .comm import Comm, VirtualComm, VirtualGroup, run_virtual_ranks, _NoComm, _
 from .layers import (ADAM_B1, ADAM_B2, ADAM_EPS, BN_EPS, DEFAULT_PRECISION, IN_EPS, PRECISION_NOTES, PRECISIONS, BatchNormAct, Conv2D, Ctx, Dense,  # noqa: F401
                      DepthToSpace, InstanceNormStyleAct, ParamStore, PlanesOnly, Resize, _p, _timed, add_, pad_symmetric, plan_decoder)
 from .mixture import DeviceMixture
+from .mixture_forms import check_status_word, family, sized_workspace
 from .profiler import KernelProfiler  # noqa: F401
 
 
@@ -276,12 +277,13 @@ PRIOR_METHODS = arch.PRIOR_METHODS
 class PriorSampler:
     """Handle of LadderEngine.prior_sampler(): ancestral samples of one prior, drawn on the device (reference codes/base.py:1065-1122).
 
-    Owns the prepared parameter buffer of csrc/sample.hip (R <= 64, or its wide sampler for 64 < R <= 256 with R % 16 == 0: one layout).
+    Owns the prepared parameter buffer of csrc/sample.hip (one layout for both of its families).
     Its Philox stream is its own -- (seed, offset) of this object, never the engine's training noise position -- and sample index i draws the same values whatever the chunking: sample(n, first) returns samples
     first .. first+n-1 of ONE stream, so a bulk run may be cut into chunks (or, later, sharded over ranks) freely."""
 
-    def __init__(self, eng, method, K, R, params, seed=0, offset=0):
-        self.eng, self.method, self.K, self.R, self.params = eng, method, int(K), int(R), params
+    def __init__(self, eng, method, form, K, R, params, seed=0, offset=0):
+        """`form`: the row of operation "sampler" (mixture_forms.py) whose `prepare` filled `params`."""
+        self.eng, self.method, self.form, self.K, self.R, self.params = eng, method, form, int(K), int(R), params
         self.seed, self.offset = int(seed), int(offset)
         self.to_code = method in ("ours", "hierarchical")      # the draw is t: the code is the inner decoder's output (base.py:1088-1118)
 
@@ -296,7 +298,7 @@ class PriorSampler:
             u, eps = eng._dev(noise["u"]).reshape(-1), eng._dev(noise["eps"])
             if tuple(u.shape) != (n,) or tuple(eps.shape) != (n, self.R):
                 raise ValueError("noise: u %s, eps %s; expected (%d,) and (%d, %d)" % (tuple(u.shape), tuple(eps.shape), n, n, self.R))
-        L.call("ladder_mixture_sample_wide" if self.R > 64 else "ladder_mixture_sample", _p(self.params), self.K, self.R, n, int(first), _p(u), _p(eps),
+        L.call(self.form.sample, _p(self.params), self.K, self.R, n, int(first), _p(u), _p(eps),
                self.seed if seed is None else int(seed), self.offset, _p(latent), _p(comp), ctx.stream)
         code = eng.decode_representation(latent) if self.to_code else latent
         return code, latent, comp
@@ -888,43 +890,32 @@ class LadderEngine:
             raise ValueError("method %r needs the inner VAE; this model's prior is %r" % (method, self.cfg["prior"]))
         self._join_aux()
         ctx, st = self.ctx, self.ctx.stream
-        keep = None
-        if method in ("GMM", "ours"):
+        full = method in ("GMM", "ours")                         # (weights, means, covs); else K diagonal components (means, scales)
+        if full:
             if mixture is None:
                 raise ValueError("method %r samples a fitted mixture: pass mixture=(weights, means, covs)" % method)
             w, m, c = (self._dev(a) for a in mixture)
             K, R = int(w.numel()), int(self.Z if method == "GMM" else self.cfg["representation_size"])
             if tuple(m.shape) != (K, R) or tuple(c.shape) != (K, R, R):
                 raise ValueError("mixture shapes %s %s %s do not fit K = %d, R = %d" % (tuple(w.shape), tuple(m.shape), tuple(c.shape), K, R))
-            prep, keep = "ladder_mixture_sample_prepare", (w, m, c)
+            keep = (w, m, c)
         elif method == "vampPrior":
             if not self.vamp:
                 raise ValueError("method 'vampPrior' needs the pseudo-inputs; this model's prior is %r" % self.cfg["prior"])
             K, R = self.K, self.Z
-            prep, keep = "ladder_mixture_sample_prepare_diag", self._vamp_components()[:2]
+            keep = self._vamp_components()[:2]
         else:
             K, R = 1, int(self.Z if method == "standard_gaussian" else self.cfg["representation_size"])
-            prep, keep = "ladder_mixture_sample_prepare_diag", (ctx.zeros(1, R), torch.ones(1, R, dtype=torch.float32, device=ctx.device))
-        wide = R > 64                                            # the wide sampler: same buffer, same draws (csrc/sample.hip)
-        if wide:
-            prep = prep.replace("ladder_mixture_sample_", "ladder_mixture_sample_wide_")
-        nbytes = L.query("ladder_mixture_sample_wide_param_bytes" if wide else "ladder_mixture_sample_param_bytes", K, R)
+            keep = (ctx.zeros(1, R), torch.ones(1, R, dtype=torch.float32, device=ctx.device))
+        form = family("sampler", K, R)                           # (both families: same buffer, same draws, csrc/sample.hip)
+        nbytes = L.query(form.param_bytes, K, R)
         if nbytes == 0:
             raise ValueError("the device sampler takes K >= 1 and 1 <= R <= 64, or 64 < R <= 256 with R %% 16 == 0 (got K = %d, R = %d)" % (K, R))
         params = torch.empty(nbytes, dtype=torch.uint8, device=ctx.device)
-        if len(keep) == 3 and wide:
-            fws = torch.empty(L.query("ladder_mixture_sample_wide_prepare_workspace_bytes", K, R), dtype=torch.uint8, device=ctx.device)
-            L.call(prep, _p(keep[0]), _p(keep[1]), _p(keep[2]), K, R, _p(params), _p(fws), fws.numel(), st)
-        elif len(keep) == 3:
-            L.call(prep, _p(keep[0]), _p(keep[1]), _p(keep[2]), K, R, _p(params), st)
-        else:
-            L.call(prep, _p(keep[0]), _p(keep[1]), K, R, _p(params), st)
-        status = int(params[:4].view(torch.int32).item())        # (the one read of the status word; also keeps the temporaries alive until the kernels ran)
-        if status >= 0:
-            raise ValueError("component %d of the %s mixture has no Cholesky factor (covariance / scale not positive definite)" % (status, method))
-        if status != -1:
-            raise ValueError("the weights of the %s mixture have no positive finite sum" % method)
-        return PriorSampler(self, method, K, R, params, seed)
+        fws, fws_args = sized_workspace(form.prepare_workspace_bytes if full else None, ctx.device, K, R)
+        L.call(form.prepare if full else form.prepare_diag, *(_p(a) for a in keep), K, R, _p(params), *fws_args, st)
+        check_status_word(params, "%s mixture" % method, "covariance / scale")      # (the read also keeps the temporaries alive until the kernels ran)
+        return PriorSampler(self, method, form, K, R, params, seed)
 
     def images_to_u8(self, x):
         """uint8 device tensor of x's shape: rint(255 * clip(x, 0, 1)), NaN -> 0 (ladder_images_to_u8)."""

@@ -106,7 +106,6 @@ def test_shape_rejections_before_launch(lib):
 
 
 def test_config_rules_of_hip_wide():
-    from ladder_latent_data_distribution_modelling_amd.codes.emgmm import family_prefix
     from ladder_latent_data_distribution_modelling_amd.codes.mixture_fit import check_device_fit_width
     cfg = dict(prior="GMM", n_mixtures=6)
     for size in (80, 256, 16, 64, 1, 144):
@@ -124,9 +123,4 @@ def test_config_rules_of_hip_wide():
     with pytest.raises(ValueError, match="kmeans_backend.*64"):                       # device k-means beyond 64 dimensions stays refused
         check_device_fit_width(dict(cfg, code_size=128, gm_fit_backend="hip_wide", kmeans_backend="hip"))
     check_device_fit_width(dict(cfg, code_size=64, gm_fit_backend="hip_wide", kmeans_backend="hip"))
-    # the mixture object picks its entry points from the width, and says which widths exist
-    assert family_prefix(64) == "ladder_emgmm_" and family_prefix(1) == "ladder_emgmm_"
-    assert family_prefix(80) == family_prefix(256) == "ladder_emgmm_wide_"
-    for R in (72, 272, 0):
-        with pytest.raises(ValueError, match=r"80 \.\. 256 in steps of 16"):
-            family_prefix(R)
+    # (how the mixture object picks its entry points from the width, and says which widths exist: tests/test_mixture_forms_cpu.py)

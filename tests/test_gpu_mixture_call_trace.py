@@ -1,0 +1,174 @@
+"""The foreign calls of every mixture owner, tier by tier, against the sequence recorded before the owners were moved onto the family table
+(mixture_forms.py): entry names, their order, every scalar argument and which pointers are NULL.  tests/golden/mixture_call_trace.json is the
+project's own recorded result, kept as recorded; `python tests/test_gpu_mixture_call_trace.py OUT.json` writes one from whatever code is checked out.
+
+One difference from the record is intended and spelt out in `without_selection_probes`: DeviceKMeans used to FIND its family by asking each
+family's state-size query in turn and then asked the chosen one again for the size; the table selects now, so of such a run of state-size queries
+only the last -- the sizing one, with its arguments -- is still issued.  Everything else, every other query included, is compared as recorded."""
+import ctypes
+import json
+import os
+import sys
+import types
+import warnings
+
+import numpy as np
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLDEN = os.path.join(ROOT, "tests", "golden", "mixture_call_trace.json")
+WIDTHS = (4, 16, 80)                 # one per tier: packed, dense, wide
+K, B, N = 3, 8, 256
+
+SECTIONS = (["term R=%d" % R for R in WIDTHS] + ["sampler %s R=%d" % (m, R) for R in WIDTHS for m in ("GMM", "standard_gaussian")]
+            + ["em fit R=%d" % R for R in (16, 80)] + ["kmeans %s R=%d" % (s, R) for R in (16, 80) for s in ("seeded", "array")]
+            + ["vb fit persistent R=4", "vb fit sharded R=4", "vb fit R=16", "slp R=4", "slp R=16"])
+
+
+class Recorder:
+    """Stands where _lib keeps the loaded library: every export looked up on it records [name, arguments] and then runs; an argument the prototype
+    declares as a pointer is kept as "NULL" or "PTR" only."""
+
+    def __init__(self, lib, prototypes):
+        self._lib, self._prototypes, self.calls = lib, prototypes, []
+
+    def __getattr__(self, name):
+        fn, argtypes = getattr(self._lib, name), self._prototypes[name][1]
+
+        def recorded(*args):
+            assert len(args) == len(argtypes), name
+            self.calls.append([name] + [("PTR" if a else "NULL") if t is ctypes.c_void_p else (float(a) if t in (ctypes.c_float, ctypes.c_double) else int(a))
+                                        for t, a in zip(argtypes, args)])
+            return fn(*args)
+        return recorded
+
+
+def mixture(R, seed=0):
+    rng = np.random.default_rng(seed)
+    A = rng.normal(0, 0.2 / np.sqrt(R), (K, R, R))
+    return (np.full(K, 1.0 / K, np.float32), rng.normal(0, 1, (K, R)).astype(np.float32),
+            (0.5 * np.eye(R)[None] + A @ A.transpose(0, 2, 1)).astype(np.float32))
+
+
+def samples(R, seed=1):
+    """N points around K well separated centres: the k-means of a cold fit ends inside its first block of iterations."""
+    rng = np.random.default_rng(seed)
+    return torch.as_tensor((4.0 * rng.normal(size=(K, R))[rng.integers(0, K, N)] + 0.3 * rng.normal(size=(N, R))).astype(np.float32)).cuda()
+
+
+def drive(golden_dir):
+    """Runs every owner once per tier -> {section: [[name, arguments...], ...]}."""
+    from ladder_latent_data_distribution_modelling_amd import _lib as L
+    from ladder_latent_data_distribution_modelling_amd.codes import mixture_fit as MF
+    from ladder_latent_data_distribution_modelling_amd.codes.emgmm import DeviceGaussianMixture
+    from ladder_latent_data_distribution_modelling_amd.codes.interpolation import SLPInterpolator
+    from ladder_latent_data_distribution_modelling_amd.codes.kmeans import DeviceKMeans
+    from ladder_latent_data_distribution_modelling_amd.codes.vbgmm import DeviceBayesianGaussianMixture
+    from ladder_latent_data_distribution_modelling_amd.engine import Ctx, LadderEngine
+    from ladder_latent_data_distribution_modelling_amd.mixture import DeviceMixture
+    real = L.load()
+    rec = Recorder(real, L.PROTOTYPES)
+    out = {}
+
+    def section(name):
+        torch.cuda.synchronize()
+        out[name], rec.calls = rec.calls, []
+
+    L._lib = rec
+    try:
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")                                   # (two-iteration fits end unconverged by construction)
+            ctx = Ctx("cuda:0")
+            rec.calls = []
+            for R in WIDTHS:
+                mix = DeviceMixture(ctx, K, R)
+                mix.set(*mixture(R))
+                mu, sd, eps, s = torch.zeros(B, R, device="cuda"), torch.ones(B, R, device="cuda"), torch.zeros(1, B, R, device="cuda"), torch.empty(1, device="cuda")
+                mix.fwd_bwd(mu, sd, eps, s, need_grad=True)
+                mix.fwd_bwd(mu, sd, eps, s, need_grad=False)
+                mix.log_prob_rows(mu)
+                section("term R=%d" % R)
+            cfg = json.loads(str(np.load(os.path.join(golden_dir, "oracle_mnist_fashion.npz"))["config"]))
+            for R in WIDTHS:
+                eng = LadderEngine(dict(cfg, prior="GMM", code_size=R, n_mixtures=K), "cuda:0", seed=2)
+                for method in ("GMM", "standard_gaussian"):
+                    torch.cuda.synchronize()
+                    rec.calls = []
+                    eng.prior_sampler(method, mixture(R) if method == "GMM" else None, seed=5).sample(8)
+                    section("sampler %s R=%d" % (method, R))
+            for R in (16, 80):
+                gm = DeviceGaussianMixture(n_components=K, max_iter=2, random_state=3, kmeans_backend="hip").fit(samples(R))
+                gm._prepare_state(gm._state, R)
+                section("em fit R=%d" % R)
+            for R in (16, 80):
+                X = samples(R)
+                DeviceKMeans(n_clusters=K, max_iter=3, random_state=3).fit(X)
+                section("kmeans seeded R=%d" % R)
+                DeviceKMeans(n_clusters=K, max_iter=3, init=X[:K].cpu().numpy()).fit(X)
+                section("kmeans array R=%d" % R)
+            vb = dict(n_components=K, max_iter=2, random_state=3, kmeans_backend="hip")
+            DeviceBayesianGaussianMixture(**vb).fit(samples(4))
+            section("vb fit persistent R=4")
+            DeviceBayesianGaussianMixture(**vb).fit_sharded(samples(4), MF.OneRank(), check_every=8)
+            section("vb fit sharded R=4")
+            DeviceBayesianGaussianMixture(**vb).fit(samples(16))
+            section("vb fit R=16")
+            for R in (4, 16):
+                rng = np.random.default_rng(7)
+                slp = SLPInterpolator(types.SimpleNamespace(ctx=ctx), *mixture(R))
+                rec.calls = []                                                # (the mixture's own set(): section "term")
+                slp.optimise_batch(rng.normal(size=(2, R)), rng.normal(size=(2, R)), n_step=4, n_iter=5)
+                section("slp R=%d" % R)
+    finally:
+        L._lib = real
+    return out
+
+
+KMEANS_STATE_QUERIES = ("ladder_kmeans_state_doubles", "ladder_kmeans_wide_state_doubles")
+
+
+def without_selection_probes(calls):
+    """The recorded calls minus every k-means state-size query that is directly followed by another one (the probes; see the module docstring)."""
+    return [c for c, nxt in zip(calls, calls[1:] + [[None]]) if not (c[0] in KMEANS_STATE_QUERIES and nxt[0] in KMEANS_STATE_QUERIES)]
+
+
+@pytest.fixture(scope="module")
+def traces(golden_dir):
+    with open(GOLDEN) as f:
+        recorded = json.load(f)
+    return recorded, json.loads(json.dumps(drive(golden_dir)))
+
+
+def test_the_record_holds_the_probes_where_a_kmeans_ran(traces):
+    """The record is the parent's: each of its k-means fits opens with the probes (one at the packed and dense tiers, two at the wide tier) and the
+    sizing query; nothing else is taken out of it."""
+    recorded = traces[0]
+    for name, calls in recorded.items():
+        names = [c[0] for c in calls]
+        dropped = len(calls) - len(without_selection_probes(calls))
+        fits = names.count("ladder_kmeans_workspace_bytes") + 2 * names.count("ladder_kmeans_wide_workspace_bytes")
+        assert dropped == fits, name
+        assert dropped > 0 or not any(n in KMEANS_STATE_QUERIES for n in names), name
+
+
+def test_every_section_is_recorded(traces):
+    want, got = traces
+    assert sorted(want) == sorted(got) == sorted(SECTIONS)
+    assert all(len(calls) > 0 for calls in want.values())
+
+
+@pytest.mark.parametrize("name", SECTIONS)
+def test_foreign_calls_are_the_recorded_ones(traces, name):
+    want, got = without_selection_probes(traces[0][name]), traces[1][name]
+    assert [c[0] for c in got] == [c[0] for c in want]                        # names and order first: the shorter message
+    assert got == want
+
+
+if __name__ == "__main__":
+    sys.path.insert(0, ROOT)
+    got = drive(os.path.join(ROOT, "tests", "golden"))
+    with open(sys.argv[1], "w") as f:                                         # one call per line
+        f.write("{\n" + ",\n".join("%s: [\n%s\n]" % (json.dumps(n), ",\n".join(json.dumps(c) for c in got[n])) for n in SECTIONS) + "\n}\n")
