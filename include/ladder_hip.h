@@ -742,6 +742,21 @@ int ladder_diag_mixture_fwd_bwd(const float* mu, const float* sd, const float* e
                                 int L, int B, int Z, int K, float* sum_logp, float* dmu, float* dsd, float* dcomp_mean,
                                 float* dcomp_sd, void* ws, size_t ws_bytes, ladder_stream_t stream);
 
+/* ---- the same term on a WIDE code (codes/base.py:216-254, 361-370 at the shipped codes/celeba_config.json width; csrc/diag_mixture_wide.hip):
+ * 80 <= Z <= 256 with Z % 16 == 0 (the widths of ladder_mixture_sample_wide_prepare_diag), 1 <= K <= 1024, L, B >= 1, L*B <= 2^30.  Arguments, outputs
+ * and signs are those of ladder_diag_mixture_fwd_bwd, which keeps Z <= 64: with t = mu[b] + sd[b] * eps[l,b],
+ *   sum_logp = sum_{l,b} log (1/K) sum_k N(t; m_k, diag(s_k^2));  dmu, dsd [B,Z];  dcomp_mean, dcomp_sd [K,Z] summed over the L*B samples.
+ * u = (t - m_k) / s_k is formed directly with 1/s_k prepared once per call, the log-sum-exp is max-subtracted (a component of responsibility 0 gets an
+ * exactly zero gradient), every sum has one fixed order (no atomics): two calls on the same inputs give the same bits whatever `ws` held before.
+ * Launches: prepare, responsibilities r [L*B, K] (+ float64 log-prob partials), accumulate on a (sample slice, 16 components) grid, three fixed-order
+ * reductions.  No allocation, no synchronisation, capturable.  `ws` >= ladder_diag_mixture_wide_workspace_bytes(L, B, Z, K) (0 outside the shapes above;
+ * it holds r, at most 64 MB of per-slice [K,Z] partials and the per-l-range [B,Z] partials, never an [L*B, K, Z] array); any alignment.
+ * LADDER_E_SHAPE outside the shapes above, LADDER_E_WORKSPACE for a NULL or short workspace; a refused call launches nothing. */
+size_t ladder_diag_mixture_wide_workspace_bytes(int L, int B, int Z, int K);
+int ladder_diag_mixture_wide_fwd_bwd(const float* mu, const float* sd, const float* eps, const float* comp_mean, const float* comp_sd,
+                                     int L, int B, int Z, int K, float* sum_logp, float* dmu, float* dsd, float* dcomp_mean,
+                                     float* dcomp_sd, void* ws, size_t ws_bytes, ladder_stream_t stream);
+
 /* ---------------------------------------------------------------- N14: minibatch assembly (the input pipeline)
  * models.py:354-371 (CelebA: uint8 HWC pixels * 1/255), data_loader.py:19-33 (MNIST floats), shuffle + batch of models.py:33-40:
  * out[b, :] = scale * float(src[idx[b], :]) for a data set resident in device memory; src is uint8 (src_is_u8) or float32 rows of

@@ -102,6 +102,8 @@ PROTOTYPES = {
     "ladder_gmm_dense_logprob_fwd_bwd": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _p, _p, _p, _p, _z, _p]),
     "ladder_diag_mixture_workspace_bytes": (_z, [_i, _i, _i]),
     "ladder_diag_mixture_fwd_bwd": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _z, _p]),
+    "ladder_diag_mixture_wide_workspace_bytes": (_z, [_i, _i, _i, _i]),
+    "ladder_diag_mixture_wide_fwd_bwd": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _z, _p]),
     "ladder_pad_symmetric_bwd": (_i, [_p, _p, _i, _i, _i, _i, _i, _p]),
     "ladder_conv1x1_smallcout_eligible": (_i, [C.c_long, _i, _i]),
     "ladder_conv1x1_smallcout_bwd_workspace_bytes": (_z, [C.c_long, _i, _i]),

@@ -576,11 +576,21 @@ class LadderEngine:
         mu_p, sd_p, sdraw_p, eps0 = self._vamp_components()
         eps_mc = self._noise(noise, "eps_mc", (self.Lmc, B, Z))
         dmu, dsd, dcm, dcs = ctx.empty(B, Z), ctx.empty(B, Z), ctx.empty(K, Z), ctx.empty(K, Z)
-        wsp, wsn = ctx.ws(L.query("ladder_diag_mixture_workspace_bytes", B, Z, K))
-        L.call("ladder_diag_mixture_fwd_bwd", _p(mu), _p(sd), _p(eps_mc), _p(mu_p), _p(sd_p), self.Lmc, B, Z, K, _p(P[L.P_LOGP:]),
+        query, entry, wide = self._vamp_entries(Z)
+        wsp, wsn = ctx.ws(L.query(query, self.Lmc, B, Z, K) if wide else L.query(query, B, Z, K))
+        L.call(entry, _p(mu), _p(sd), _p(eps_mc), _p(mu_p), _p(sd_p), self.Lmc, B, Z, K, _p(P[L.P_LOGP:]),
                _p(dmu), _p(dsd), _p(dcm), _p(dcs), wsp, wsn, st)
         self.vamp_state = (mu_p, sd_p, sdraw_p, eps0, dcm, dcs)
         return dmu, dsd
+
+    @staticmethod
+    def _vamp_entries(Z):
+        """(workspace query, term, wide) of the VampPrior term on a code of width Z: the wide pair (csrc/diag_mixture_wide.hip; its query
+        takes L as well) for 80 .. 256 in steps of 16, the widths of the wide diagonal sampler; the narrow pair (csrc/mixture.hip) for
+        every other width, which refuses Z > 64 itself."""
+        if 80 <= Z <= 256 and Z % 16 == 0:
+            return "ladder_diag_mixture_wide_workspace_bytes", "ladder_diag_mixture_wide_fwd_bwd", True
+        return "ladder_diag_mixture_workspace_bytes", "ladder_diag_mixture_fwd_bwd", False
 
     def _vamp_backward(self, wgrad, need_input_dx):
         """Backward of the pseudo-input pass: d loss/d components = -(1/LB) * (dcomp_mean, dcomp_sd) through the heads."""
