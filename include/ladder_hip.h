@@ -1079,6 +1079,35 @@ int ladder_kmeans_wide_assign(const float* X, int N, int K, int R, int it, const
 int ladder_kmeans_wide_update(const float* X, int N, int K, int R, const int* labels, double* state, double tol, int max_iter, int it, void* ws,
                               size_t ws_bytes, ladder_stream_t stream);
 
+/* ---------------------------------------------------------------- N24: two-sample statistics over all pairs of two row sets (csrc/twosample.hip)
+ * Improved precision / recall (Kynkaanniemi et al., 2019: k-NN balls on feature rows) and the kernel inception distance (Binkowski et al., 2018: an
+ * unbiased MMD^2 with a polynomial kernel), for fp32 rows [n, D] of any width: VGG16 features and latent codes alike.  One pair-walk core on
+ * v_mfma_f64_16x16x4_f64 forms G_ij = (a_i - c).(b_j - c) for 64 x 64 tiles (c = `shift` [D], fp32, NULL = none; x - c is taken in float64), three
+ * epilogues consume the tile on chip.  No n x m array exists in global memory, nothing is added atomically, and every floating-point sum has one
+ * fixed order: a call gives the same bits every time.  Squared distances are d_ij = max(norms_i + norms_j - 2 G_ij, 0), float64.
+ *   ladder_pairs_row_norms: norms[i] = sum_k (x_ik - c_k)^2, float64, k ascending.  The SAME shift must go to every call that meets these norms.
+ *   ladder_pairs_knn_radii: r2[i] = the k-th smallest d_ij over j != i inside ONE set a [n, D].  Self is excluded by index, never by value: duplicate
+ *     rows give radius 0.  1 <= k <= 8 and k <= n - 1.
+ *   ladder_pairs_ball_counts: counts[i] (int32) = the number of j with d(q_i, a_j) <= r2[j] (non-strict), q [m, D] the queries, a [n, D] the ball
+ *     centres with their radii r2 [n].
+ *   ladder_pairs_poly_sums: x [n_blocks * sx, D] and y [n_blocks * sy, D] are n_blocks gathered subset pairs; sums [n_blocks][3] (float64) receives
+ *     per block  sum_{i != j} kappa(x_i, x_j) | sum_{i != j} kappa(y_i, y_j) | sum_{i, j} kappa(x_i, y_j)  with kappa(u, v) = (gamma u.v + coef0)^degree
+ *     on RAW dot products (no shift), degree 1 .. 4, all blocks in one launch.  A block's sums do not depend on the other blocks of the launch.
+ *   ladder_pairs_workspace_bytes(rows, cols, D, k, n_blocks): the workspace of the three walks --  k >= 1, n_blocks == 0: knn_radii of rows == cols rows;
+ *     k == 0, n_blocks == 0: ball_counts of `rows` queries against `cols` balls;  k == 0, n_blocks >= 1: poly_sums with sx = rows, sy = cols.
+ *     0 for any other combination and outside the limits below.
+ * Limits: 1 <= D <= 32768; every row count (n, m, n_blocks * sx, n_blocks * sy) from 1 to 2^24; 1 <= n_blocks <= 65535.  LADDER_E_SHAPE (nothing
+ * launched) outside them, for a k or degree out of range and for a NULL array (shift excepted); LADDER_E_ALIGN for float64 arrays off 8 bytes;
+ * LADDER_E_WORKSPACE for a workspace shorter than the query's answer.  No read goes past rows * D floats of a set. */
+size_t ladder_pairs_workspace_bytes(int rows, int cols, int D, int k, int n_blocks);
+int ladder_pairs_row_norms(const float* x, int n, int D, const float* shift, double* norms, ladder_stream_t stream);
+int ladder_pairs_knn_radii(const float* a, const double* norms_a, int n, int D, const float* shift, int k, double* r2, void* ws, size_t ws_bytes,
+                           ladder_stream_t stream);
+int ladder_pairs_ball_counts(const float* q, const double* norms_q, int m, const float* a, const double* norms_a, const double* r2, int n, int D,
+                             const float* shift, int* counts, void* ws, size_t ws_bytes, ladder_stream_t stream);
+int ladder_pairs_poly_sums(const float* x, int sx, const float* y, int sy, int n_blocks, int D, int degree, double gamma, double coef0, double* sums,
+                           void* ws, size_t ws_bytes, ladder_stream_t stream);
+
 /* ---------------------------------------------------------------- helpers */
 /* HOST function (no device work): CRC-32C (Castagnoli) of host memory, crc = 0 to start, chainable.  Used by the
  * tf.train.Saver checkpoint-v2 reader/writer (codes/base.py:37-85: saver_ae / saver_prior) for block and tensor checksums. */

@@ -280,6 +280,11 @@ PROTOTYPES = {
     "ladder_mixture_sample_wide_prepare": (_i, [_p, _p, _p, _i, _i, _p, _p, _z, _p]),
     "ladder_mixture_sample_wide_prepare_diag": (_i, [_p, _p, _i, _i, _p, _p]),
     "ladder_mixture_sample_wide": (_i, [_p, _i, _i, _i, C.c_int64, _p, _p, _u64, _u64, _p, _p, _p]),
+    "ladder_pairs_workspace_bytes": (_z, [_i] * 5),
+    "ladder_pairs_row_norms": (_i, [_p, _i, _i, _p, _p, _p]),
+    "ladder_pairs_knn_radii": (_i, [_p, _p, _i, _i, _p, _i, _p, _p, _z, _p]),
+    "ladder_pairs_ball_counts": (_i, [_p, _p, _i, _p, _p, _p, _i, _i, _p, _p, _p, _z, _p]),
+    "ladder_pairs_poly_sums": (_i, [_p, _i, _p, _i, _i, _i, _i, _d, _d, _p, _p, _z, _p]),
 }
 
 _lib = None

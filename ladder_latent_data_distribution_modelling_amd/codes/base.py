@@ -501,6 +501,49 @@ class BaseTrain_joint(BaseTrain):
         (_, m1, c1), (_, m2, c2) = s_real.moments(), s_gen.moments()
         return fid.frechet_distance(m1, c1, m2, c2)
 
+    def compute_sample_metrics(self, real, n, weights, metrics=("fid", "kid", "pr"), mode="accurate-GM", method=None, pooling="avg", chunk=128, seed=None,
+                               input_size=64, k=3, n_subsets=100, subset_size=1000, kid_seed=0):
+        """compute_FID's two sets through the feature network ONCE for any of "fid", "kid" and "pr" (fid.metrics_from_arrays: kernel inception
+        distance over n_subsets seeded subsets of subset_size rows; improved precision / recall and density on k-NN balls).  The generated images go
+        from the decoder into the feature network, the float64 statistics and the feature bank: they never leave the device.  -> dict."""
+        from .. import fid, two_sample as T
+        metrics = T.check_metrics(metrics)
+        real = fid.load_images(real)
+        if "pr" in metrics:
+            T.check_k(k, int(real.shape[0]), int(n))
+        self.flush()
+        _, sampler = self._prior_sampler(mode, method, seed)
+        features = fid.VGG16Features(self.engine.ctx, weights, fid.check_pooling(pooling), input_size)
+        sets = fid.MetricSets(features, metrics)
+        for x in fid._device_chunks(real, int(chunk), features):
+            sets.feed(0, features(x, "original"))
+        self.engine.generate(n, sampler, chunk=chunk, sink=lambda img, _first: sets.feed(1, features(img, "generated")))
+        return sets.results(k, n_subsets, subset_size, kid_seed)
+
+    def latent_match(self, iterator, n, mode="accurate-GM", method=None, k=3, n_subsets=100, subset_size=1000, seed=None):
+        """How well the aggregate posterior q(z) matches the prior p(z), measured on the codes themselves: n posterior codes (engine.sample_code over
+        ceil(n / batch) minibatches of `iterator`, truncated to n) are the "real" set, n prior codes (the sampler generate_images draws from,
+        sample(n)[0]) the "generated" one.  -> dict(kid_mean, kid_std, precision, recall, density): KID over n_subsets subsets of subset_size codes
+        (seeded with `seed`, 0 when None), precision = the share of prior codes inside a posterior k-NN ball, recall = the share of posterior codes
+        inside a prior ball.  Under data parallelism the statistic is taken over the CALLING rank's samples only: no collective is issued, and
+        ranks that call it get different values."""
+        from .. import two_sample as T
+        n = int(n)
+        T.check_k(k, n, n)
+        self.flush()
+        eng = self.engine
+        bank = None
+        while bank is None or bank.n < n:
+            z = eng.sample_code(iterator.next())
+            if bank is None:
+                bank = T.FeatureBank(eng.ctx, int(z.shape[1]))
+            bank.add(z[:n - bank.n])
+        _, sampler = self._prior_sampler(mode, method, seed)
+        prior = sampler.sample(n)[0]
+        kid_mean, kid_std, _ = T.kid(bank, prior, n_subsets=n_subsets, subset_size=subset_size, seed=0 if seed is None else int(seed))
+        pr = T.precision_recall(bank, prior, k=k)
+        return dict(kid_mean=kid_mean, kid_std=kid_std, precision=pr["precision"], recall=pr["recall"], density=pr["density"])
+
     def interpolate_paths(self, starts, ends, mode="accurate-GM", n_step=5, n_iter=500, decode=True, **kw):
         """Shortest-likely-path interpolation between P pairs of representations (latent-space-interpolation-mnist.ipynb cells 18-23) under
         the fitted mixture that `mode` names, as _prior_sampler picks it: "crude-GM" -> gm_params, any other mode -> gm_final_params.

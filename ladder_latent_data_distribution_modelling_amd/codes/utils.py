@@ -108,6 +108,17 @@ def compute_FID_score(data_file1, data_file2, FID_network, pooling_option, secon
     return fid.score_archives(data_file1, data_file2, FID_network, pooling_option, second_set, weights, chunk, input_size, device)
 
 
+def compute_sample_metrics(data_file1, data_file2, FID_network, pooling_option, second_set='generated', metrics=("fid", "kid", "pr"), weights=None,
+                           chunk=256, input_size=64, device="cuda:0", k=3, n_subsets=100, subset_size=1000, seed=0):
+    """compute_FID_score's two archives through the same VGG16 features ONCE, for any of the metrics "fid", "kid" (kernel inception distance: unbiased
+    MMD^2 with the cubic kernel over n_subsets subsets of subset_size rows, seeded) and "pr" (improved precision / recall and density on k-NN balls).
+    Prints the FID line of compute_FID_score and one line per further metric; -> dict (fid | kid_mean, kid_std, kid_per_subset | precision, recall,
+    density, counts_gen, counts_real).  Same refusals as compute_FID_score, "inception" included."""
+    from .. import fid
+    return fid.sample_metrics_archives(data_file1, data_file2, FID_network, pooling_option, second_set, weights, chunk, input_size, device, metrics, k,
+                                       n_subsets, subset_size, seed)
+
+
 def get_args():
     parser = argparse.ArgumentParser(description="LaDDer training on the MI355X HIP path")
     parser.add_argument("-c", "--config", metavar="C", default="None", help="The Configuration file")

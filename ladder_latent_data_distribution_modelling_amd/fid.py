@@ -12,6 +12,9 @@ D x D eigenproblems of the distance run on the host in numpy float64.
 imports torch and the library on first use.
 
     python3 fid.py --real a.npz --generated b.npz --weights vgg16.npz [--pooling avg|max|none] [--chunk 256]
+                   [--metrics fid,kid,pr] [--k 3] [--kid-subsets 100] [--kid-subset-size 1000] [--seed 0]
+
+`metrics_from_arrays` adds KID and precision / recall / density on the same features (two_sample.py): each set still goes through the network once.
 """
 import argparse
 
@@ -372,6 +375,56 @@ def fid_from_arrays(a, b, features, chunk=256, second_set="generated"):
     return frechet_distance(m1, c1, m2, c2)
 
 
+class MetricSets:
+    """What the metrics named in `metrics` (two_sample.METRICS) need of the two feature sets (0: real, 1: generated): a FrechetStats each for "fid", a
+    FeatureBank each for "kid" and "pr".  feed() never synchronises; results() copies to the host once per metric."""
+
+    def __init__(self, features, metrics):
+        from . import two_sample as T
+        self.metrics = T.check_metrics(metrics)
+        self.stats = [FrechetStats(features.ctx, features.D) for _ in range(2)] if "fid" in self.metrics else None
+        self.banks = [T.FeatureBank(features.ctx, features.D) for _ in range(2)] if set(self.metrics) - {"fid"} else None
+
+    def feed(self, which, f):
+        if self.stats is not None:
+            self.stats[which].update(f)
+        if self.banks is not None:
+            self.banks[which].add(f)
+
+    def results(self, k=3, n_subsets=100, subset_size=1000, seed=0):
+        """-> dict with  fid | kid_mean, kid_std, kid_per_subset | precision, recall, density, counts_gen, counts_real."""
+        from . import two_sample as T
+        out = {}
+        if "fid" in self.metrics:
+            (_, m1, c1), (_, m2, c2) = self.stats[0].moments(), self.stats[1].moments()
+            out["fid"] = frechet_distance(m1, c1, m2, c2)
+        if "kid" in self.metrics:
+            out["kid_mean"], out["kid_std"], out["kid_per_subset"] = T.kid(*self.banks, n_subsets=n_subsets, subset_size=subset_size, seed=seed)
+        if "pr" in self.metrics:
+            out.update(T.precision_recall(*self.banks, k=k))
+        return out
+
+
+def metrics_from_arrays(a, b, features, metrics=("fid",), chunk=256, second_set="generated", k=3, n_subsets=100, subset_size=1000, seed=0):
+    """The metrics named in `metrics` for two image sets, each sent through `features` ONCE (MetricSets).  "fid" is fid_from_arrays' value bit for bit
+    (same chunks, same updates); `k` is the neighbour rank of the precision / recall balls, n_subsets / subset_size / seed are KID's (two_sample.kid)."""
+    from . import two_sample as T
+    metrics = T.check_metrics(metrics)
+    chunk = int(chunk)
+    if chunk < 1:
+        raise ValueError("chunk >= 1 (got %d)" % chunk)
+    n, m = int(a.shape[0]), int(b.shape[0])
+    if "pr" in metrics:
+        T.check_k(k, n, m)
+    if "kid" in metrics and min(n, m, int(subset_size)) < 2:
+        raise ValueError("KID needs subsets of at least 2 rows (subset_size %d, %d and %d images)" % (subset_size, n, m))
+    sets = MetricSets(features, metrics)
+    for which, (arr, mode) in enumerate(((a, "original"), (b, "generated" if second_set == "generated" else "original"))):
+        for x in _device_chunks(arr, chunk, features):
+            sets.feed(which, features(x, mode))
+    return sets.results(k, n_subsets, subset_size, seed)
+
+
 def load_images(path_or_array):
     """The `sampled_images` array of an archive (codes/utils.py:142-143, 147-148), or the array itself."""
     if isinstance(path_or_array, (str, bytes)) or hasattr(path_or_array, "__fspath__"):
@@ -391,15 +444,29 @@ def parse_args(argv=None):
                     help="preprocessing of the second archive (default: 'original' for uint8 bytes, 'generated' for floats)")
     ap.add_argument("--input-size", type=int, default=64)
     ap.add_argument("--device", default="cuda:0")
+    ap.add_argument("--metrics", default="fid", help="comma-separated: fid, kid (kernel inception distance), pr (precision / recall / density)")
+    ap.add_argument("--k", type=int, default=3, help="neighbour rank of the precision / recall balls")
+    ap.add_argument("--kid-subsets", type=int, default=100)
+    ap.add_argument("--kid-subset-size", type=int, default=1000)
+    ap.add_argument("--seed", type=int, default=0, help="seed of the KID subsets")
     a = ap.parse_args(argv)
     if a.chunk < 1:
         ap.error("--chunk must be >= 1")
+    from . import two_sample as T
+    try:
+        a.metrics = T.check_metrics(a.metrics)
+    except ValueError as e:
+        ap.error(str(e))
     return a
 
 
-def score_archives(data_file1, data_file2, FID_network, pooling_option, second_set, weights, chunk, input_size, device):
-    """compute_FID_score (codes/utils.py) behind its argument checks.  second_set None: decided from the second array's dtype (second_set_for).  Each
-    archive is opened once, the weights are validated once, both before the device is touched."""
+def sample_metrics_archives(data_file1, data_file2, FID_network, pooling_option, second_set, weights, chunk, input_size, device,
+                            metrics=("fid", "kid", "pr"), k=3, n_subsets=100, subset_size=1000, seed=0):
+    """compute_sample_metrics (codes/utils.py) behind its argument checks.  second_set None: decided from the second array's dtype (second_set_for).
+    Each archive is opened once, the weights are validated once, both before the device is touched.  Prints the FID line of the reference, then one
+    line per further metric.  -> the dict of metrics_from_arrays."""
+    from . import two_sample as T
+    metrics = T.check_metrics(metrics)
     check_network(FID_network)
     pooling = check_pooling(pooling_option)
     input_hw(input_size)
@@ -408,16 +475,32 @@ def score_archives(data_file1, data_file2, FID_network, pooling_option, second_s
     second_set, note = second_set_for(b, second_set)
     if note:
         print("fid.py: " + note)
+    if "pr" in metrics:
+        T.check_k(k, int(a.shape[0]), int(b.shape[0]))
     from .layers import Ctx
     features = VGG16Features(Ctx(device), values, pooling, input_size)
-    score = fid_from_arrays(a, b, features, chunk=chunk, second_set=second_set)
-    print("FID score between {} and {} is:\n{}".format(data_file1, data_file2, score))
-    return score
+    out = metrics_from_arrays(a, b, features, metrics, chunk, second_set, k, n_subsets, subset_size, seed)
+    if "fid" in metrics:
+        print("FID score between {} and {} is:\n{}".format(data_file1, data_file2, out["fid"]))
+    if "kid" in metrics:
+        print("KID between {} and {} ({} subsets of {}) is:\n{} +- {}".format(data_file1, data_file2, len(out["kid_per_subset"]),
+                                                                              min(subset_size, int(a.shape[0]), int(b.shape[0])), out["kid_mean"], out["kid_std"]))
+    if "pr" in metrics:
+        print("Precision / recall / density (k = {}) between {} and {} are:\n{} / {} / {}".format(k, data_file1, data_file2, out["precision"], out["recall"],
+                                                                                                   out["density"]))
+    return out
+
+
+def score_archives(data_file1, data_file2, FID_network, pooling_option, second_set, weights, chunk, input_size, device):
+    """compute_FID_score (codes/utils.py): sample_metrics_archives for "fid" alone -> the score."""
+    return sample_metrics_archives(data_file1, data_file2, FID_network, pooling_option, second_set, weights, chunk, input_size, device, ("fid",))["fid"]
 
 
 def main(argv=None):
     a = parse_args(argv)
-    return score_archives(a.real, a.generated, "VGG", a.pooling, a.second_set, a.weights, a.chunk, a.input_size, a.device)
+    out = sample_metrics_archives(a.real, a.generated, "VGG", a.pooling, a.second_set, a.weights, a.chunk, a.input_size, a.device, a.metrics, a.k,
+                                  a.kid_subsets, a.kid_subset_size, a.seed)
+    return out["fid"] if a.metrics == ("fid",) else out
 
 
 if __name__ == "__main__":
