@@ -1108,6 +1108,44 @@ int ladder_pairs_ball_counts(const float* q, const double* norms_q, int m, const
 int ladder_pairs_poly_sums(const float* x, int sx, const float* y, int sy, int n_blocks, int D, int degree, double gamma, double coef0, double* sums,
                            void* ws, size_t ws_bytes, ladder_stream_t stream);
 
+/* ---------------------------------------------------------------- N25: importance-weighted marginal log-likelihood (csrc/iwll.hip)
+ * log p(x) ~ log (1/S) sum_s w_s, the number the baselines of the reference are compared by (Tomczak & Welling 2018, S = 5 000; Burda et al. 2016).
+ * The reference only ever evaluates the ELBO of test_step (codes/base.py:944-986); these exports restate its densities PER ROW, in float64:
+ *   ladder_iw_sample_rows   codes/models.py:97-103 / codes/base.py:164-167 (sample = mean + std_dev * eps) and the log-density of that draw under q.
+ *   ladder_iw_laplace_rows  codes/base.py:383-396 (define_loss): -sum_d |x_d - xhat_d| / sigma - D log(2 sigma), sigma a fixed number of the call.
+ *   ladder_iw_gauss_rows    codes/base.py:286-297, 350-353: -sum (a - b)^2 / (2 s^2) - W log s - W/2 log 2pi (b = NULL: zeros; s = 1: standard normal).
+ *   ladder_diag_mixture_logprob_rows   codes/base.py:216-254, 361-370: log (1/K) sum_k N(z; m_k, diag s_k^2) per row, max-subtracted; the component arithmetic
+ *                           of ladder_diag_mixture_wide_fwd_bwd (u = (z - m_k) / s_k formed directly, 1/s_k and sum log s_k prepared once per call), fp32.
+ * Rows are image-major: row r = b * C + c is sample c of image b of the current chunk; `per` = rows per parent row (z level: C, t level: 1), n % per == 0.
+ *   sample_rows: mu, sd [n/per, W], eps [n, W] -> sample [n, W] = fmaf(sd, eps, mu) in fp32 (the bits of ladder_latent_fwd's z), logq [n] float64 =
+ *     -1/2 sum eps^2 - sum log sd - W/2 log 2pi.
+ *   laplace_rows: x [n/per, D], xhat [n, D] -> out [n] float64.  One workgroup per row from 256 rows on; below, a (row, slice) grid writes float64 partials
+ *     into `ws` and a second launch adds them in slice order (ws >= ladder_iw_laplace_rows_workspace_bytes(n, D); 0 and ws = NULL when one slice is enough).
+ *     16-byte loads when D % 4 == 0 and both arrays sit on 16 bytes, scalar loads otherwise.
+ *   randn_rows: out [B * C, W] standard normals; element (image0 + b, sample0 + c, j) of `level` (0 .. 15) draws from its own Philox4x32-10 counter under
+ *     `seed`: the draws of a sample do not depend on B, C or the order of the calls.
+ *   add_term: logw[i] = (init ? 0 : logw[i]) + sign * term[i], term fp32 (term_is_f32) or float64.
+ *   accumulate: logw [B * C] float64 -> state [B, 5] float64 = { running maximum M, sum exp(logw - M), sum exp(2 (logw - M)), sum logw, count }, updated
+ *     chunk after chunk; one wavefront per image.  A -inf log-weight adds 0; a state row whose count is 0 is empty whatever else it holds.
+ *   finish: out [B, 4] float64 = { log_px = M + log sum - log S, elbo_1 = mean logw, ess = (sum w)^2 / sum w^2, S }; an image whose weights are all 0 gets
+ *     log_px = -inf and ess = 0, an empty row NaN with S = 0.
+ * Differences, squares and sums are formed in float64 from the fp32 inputs; every sum has one fixed order (no atomics): two calls give the same bits.
+ * Limits: 1 <= n, B * C <= 2^24; 1 <= W <= 65536; 1 <= D <= 2^22; diag rows 1 <= Z <= 256, 1 <= K <= 1024; sigma, s finite and > 0.  LADDER_E_SHAPE outside
+ * them and for a NULL array (b and an unneeded ws excepted), LADDER_E_ALIGN for a float64 array off 8 bytes, LADDER_E_WORKSPACE for a NULL or short workspace;
+ * a refused call launches nothing.  No allocation, no synchronisation, capturable. */
+int ladder_iw_randn_rows(float* out, int B, int C, int W, uint64_t image0, uint64_t sample0, uint64_t seed, int level, ladder_stream_t stream);
+int ladder_iw_sample_rows(const float* mu, const float* sd, const float* eps, int n, int per, int W, float* sample, double* logq, ladder_stream_t stream);
+size_t ladder_iw_laplace_rows_workspace_bytes(int n, int D);
+int ladder_iw_laplace_rows(const float* x, const float* xhat, int n, int per, int D, double sigma, double* out, void* ws, size_t ws_bytes,
+                           ladder_stream_t stream);
+int ladder_iw_gauss_rows(const float* a, const float* b, double s, int n, int W, double* out, ladder_stream_t stream);
+size_t ladder_diag_mixture_logprob_rows_workspace_bytes(int n, int Z, int K);
+int ladder_diag_mixture_logprob_rows(const float* z, const float* comp_mean, const float* comp_sd, int n, int Z, int K, float* logp, void* ws,
+                                     size_t ws_bytes, ladder_stream_t stream);
+int ladder_iw_add_term(const void* term, int term_is_f32, double sign, int n, int init, double* logw, ladder_stream_t stream);
+int ladder_iw_accumulate(const double* logw, int B, int C, double* state, ladder_stream_t stream);
+int ladder_iw_finish(const double* state, int B, double* out, ladder_stream_t stream);
+
 /* ---------------------------------------------------------------- helpers */
 /* HOST function (no device work): CRC-32C (Castagnoli) of host memory, crc = 0 to start, chainable.  Used by the
  * tf.train.Saver checkpoint-v2 reader/writer (codes/base.py:37-85: saver_ae / saver_prior) for block and tensor checksums. */

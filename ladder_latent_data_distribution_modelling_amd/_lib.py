@@ -285,6 +285,16 @@ PROTOTYPES = {
     "ladder_pairs_knn_radii": (_i, [_p, _p, _i, _i, _p, _i, _p, _p, _z, _p]),
     "ladder_pairs_ball_counts": (_i, [_p, _p, _i, _p, _p, _p, _i, _i, _p, _p, _p, _z, _p]),
     "ladder_pairs_poly_sums": (_i, [_p, _i, _p, _i, _i, _i, _i, _d, _d, _p, _p, _z, _p]),
+    "ladder_iw_randn_rows": (_i, [_p, _i, _i, _i, _u64, _u64, _u64, _i, _p]),
+    "ladder_iw_sample_rows": (_i, [_p, _p, _p, _i, _i, _i, _p, _p, _p]),
+    "ladder_iw_laplace_rows_workspace_bytes": (_z, [_i, _i]),
+    "ladder_iw_laplace_rows": (_i, [_p, _p, _i, _i, _i, _d, _p, _p, _z, _p]),
+    "ladder_iw_gauss_rows": (_i, [_p, _p, _d, _i, _i, _p, _p]),
+    "ladder_diag_mixture_logprob_rows_workspace_bytes": (_z, [_i, _i, _i]),
+    "ladder_diag_mixture_logprob_rows": (_i, [_p, _p, _p, _i, _i, _i, _p, _p, _z, _p]),
+    "ladder_iw_add_term": (_i, [_p, _i, _d, _i, _i, _p, _p]),
+    "ladder_iw_accumulate": (_i, [_p, _i, _i, _p, _p]),
+    "ladder_iw_finish": (_i, [_p, _i, _p, _p]),
 }
 
 _lib = None

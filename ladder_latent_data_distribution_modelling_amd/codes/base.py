@@ -544,6 +544,31 @@ class BaseTrain_joint(BaseTrain):
         pr = T.precision_recall(bank, prior, k=k)
         return dict(kid_mean=kid_mean, kid_std=kid_std, precision=pr["precision"], recall=pr["recall"], density=pr["density"])
 
+    def estimate_log_likelihood(self, data, n_samples=5000, mode="accurate-GM", sigma=None, rows=128, seed=None, max_images=None):
+        """Importance-weighted estimate of the marginal log-likelihood log p(x) ~ log (1/S) sum_s w_s of held-out images, S = n_samples draws from the
+        encoder per image (log_likelihood.ImportanceEstimator; the number the VampPrior / hierarchical / GMM baselines are compared by).  `data`: an
+        array [N, H, W, C] or one of the trainer's iterators (then `max_images` is required).  The priors "ours" and "GMM" are evaluated under the fitted
+        mixture that `mode` names, as _prior_sampler picks it.  `sigma`: the pixel-likelihood scale, ONE number for the whole call (default
+        |sigma/Variable|), never test_step's batch-dependent maximum with the mean pixel error.  -> dict (log_px, elbo_1, ess per image; mean_log_px,
+        stderr_log_px, mean_elbo_1, mean_ess, n_samples, n_images, sigma), also saved as <result_dir>log_likelihood_<mode>.npz."""
+        from .. import log_likelihood as LL
+        LL.check_counts(n_samples, rows)
+        if not hasattr(data, "next") and np.ndim(data) != 4:
+            raise ValueError("estimate_log_likelihood: data must be an array [N, H, W, C] or an iterator (got shape %s)" % (np.shape(data),))
+        if hasattr(data, "next") and (max_images is None or int(max_images) < 1):
+            raise ValueError("estimate_log_likelihood: an iterator has no end, pass max_images >= 1")
+        prior, mixture = self.config["prior"], None
+        if prior in LL.FULL_MIXTURE_PRIORS:
+            mixture = self.gm_params if mode == "crude-GM" else getattr(self, "gm_final_params", None)
+            if mixture is None:
+                raise LL.mixture_missing(prior, mode)
+        self.flush()
+        self._enc_batch = None          # this call overwrites the engine's encoder cache with other batches
+        est = LL.ImportanceEstimator(self.engine, mixture, sigma=sigma, seed=self.cur_epoch if seed is None else int(seed))
+        res = est.estimate(data, n_samples=n_samples, rows=rows, max_images=max_images)
+        np.savez("{}log_likelihood_{}.npz".format(self.config["result_dir"], mode), **res)
+        return res
+
     def interpolate_paths(self, starts, ends, mode="accurate-GM", n_step=5, n_iter=500, decode=True, **kw):
         """Shortest-likely-path interpolation between P pairs of representations (latent-space-interpolation-mnist.ipynb cells 18-23) under
         the fitted mixture that `mode` names, as _prior_sampler picks it: "crude-GM" -> gm_params, any other mode -> gm_final_params.

@@ -119,6 +119,14 @@ def compute_sample_metrics(data_file1, data_file2, FID_network, pooling_option, 
                                        n_subsets, subset_size, seed)
 
 
+def compute_log_likelihood(config_file, n_samples=5000, images=None, max_images=None, rows=128, sigma=None, gm=None, seed=0, batch_size=None):
+    """Importance-weighted marginal log-likelihood of a trained model on held-out images (evaluate.py's work as a function): restores the checkpoints the
+    config names, reads the fitted mixture of the priors "ours" / "GMM" from <result_dir>GM_prior_info.npz (or `gm`), takes the images from the archive
+    `images` (first array; uint8 is scaled by 1/255) or the config's test split, and returns ImportanceEstimator.estimate's dict."""
+    from .. import evaluate
+    return evaluate.run(config_file, n_samples, images, max_images, rows, sigma, gm, seed, batch_size)
+
+
 def get_args():
     parser = argparse.ArgumentParser(description="LaDDer training on the MI355X HIP path")
     parser.add_argument("-c", "--config", metavar="C", default="None", help="The Configuration file")

@@ -17,14 +17,13 @@
 //   reduce x2, sum   fixed-order sums of the partials (four interleaved running sums per element, combined as (0+1)+(2+3)).
 //
 // No floating-point atomics, no grid-wide synchronisation, no [S,K,Z] array; every partial that is read was written by the same call.
-#include "common.h"
+#include "diag_mixture_common.h"   // prepare kernel + component arithmetic, shared with csrc/iwll.hip
 
 namespace {
 constexpr int DW_NS = 4;                        // samples per wavefront of the resp launch
 constexpr int DW_KC = 16;                       // components per workgroup of the accumulate launch
 constexpr int DW_SLICES = 256;                  // sample slices of the accumulate launch: one per CU
 constexpr size_t DW_PART_BYTES = (size_t)64 << 20;   // cap on the slices' [K,Z] partial pairs (K = 1024, Z = 256: 32 slices)
-constexpr float kHalfLog2Pi = 0.91893853320467274f;
 
 // How a shape is cut up, and where its pieces sit in the (256-byte aligned) workspace.  The query and the launch both come through here.
 struct DwPlan {
@@ -66,20 +65,6 @@ DwPlan dw_plan(int L, int B, int Z, int K) {
   return p;
 }
 
-__global__ __launch_bounds__(64) void dw_prepare_kernel(const float* __restrict__ cm, const float* __restrict__ cs, int Z, int K,
-                                                        float* __restrict__ m, float* __restrict__ is, float* __restrict__ c) {
-  const int k = blockIdx.x, lane = threadIdx.x;
-  float ls = 0.f;
-  for (int z = lane; z < Z; z += 64) {
-    const float s = cs[(size_t)k * Z + z];
-    m[(size_t)k * Z + z] = cm[(size_t)k * Z + z];
-    is[(size_t)k * Z + z] = 1.f / s;
-    ls += logf(s);
-  }
-  ls = wave_sum(ls);
-  if (lane == 0) c[k] = -ls - (float)Z * kHalfLog2Pi - logf((float)K);
-}
-
 __global__ __launch_bounds__(256) void dw_resp_kernel(const float* __restrict__ mu, const float* __restrict__ sd, const float* __restrict__ eps,
                                                       const float* __restrict__ m, const float* __restrict__ is, const float* __restrict__ c,
                                                       long S, int B, int Z, int K, int Kp, float* r, double* __restrict__ blk_lp) {
@@ -111,9 +96,7 @@ __global__ __launch_bounds__(256) void dw_resp_kernel(const float* __restrict__ 
       const float ck = c[kc + kk];
 #pragma unroll
       for (int i = 0; i < DW_NS; ++i) {
-        const float u0 = (t[i][0] - mv.x) * iv.x, u1 = (t[i][1] - mv.y) * iv.y, u2 = (t[i][2] - mv.z) * iv.z, u3 = (t[i][3] - mv.w) * iv.w;
-        const float q = wave_sum((u0 * u0 + u1 * u1) + (u2 * u2 + u3 * u3));
-        const float v = fmaf(-0.5f, q, ck);
+        const float v = dw_component_logp(dw_quad_partial(t[i], mv, iv), ck);
         if (lane == kk) mine[i] = v;
       }
     }
@@ -254,7 +237,7 @@ int ladder_diag_mixture_wide_fwd_bwd(const float* mu, const float* sd, const flo
   const long S = (long)L * B;
   const size_t KZ = (size_t)K * Z, BZ = (size_t)B * Z;
   const int slices = p.nbg * p.lsplit;
-  hipLaunchKernelGGL(dw_prepare_kernel, dim3(K), dim3(64), 0, stream, comp_mean, comp_sd, Z, K, m, is, c);
+  hipLaunchKernelGGL(dw_prepare_kernel, dim3(K), dim3(64), 0, stream, comp_mean, comp_sd, Z, Z, K, m, is, c);
   hipLaunchKernelGGL(dw_resp_kernel, dim3(p.nblk), dim3(256), 0, stream, mu, sd, eps, (const float*)m, (const float*)is, (const float*)c, S, B, Z, K,
                      p.kp, r, blk_lp);
   hipLaunchKernelGGL(dw_accum_kernel, dim3(slices, p.nkc), dim3((Z + 63) / 64 * 64), 0, stream, mu, sd, eps, (const float*)m, (const float*)is,
