@@ -733,29 +733,34 @@ int ladder_gmm_dense_logprob_fwd_bwd(const float* mu, const float* sd, const flo
 int ladder_gmm_dense_logprob_rows(const float* t, const float* params, int n, int R, int K, float* logp, void* ws, size_t ws_bytes,
                                   ladder_stream_t stream);
 
-/* ---- VampPrior (codes/base.py:216-254, 361-370): equally weighted mixture of K DIAGONAL Gaussians on z (Z <= 64) whose
- * components (comp_mean, comp_sd [K,Z]) are the encoder's outputs on the trainable pseudo-inputs.  sum_logp = sum over the L*B MC
- * samples of log p(z); dmu/dsd as in ladder_gmm_logprob_fwd_bwd; dcomp_mean/dcomp_sd [K,Z] = sum over samples of
- * dlog p/d comp_mean, dlog p/d comp_sd (fixed-order reduction) -- the gradient entering the pseudo-input encoder pass. */
+/* ---- diagonal mixture (csrc/diag_mixture.hip): the VampPrior (codes/base.py:216-254, 361-370), the equally weighted mixture of K DIAGONAL Gaussians on z
+ * whose components (comp_mean, comp_sd [K,Z]) are the encoder's outputs on the trainable pseudo-inputs.
+ *   ladder_diag_mixture_fwd_bwd        the term of crossEntropy_prior on a NARROW code: 1 <= Z <= 64, L, B, K >= 1 with (8 K Z + 4 K) floats within 150 KB of LDS.
+ *   ladder_diag_mixture_wide_fwd_bwd   the same term on a WIDE code (the shipped codes/celeba_config.json width): 80 <= Z <= 256 with Z % 16 == 0 (the widths of
+ *                                      ladder_mixture_sample_wide_prepare_diag), 1 <= K <= 1024, L, B >= 1, L*B <= 2^30.
+ *   ladder_diag_mixture_logprob_rows   log p(z_i) of n separate points z [n,Z] -> logp [n] (the log p(z) of the importance-weighted estimate, N25):
+ *                                      1 <= n <= 2^24, 1 <= Z <= 256, 1 <= K <= 1024; every array non-NULL.
+ * The two terms take the same arguments and give the same outputs and signs: mu, sd [B,Z], eps [L,B,Z]; with t = mu[b] + sd[b] * eps[l,b],
+ *   sum_logp = sum_{l,b} log (1/K) sum_k N(t; m_k, diag(s_k^2));  dmu, dsd [B,Z] as in ladder_gmm_logprob_fwd_bwd;  dcomp_mean, dcomp_sd [K,Z] = sum over
+ *   the L*B samples of dlog p/d comp_mean, dlog p/d comp_sd -- the gradient entering the pseudo-input encoder pass.
+ * The wide term and the rows form u = (t - m_k) / s_k directly with 1/s_k and sum log s_k prepared once per call, and the log-sum-exp is max-subtracted (a
+ * component of responsibility 0 gets an exactly zero gradient); the narrow term divides and uses the fast exp / log.  Every sum has one fixed order (no
+ * atomics): two calls on the same inputs give the same bits whatever `ws` held before.  Launches of the wide term: prepare, responsibilities r [L*B, K]
+ * (+ float64 log-prob partials), accumulate on a (sample slice, 16 components) grid, three fixed-order reductions; of the rows: prepare, one row kernel.
+ * No allocation, no synchronisation, capturable.  `ws` >= the entry's own query (the narrow one takes no L; the wide and the rows query answer 0 outside
+ * their shapes; the wide workspace holds r, at most 64 MB of per-slice [K,Z] partials and the per-l-range [B,Z] partials, never an [L*B, K, Z] array); any
+ * alignment.  LADDER_E_SHAPE outside the shapes above, LADDER_E_WORKSPACE for a NULL or short workspace; a refused call launches nothing. */
 size_t ladder_diag_mixture_workspace_bytes(int B, int Z, int K);
 int ladder_diag_mixture_fwd_bwd(const float* mu, const float* sd, const float* eps, const float* comp_mean, const float* comp_sd,
                                 int L, int B, int Z, int K, float* sum_logp, float* dmu, float* dsd, float* dcomp_mean,
                                 float* dcomp_sd, void* ws, size_t ws_bytes, ladder_stream_t stream);
-
-/* ---- the same term on a WIDE code (codes/base.py:216-254, 361-370 at the shipped codes/celeba_config.json width; csrc/diag_mixture_wide.hip):
- * 80 <= Z <= 256 with Z % 16 == 0 (the widths of ladder_mixture_sample_wide_prepare_diag), 1 <= K <= 1024, L, B >= 1, L*B <= 2^30.  Arguments, outputs
- * and signs are those of ladder_diag_mixture_fwd_bwd, which keeps Z <= 64: with t = mu[b] + sd[b] * eps[l,b],
- *   sum_logp = sum_{l,b} log (1/K) sum_k N(t; m_k, diag(s_k^2));  dmu, dsd [B,Z];  dcomp_mean, dcomp_sd [K,Z] summed over the L*B samples.
- * u = (t - m_k) / s_k is formed directly with 1/s_k prepared once per call, the log-sum-exp is max-subtracted (a component of responsibility 0 gets an
- * exactly zero gradient), every sum has one fixed order (no atomics): two calls on the same inputs give the same bits whatever `ws` held before.
- * Launches: prepare, responsibilities r [L*B, K] (+ float64 log-prob partials), accumulate on a (sample slice, 16 components) grid, three fixed-order
- * reductions.  No allocation, no synchronisation, capturable.  `ws` >= ladder_diag_mixture_wide_workspace_bytes(L, B, Z, K) (0 outside the shapes above;
- * it holds r, at most 64 MB of per-slice [K,Z] partials and the per-l-range [B,Z] partials, never an [L*B, K, Z] array); any alignment.
- * LADDER_E_SHAPE outside the shapes above, LADDER_E_WORKSPACE for a NULL or short workspace; a refused call launches nothing. */
 size_t ladder_diag_mixture_wide_workspace_bytes(int L, int B, int Z, int K);
 int ladder_diag_mixture_wide_fwd_bwd(const float* mu, const float* sd, const float* eps, const float* comp_mean, const float* comp_sd,
                                      int L, int B, int Z, int K, float* sum_logp, float* dmu, float* dsd, float* dcomp_mean,
                                      float* dcomp_sd, void* ws, size_t ws_bytes, ladder_stream_t stream);
+size_t ladder_diag_mixture_logprob_rows_workspace_bytes(int n, int Z, int K);
+int ladder_diag_mixture_logprob_rows(const float* z, const float* comp_mean, const float* comp_sd, int n, int Z, int K, float* logp, void* ws,
+                                     size_t ws_bytes, ladder_stream_t stream);
 
 /* ---------------------------------------------------------------- N14: minibatch assembly (the input pipeline)
  * models.py:354-371 (CelebA: uint8 HWC pixels * 1/255), data_loader.py:19-33 (MNIST floats), shuffle + batch of models.py:33-40:
@@ -1114,8 +1119,7 @@ int ladder_pairs_poly_sums(const float* x, int sx, const float* y, int sy, int n
  *   ladder_iw_sample_rows   codes/models.py:97-103 / codes/base.py:164-167 (sample = mean + std_dev * eps) and the log-density of that draw under q.
  *   ladder_iw_laplace_rows  codes/base.py:383-396 (define_loss): -sum_d |x_d - xhat_d| / sigma - D log(2 sigma), sigma a fixed number of the call.
  *   ladder_iw_gauss_rows    codes/base.py:286-297, 350-353: -sum (a - b)^2 / (2 s^2) - W log s - W/2 log 2pi (b = NULL: zeros; s = 1: standard normal).
- *   ladder_diag_mixture_logprob_rows   codes/base.py:216-254, 361-370: log (1/K) sum_k N(z; m_k, diag s_k^2) per row, max-subtracted; the component arithmetic
- *                           of ladder_diag_mixture_wide_fwd_bwd (u = (z - m_k) / s_k formed directly, 1/s_k and sum log s_k prepared once per call), fp32.
+ * (log p(z) of the VampPrior, codes/base.py:216-254, 361-370, is ladder_diag_mixture_logprob_rows in the diagonal-mixture section above: fp32 rows.)
  * Rows are image-major: row r = b * C + c is sample c of image b of the current chunk; `per` = rows per parent row (z level: C, t level: 1), n % per == 0.
  *   sample_rows: mu, sd [n/per, W], eps [n, W] -> sample [n, W] = fmaf(sd, eps, mu) in fp32 (the bits of ladder_latent_fwd's z), logq [n] float64 =
  *     -1/2 sum eps^2 - sum log sd - W/2 log 2pi.
@@ -1130,7 +1134,7 @@ int ladder_pairs_poly_sums(const float* x, int sx, const float* y, int sy, int n
  *   finish: out [B, 4] float64 = { log_px = M + log sum - log S, elbo_1 = mean logw, ess = (sum w)^2 / sum w^2, S }; an image whose weights are all 0 gets
  *     log_px = -inf and ess = 0, an empty row NaN with S = 0.
  * Differences, squares and sums are formed in float64 from the fp32 inputs; every sum has one fixed order (no atomics): two calls give the same bits.
- * Limits: 1 <= n, B * C <= 2^24; 1 <= W <= 65536; 1 <= D <= 2^22; diag rows 1 <= Z <= 256, 1 <= K <= 1024; sigma, s finite and > 0.  LADDER_E_SHAPE outside
+ * Limits: 1 <= n, B * C <= 2^24; 1 <= W <= 65536; 1 <= D <= 2^22; sigma, s finite and > 0.  LADDER_E_SHAPE outside
  * them and for a NULL array (b and an unneeded ws excepted), LADDER_E_ALIGN for a float64 array off 8 bytes, LADDER_E_WORKSPACE for a NULL or short workspace;
  * a refused call launches nothing.  No allocation, no synchronisation, capturable. */
 int ladder_iw_randn_rows(float* out, int B, int C, int W, uint64_t image0, uint64_t sample0, uint64_t seed, int level, ladder_stream_t stream);
@@ -1139,9 +1143,6 @@ size_t ladder_iw_laplace_rows_workspace_bytes(int n, int D);
 int ladder_iw_laplace_rows(const float* x, const float* xhat, int n, int per, int D, double sigma, double* out, void* ws, size_t ws_bytes,
                            ladder_stream_t stream);
 int ladder_iw_gauss_rows(const float* a, const float* b, double s, int n, int W, double* out, ladder_stream_t stream);
-size_t ladder_diag_mixture_logprob_rows_workspace_bytes(int n, int Z, int K);
-int ladder_diag_mixture_logprob_rows(const float* z, const float* comp_mean, const float* comp_sd, int n, int Z, int K, float* logp, void* ws,
-                                     size_t ws_bytes, ladder_stream_t stream);
 int ladder_iw_add_term(const void* term, int term_is_f32, double sign, int n, int init, double* logw, ladder_stream_t stream);
 int ladder_iw_accumulate(const double* logw, int B, int C, double* state, ladder_stream_t stream);
 int ladder_iw_finish(const double* state, int B, double* out, ladder_stream_t stream);

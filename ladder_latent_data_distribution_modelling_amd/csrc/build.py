@@ -12,7 +12,7 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
-SOURCES = ["igemm.hip", "igemm_wgrad.hip", "igemm_split.hip", "convdirect.hip", "convsplit.hip", "convf32.hip", "convf32s.hip", "upproj.hip", "densef32.hip", "densesplit.hip", "convrgb.hip", "norm.hip", "elbo.hip", "mixture.hip", "mixture_wide.hip", "diag_mixture_wide.hip", "hostutil.hip", "vbgmm.hip", "sample.hip", "slp.hip", "slp_wide.hip", "fid.hip", "emgmm.hip", "emgmm_wide.hip", "kmeans.hip", "kmeans_wide.hip", "twosample.hip", "iwll.hip"]
+SOURCES = ["igemm.hip", "igemm_wgrad.hip", "igemm_split.hip", "convdirect.hip", "convsplit.hip", "convf32.hip", "convf32s.hip", "upproj.hip", "densef32.hip", "densesplit.hip", "convrgb.hip", "norm.hip", "elbo.hip", "mixture.hip", "mixture_wide.hip", "diag_mixture.hip", "hostutil.hip", "vbgmm.hip", "sample.hip", "slp.hip", "slp_wide.hip", "fid.hip", "emgmm.hip", "emgmm_wide.hip", "kmeans.hip", "kmeans_wide.hip", "twosample.hip", "iwll.hip"]
 LIB = os.path.join(HERE, "libladder_hip.so")
 
 

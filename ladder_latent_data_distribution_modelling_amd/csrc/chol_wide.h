@@ -25,7 +25,7 @@ inline size_t cw_workspace_bytes(int K, int R) {
   if (K < 1 || !cw_width_ok(R)) return 0;
   return (size_t)cw_slots(K) * R * R * sizeof(double) + 256;
 }
-inline double* cw_workspace_base(void* ws) { return reinterpret_cast<double*>((reinterpret_cast<uintptr_t>(ws) + 255) & ~(uintptr_t)255); }
+inline double* cw_workspace_base(void* ws) { return reinterpret_cast<double*>(ladder_align256(ws)); }
 
 // LDS of one factorisation (static, 43 KB)
 struct CwShared {

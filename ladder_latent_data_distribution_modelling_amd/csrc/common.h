@@ -34,6 +34,10 @@
   }
 
 static inline bool ladder_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+// Workspaces are carved in 256-byte units: a piece's size rounded up, and the caller's pointer moved up to the first boundary (a workspace query adds
+// 256 bytes for that move).
+static inline size_t ladder_round256(size_t n) { return (n + 255) & ~(size_t)255; }
+static inline char* ladder_align256(void* ws) { return reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(ws) + 255) & ~(uintptr_t)255); }
 
 __device__ __forceinline__ float ladder_act_fn(float v, int act) {
   switch (act) {
@@ -68,6 +72,21 @@ __device__ __forceinline__ double wave_sum_d(double v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
+}
+__device__ __forceinline__ double wave_max_d(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
+  return v;
+}
+
+// out[0] = the sum of the n float64 partials of a mixture term's log-probabilities, by ONE wavefront: lane-strided partial sums, then a fixed-order
+// shuffle tree.  (A template so that only the files that launch it hold a copy; they launch sum_doubles_kernel<float>.)
+template <typename T>
+__global__ __launch_bounds__(64) void sum_doubles_kernel(const double* __restrict__ part, int n, T* __restrict__ out) {
+  double s = 0.0;
+  for (int i = threadIdx.x; i < n; i += 64) s += part[i];
+  s = wave_sum_d(s);
+  if (threadIdx.x == 0) out[0] = (T)s;
 }
 
 // Bijective XCD-aware remap: hardware places block b on XCD b%8; give every XCD a contiguous

@@ -1,6 +1,6 @@
 // ELBO-side kernels of the LaDDer path for gfx950: latent blocks, pixel reductions, the scalar algebra of define_loss
 // (codes/base.py:257-413) evaluated ON DEVICE so the step never syncs with the host, fused clip+Adam, and a Philox normal
-// generator.  The mixture terms of the priors are in csrc/mixture.hip.
+// generator.  The mixture terms of the priors are in csrc/mixture.hip and csrc/diag_mixture.hip.
 #include "common.h"
 #include "gmm_packed.h"   // kLog2Pi
 #include "philox.h"

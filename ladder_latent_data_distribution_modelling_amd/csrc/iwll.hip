@@ -7,15 +7,13 @@
 //   laplace_rows    log p(x|z) = -sum_d |x_d - xhat_d| / sigma - D log(2 sigma) (define_loss, codes/base.py:383-396).  A workgroup per row when the rows fill
 //                   the chip, else a (row, slice) grid whose float64 partials a second launch adds in slice order.
 //   gauss_rows      -sum (a - b)^2 / (2 s^2) - W log s - W/2 log 2pi.
-//   diag rows       log (1/K) sum_k N(z; m_k, diag s_k^2): the arithmetic of the responsibilities pass of csrc/diag_mixture_wide.hip (diag_mixture_common.h),
-//                   for any 1 <= Z <= 256 -- the prepared rows are padded to whole 16-byte groups.
 //   add_term        logw (+)= sign * term, term fp32 or float64.
 //   accumulate / finish   per image: running maximum M, sum exp(logw - M), sum exp(2 (logw - M)), sum logw, count -> log_px, elbo_1, ess, S.
 //
 // Row values are float64: at 49 152 pixels log p(x|z) is of order 1e4 - 1e5 and differences of order 1 between samples decide the estimate.  Inputs are the
 // engine's fp32 tensors; differences, squares and sums are formed in float64.  Every sum has one fixed order (lane-strided partial sums, a shuffle tree, the
 // wavefronts of a workgroup in index order): no atomics, two calls on the same inputs give the same bits.
-#include "diag_mixture_common.h"
+#include "common.h"
 #include "philox.h"
 
 namespace {
@@ -24,17 +22,8 @@ constexpr int IW_CUS = 256;                    // a row per workgroup fills the 
 constexpr int IW_SLICE_FLOATS = 1024;          // granularity of a slice of a row: whole 16-byte groups for every thread of the workgroup
 constexpr int IW_MAX_SLICES = 64;              // the second pass adds a row's partials with one wavefront
 constexpr int IW_MAX_D = 1 << 22, IW_MAX_W = 1 << 16, IW_MAX_ROWS = 1 << 24;
-constexpr int DM_NS = 4;                       // rows per wavefront of the diagonal-mixture launch
-constexpr int DM_MAX_K = 1024, DM_MAX_Z = 256;
 
-size_t iw_align(size_t n) { return (n + 255) & ~(size_t)255; }
 bool iw_aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
-
-__device__ __forceinline__ double wave_max_d(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-  return v;
-}
 
 // ---------------------------------------------------------------------------------------------------------------- noise
 // out[(b * C + c) * W + j]: counter = (block j / 4 | level << 28, sample, image lo, image hi) under the key `seed`.
@@ -137,7 +126,7 @@ LapPlan lap_plan(int n, int D) {
   want = want > IW_MAX_SLICES ? IW_MAX_SLICES : want;
   p.chunk = ((D + want - 1) / want + IW_SLICE_FLOATS - 1) / IW_SLICE_FLOATS * IW_SLICE_FLOATS;
   p.slices = (D + p.chunk - 1) / p.chunk;                    // no empty slice
-  p.bytes = p.slices == 1 ? 0 : iw_align((size_t)n * p.slices * sizeof(double)) + 256;
+  p.bytes = p.slices == 1 ? 0 : ladder_round256((size_t)n * p.slices * sizeof(double)) + 256;
   return p;
 }
 bool lap_shape_ok(int n, int per, int D) { return n >= 1 && n <= IW_MAX_ROWS && per >= 1 && n % per == 0 && D >= 1 && D <= IW_MAX_D; }
@@ -147,71 +136,6 @@ __global__ __launch_bounds__(256) void iw_add_term_kernel(const void* __restrict
   if (i >= n) return;
   const double v = is_f32 ? (double)reinterpret_cast<const float*>(term)[i] : reinterpret_cast<const double*>(term)[i];
   logw[i] = init ? sign * v : logw[i] + sign * v;
-}
-
-// ---------------------------------------------------------------------------------------------------------------- diagonal mixture rows
-struct DmPlan { int ld; size_t o_m, o_is, o_c, bytes; };
-bool dm_shape_ok(int n, int Z, int K) { return n >= 1 && n <= IW_MAX_ROWS && Z >= 1 && Z <= DM_MAX_Z && K >= 1 && K <= DM_MAX_K; }
-DmPlan dm_plan(int Z, int K) {
-  DmPlan p;
-  p.ld = (Z + 3) & ~3;
-  size_t o = 0;
-  p.o_m = o;  o += iw_align((size_t)K * p.ld * sizeof(float));
-  p.o_is = o; o += iw_align((size_t)K * p.ld * sizeof(float));
-  p.o_c = o;  o += iw_align((size_t)K * sizeof(float));
-  p.bytes = o + 256;
-  return p;
-}
-
-// A wavefront takes DM_NS rows, a lane four consecutive dimensions of each (zeros past Z, where the prepared rows hold zeros too); per component one
-// 16-byte load of m and of 1/s serves all rows.  Lane k % 64 keeps lp[row, k] in registers (K <= 1024: 16 per row), then the max-subtracted log-sum-exp.
-__global__ __launch_bounds__(256) void dm_rows_kernel(const float* __restrict__ z, const float* __restrict__ m, const float* __restrict__ is,
-                                                      const float* __restrict__ c, int n, int Z, int ld, int K, float* __restrict__ logp) {
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int z0 = 4 * lane;
-  const bool on = z0 < ld;
-  const long sbase = ((long)blockIdx.x * 4 + wv) * DM_NS;
-  if (sbase >= n) return;                               // wavefront-uniform
-  float t[DM_NS][4];
-#pragma unroll
-  for (int i = 0; i < DM_NS; ++i) {
-    const long s = sbase + i < n ? sbase + i : n - 1;   // past the end: the last row again, nothing stored
-#pragma unroll
-    for (int j = 0; j < 4; ++j) t[i][j] = z0 + j < Z ? z[(size_t)s * Z + z0 + j] : 0.f;
-  }
-  float mine[DM_MAX_K / 64][DM_NS];
-#pragma unroll
-  for (int cc = 0; cc < DM_MAX_K / 64; ++cc) {
-#pragma unroll
-    for (int i = 0; i < DM_NS; ++i) mine[cc][i] = -INFINITY;
-    const int kc = cc * 64;
-    if (kc < K) {                                       // uniform
-      const int kend = K - kc < 64 ? K - kc : 64;
-      for (int kk = 0; kk < kend; ++kk) {
-        const size_t row = (size_t)(kc + kk) * ld + z0;
-        const float4 mv = on ? *reinterpret_cast<const float4*>(m + row) : make_float4(0.f, 0.f, 0.f, 0.f);
-        const float4 iv = on ? *reinterpret_cast<const float4*>(is + row) : make_float4(0.f, 0.f, 0.f, 0.f);
-        const float ck = c[kc + kk];
-#pragma unroll
-        for (int i = 0; i < DM_NS; ++i) {
-          const float v = dw_component_logp(dw_quad_partial(t[i], mv, iv), ck);
-          if (lane == kk) mine[cc][i] = v;
-        }
-      }
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < DM_NS; ++i) {
-    float mx = -INFINITY;
-#pragma unroll
-    for (int cc = 0; cc < DM_MAX_K / 64; ++cc) mx = fmaxf(mx, mine[cc][i]);
-    const float top = wave_max(mx);
-    float se = 0.f;
-#pragma unroll
-    for (int cc = 0; cc < DM_MAX_K / 64; ++cc) se += expf(mine[cc][i] - top);     // an unused slot holds -inf: exp gives an exact 0
-    se = wave_sum(se);
-    if (lane == 0 && sbase + i < n) logp[sbase + i] = top + logf(se);
-  }
 }
 
 // ---------------------------------------------------------------------------------------------------------------- streaming log-sum-exp
@@ -312,7 +236,7 @@ int ladder_iw_laplace_rows(const float* x, const float* xhat, int n, int per, in
   double* part = nullptr;
   if (p.slices > 1) {
     if (ws == nullptr || ws_bytes < p.bytes) return LADDER_E_WORKSPACE;
-    part = (double*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
+    part = (double*)ladder_align256(ws);
   }
   const bool vec = D % 4 == 0 && ladder_aligned16(x) && ladder_aligned16(xhat);
   const dim3 grid((unsigned)n, (unsigned)p.slices);
@@ -328,24 +252,6 @@ int ladder_iw_add_term(const void* term, int term_is_f32, double sign, int n, in
   if (term == nullptr || logw == nullptr || n < 1 || n > IW_MAX_ROWS) return LADDER_E_SHAPE;
   if (!iw_aligned8(logw) || (!term_is_f32 && !iw_aligned8(term))) return LADDER_E_ALIGN;
   hipLaunchKernelGGL(iw_add_term_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, term, term_is_f32, sign, n, init, logw);
-  LADDER_CHECK_LAUNCH();
-  return LADDER_OK;
-}
-
-size_t ladder_diag_mixture_logprob_rows_workspace_bytes(int n, int Z, int K) { return dm_shape_ok(n, Z, K) ? dm_plan(Z, K).bytes : 0; }
-
-int ladder_diag_mixture_logprob_rows(const float* z, const float* comp_mean, const float* comp_sd, int n, int Z, int K, float* logp, void* ws,
-                                     size_t ws_bytes, ladder_stream_t stream) {
-  if (z == nullptr || comp_mean == nullptr || comp_sd == nullptr || logp == nullptr || !dm_shape_ok(n, Z, K)) return LADDER_E_SHAPE;
-  const DmPlan p = dm_plan(Z, K);
-  if (ws == nullptr || ws_bytes < p.bytes) return LADDER_E_WORKSPACE;
-  char* w = (char*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
-  float* m = (float*)(w + p.o_m);
-  float* is = (float*)(w + p.o_is);
-  float* c = (float*)(w + p.o_c);
-  hipLaunchKernelGGL(dw_prepare_kernel, dim3(K), dim3(64), 0, stream, comp_mean, comp_sd, Z, p.ld, K, m, is, c);
-  hipLaunchKernelGGL(dm_rows_kernel, dim3((n + 4 * DM_NS - 1) / (4 * DM_NS)), dim3(256), 0, stream, z, (const float*)m, (const float*)is, (const float*)c,
-                     n, Z, p.ld, K, logp);
   LADDER_CHECK_LAUNCH();
   return LADDER_OK;
 }

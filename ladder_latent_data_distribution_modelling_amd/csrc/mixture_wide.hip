@@ -19,7 +19,7 @@
 // The term (ladder_gmm_wide_logprob_fwd_bwd), S = L*B samples in tiles of 64 (4 wavefronts x 16 rows), t = mu + sd * eps formed in registers:
 //   gmmw_q_kernel     grid (tiles, KS): per component of the workgroup's K range d = t - m_k, y = Linv_k d block row by block row, q[s][k] = |y|^2
 //   gmmw_lse_kernel   a thread per sample: lp_k = logc_k - q_k / 2, max-subtracted logsumexp, q <- responsibilities, a double partial per workgroup
-//   gmmw_sum_kernel   the partials in a fixed order -> sum_logp
+//   sum_doubles_kernel   (common.h) the partials in a fixed order -> sum_logp
 //   gmmw_g_kernel     grid (tiles, KS): acc = sum_k (r_sk d_sk) P_k over the K range with the scaled operand formed in registers, g[ks][s][:] = -acc;
 //                     a component whose responsibilities are exactly zero on all 16 samples of a wavefront's rows is skipped (it adds +-0)
 //   gmmw_reduce_kernel dmu[b] = sum_l sum_ks g[ks][l,b], dsd[b] = sum_l (sum_ks g[ks][l,b]) eps[l,b], l ascending, ks ascending inside
@@ -244,13 +244,6 @@ __global__ __launch_bounds__(256) void gmmw_lse_kernel(float* __restrict__ q, co
   if (threadIdx.x == 0) part[blockIdx.x] = (blk[0] + blk[1]) + (blk[2] + blk[3]);
 }
 
-__global__ __launch_bounds__(64) void gmmw_sum_kernel(const double* __restrict__ part, int n, float* __restrict__ out) {
-  double s = 0.0;                                        // one wavefront: lane-strided partial sums, then a fixed-order shuffle tree
-  for (int i = threadIdx.x; i < n; i += 64) s += part[i];
-  s = wave_sum_d(s);
-  if (threadIdx.x == 0) out[0] = (float)s;
-}
-
 __global__ __launch_bounds__(256) void gmmw_g_kernel(const float* __restrict__ mu, const float* __restrict__ sd, const float* __restrict__ eps,
                                                      const unsigned char* __restrict__ params, const float* __restrict__ resp, int S, int B, int R,
                                                      int K, float* __restrict__ g) {
@@ -324,7 +317,6 @@ __global__ void gmmw_reduce_kernel(const float* __restrict__ g, const float* __r
 }
 
 // ----------------------------------------------------------------------------------------------------------------- host side
-size_t gw_align(size_t n) { return (n + 255) & ~(size_t)255; }
 int gw_tiles(size_t S) { return (int)((S + GW_TILE - 1) / GW_TILE); }
 // K is split over gridDim.y workgroups per tile to fill the chip.  The matrix kernels run two workgroups per CU (two wavefronts per SIMD), 512 at
 // a time on the 256 CUs this library is built for; with equal workgroups a launch takes ceil(workgroups / 512) rounds of ceil(K / KS) components, and
@@ -361,13 +353,13 @@ struct GwLayout {
 };
 GwLayout gw_layout(size_t S, int R, int K) {
   GwLayout l;
-  l.part = gw_align(S * K * 4);
-  l.g = l.part + gw_align(((S + 255) / 256) * 8);
-  l.total = l.g + gw_align((size_t)gw_gsplits_max(S) * S * R * 4) + 256;
+  l.part = ladder_round256(S * K * 4);
+  l.g = l.part + ladder_round256(((S + 255) / 256) * 8);
+  l.total = l.g + ladder_round256((size_t)gw_gsplits_max(S) * S * R * 4) + 256;
   return l;
 }
 GwWorkspace gw_workspace(size_t S, int R, int K, void* ws) {
-  char* p = (char*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
+  char* p = ladder_align256(ws);
   const GwLayout l = gw_layout(S, R, K);
   return GwWorkspace{(float*)p, (double*)(p + l.part), (float*)(p + l.g)};
 }
@@ -411,7 +403,7 @@ int ladder_gmm_wide_logprob_fwd_bwd(const float* mu, const float* sd, const floa
   const int train = dmu != nullptr ? 1 : 0;
   hipLaunchKernelGGL(gmmw_q_kernel<false>, dim3(tiles, KSq), dim3(256), 0, stream, mu, sd, eps, p, (int)S, B, R, K, w.q);
   hipLaunchKernelGGL(gmmw_lse_kernel, dim3(nblk), dim3(256), 0, stream, w.q, p, (int)S, K, R, train, w.part, (float*)nullptr);
-  hipLaunchKernelGGL(gmmw_sum_kernel, dim3(1), dim3(64), 0, stream, (const double*)w.part, nblk, sum_logp);
+  hipLaunchKernelGGL(sum_doubles_kernel<float>, dim3(1), dim3(64), 0, stream, (const double*)w.part, nblk, sum_logp);
   if (train) {
     hipLaunchKernelGGL(gmmw_g_kernel, dim3(tiles, KS), dim3(256), 0, stream, mu, sd, eps, p, (const float*)w.q, (int)S, B, R, K, w.g);
     hipLaunchKernelGGL(gmmw_reduce_kernel, dim3((B * R + 63) / 64), dim3(64), 0, stream, (const float*)w.g, eps, dmu, dsd, L, B * R, KS);

@@ -14,7 +14,7 @@ from . import layers as _layers
 from .comm import Comm, VirtualComm, VirtualGroup, run_virtual_ranks, _NoComm, _DoneWork, _TracedWork  # noqa: F401  (re-exported: tests, bench.py)
 from .layers import (ADAM_B1, ADAM_B2, ADAM_EPS, BN_EPS, DEFAULT_PRECISION, IN_EPS, PRECISION_NOTES, PRECISIONS, BatchNormAct, Conv2D, Ctx, Dense,  # noqa: F401
                      DepthToSpace, InstanceNormStyleAct, ParamStore, PlanesOnly, Resize, _p, _timed, add_, pad_symmetric, plan_decoder)
-from .mixture import DeviceMixture
+from .mixture import DeviceMixture, DiagMixture
 from .mixture_forms import check_status_word, family, sized_workspace
 from .profiler import KernelProfiler  # noqa: F401
 
@@ -362,6 +362,7 @@ class LadderEngine:
         self.rng_counter = torch.zeros(1, dtype=torch.int64, device=self.ctx.device)   # Philox stream position (device)
         self._run_calls = 0
         self.mixture = None                                  # DeviceMixture, once set_mixture() / set_sg_mixture() was called
+        self.vamp_mixture = DiagMixture(self.ctx, self.K, self.Z) if self.vamp else None
         self.use_graphs = False
         # filter gradients on a second stream beside the backward chain (config key `overlap_filter_gradients` / environment variable
         # LADDER_OVERLAP_FILTER_GRADIENTS): +0.7-1 % per iteration with the f16x3 kernels, nothing with the fp32 ones (round 4: 3 328 / 3 327 img/s --
@@ -572,25 +573,11 @@ class LadderEngine:
     def _vamp_term(self, mu, sd, noise, B):
         """crossEntropy_prior of the VampPrior (base.py:361-370): the components at the pseudo-inputs, then the MC mixture term and its
         gradients towards both the posterior heads and the components."""
-        ctx, st, Z, K, P = self.ctx, self.ctx.stream, self.Z, self.K, self.partials
         mu_p, sd_p, sdraw_p, eps0 = self._vamp_components()
-        eps_mc = self._noise(noise, "eps_mc", (self.Lmc, B, Z))
-        dmu, dsd, dcm, dcs = ctx.empty(B, Z), ctx.empty(B, Z), ctx.empty(K, Z), ctx.empty(K, Z)
-        query, entry, wide = self._vamp_entries(Z)
-        wsp, wsn = ctx.ws(L.query(query, self.Lmc, B, Z, K) if wide else L.query(query, B, Z, K))
-        L.call(entry, _p(mu), _p(sd), _p(eps_mc), _p(mu_p), _p(sd_p), self.Lmc, B, Z, K, _p(P[L.P_LOGP:]),
-               _p(dmu), _p(dsd), _p(dcm), _p(dcs), wsp, wsn, st)
+        eps_mc = self._noise(noise, "eps_mc", (self.Lmc, B, self.Z))
+        dmu, dsd, dcm, dcs = self.vamp_mixture.fwd_bwd(mu, sd, eps_mc, mu_p, sd_p, self.partials[L.P_LOGP:])
         self.vamp_state = (mu_p, sd_p, sdraw_p, eps0, dcm, dcs)
         return dmu, dsd
-
-    @staticmethod
-    def _vamp_entries(Z):
-        """(workspace query, term, wide) of the VampPrior term on a code of width Z: the wide pair (csrc/diag_mixture_wide.hip; its query
-        takes L as well) for 80 .. 256 in steps of 16, the widths of the wide diagonal sampler; the narrow pair (csrc/mixture.hip) for
-        every other width, which refuses Z > 64 itself."""
-        if 80 <= Z <= 256 and Z % 16 == 0:
-            return "ladder_diag_mixture_wide_workspace_bytes", "ladder_diag_mixture_wide_fwd_bwd", True
-        return "ladder_diag_mixture_workspace_bytes", "ladder_diag_mixture_fwd_bwd", False
 
     def _vamp_backward(self, wgrad, need_input_dx):
         """Backward of the pseudo-input pass: d loss/d components = -(1/LB) * (dcomp_mean, dcomp_sd) through the heads."""

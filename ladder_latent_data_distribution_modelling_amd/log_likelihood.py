@@ -1,5 +1,5 @@
 """Importance-weighted estimate of the marginal log-likelihood, log p(x) ~ log (1/S) sum_s w_s, for every prior (DESIGN.md "Importance-weighted
-log-likelihood"; kernels: csrc/iwll.hip).
+log-likelihood"; kernels: csrc/iwll.hip, and csrc/diag_mixture.hip for log p(z) of the vampPrior).
 
 A batch of B images is encoded once, as `test_step` encodes it (batch-norm statistics of that batch) -> mu_z, sd_z.  Sample s of image b is
 z = mu_z[b] + sd_z[b] * eps_z and its log-weight
@@ -19,7 +19,6 @@ import torch
 from . import _lib as L
 from .layers import _p
 from .mixture import DeviceMixture
-from .mixture_forms import sized_workspace
 
 FULL_MIXTURE_PRIORS = ("ours", "GMM")
 TERMS = ("log_px_z", "log_pz", "log_pt", "log_qz", "log_qt")       # + "logw" and the code samples "z" with return_terms
@@ -79,7 +78,6 @@ class ImportanceEstimator:
                 self.vamp = eng._vamp_components()[:2]
             finally:
                 ctx.keep_activations = keep
-            self.vamp_ws = sized_workspace("ladder_diag_mixture_logprob_rows_workspace_bytes", ctx.device, 1, self.Z, eng.K)
 
     # ------------------------------------------------------------------------------------------ row terms
     def _f64(self, n):
@@ -121,12 +119,6 @@ class ImportanceEstimator:
         L.call("ladder_iw_laplace_rows", _p(x), _p(xhat), n, per, self.D, self.sigma, _p(out), wsp, wsn, ctx.stream)
         return out
 
-    def _vamp_rows(self, z):
-        ctx, n = self.eng.ctx, int(z.shape[0])
-        out = ctx.empty(n)
-        L.call("ladder_diag_mixture_logprob_rows", _p(z), _p(self.vamp[0]), _p(self.vamp[1]), n, self.Z, self.eng.K, _p(out), *self.vamp_ws[1], ctx.stream)
-        return out
-
     def _chunk_terms(self, x, mu, sd, noise, s0, c, first):
         """The term vectors [B * c] of samples s0 .. s0 + c - 1 of every image of the batch -> ({name: (tensor, sign)}, z rows)."""
         eng, B = self.eng, int(mu.shape[0])
@@ -139,7 +131,7 @@ class ImportanceEstimator:
         elif self.prior == "GMM":
             terms["log_pz"] = (self.mixture.log_prob_rows(z), 1.0)
         elif self.prior == "vampPrior":
-            terms["log_pz"] = (self._vamp_rows(z), 1.0)
+            terms["log_pz"] = (eng.vamp_mixture.log_prob_rows(z, *self.vamp), 1.0)
         else:
             mu_t, sdraw_t = eng.inner.encode(z)
             t, logq_t = self._sample(mu_t, self._sd(sdraw_t), self._eps(noise, "eps_t", 1, s0, c, B, self.R, first), 1)

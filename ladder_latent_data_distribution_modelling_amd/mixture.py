@@ -1,6 +1,7 @@
 """The fitted full-covariance Gaussian mixture on the device: the one owner of the prepared parameter buffer, in the form of its width's tier
 (mixture_forms.py, operation "term": packed, dense or wide).  The ELBO term (LadderEngine), the demo's `log_prob` (demo/demo_tools.py) and the SLP
-interpolation (codes/interpolation.py, which reads the packed and the dense buffer) all evaluate the mixture through this class.
+interpolation (codes/interpolation.py, which reads the packed and the dense buffer) all evaluate the mixture through this class.  `DiagMixture` is the
+owner of the VampPrior's equally weighted diagonal mixture (csrc/diag_mixture.hip), whose components arrive with every call.
 """
 import numpy as np
 import torch
@@ -61,4 +62,35 @@ class DeviceMixture:
         out = torch.empty(n, device=dev)
         ws, ws_args = sized_workspace(form.workspace_bytes if form.rows_workspace else None, dev, 1, n, self.R, self.K)
         L.call(form.logprob_rows, _p(t), _p(self.buf), n, self.R, self.K, _p(out), *ws_args, self.ctx.stream)
+        return out
+
+
+class DiagMixture:
+    """The equally weighted mixture of K diagonal Gaussians on Z dimensions (the VampPrior): its ELBO term in the form of its width (mixture_forms.py,
+    operation "diag_term") and the log-density of separate points.  It keeps no parameters: the components (comp_mean, comp_sd [K, Z]) are what the
+    encoder gives at the pseudo-inputs, passed with each call."""
+
+    def __init__(self, ctx, K, Z):
+        self.ctx, self.K, self.Z = ctx, int(K), int(Z)
+        self.form = family("diag_term", self.K, self.Z)
+        self.rows_ws = None                                  # (tensor, arguments) of the workspace log_prob_rows takes: sized once, by its first call
+
+    def fwd_bwd(self, mu, sd, eps, comp_mean, comp_sd, sum_out):
+        """MC estimate over the L = eps.shape[0] samples t = mu + sd * eps of each of the B rows: writes the sum of the log-probs to `sum_out` and
+        returns (dmu, dsd [B, Z], dcomp_mean, dcomp_sd [K, Z]), the sums over the samples of dlogp/dt, dlogp/dt * eps and dlogp/d component."""
+        ctx, form, K, Z = self.ctx, self.form, self.K, self.Z
+        Lmc, B = int(eps.shape[0]), int(mu.shape[0])
+        dmu, dsd, dcm, dcs = ctx.empty(B, Z), ctx.empty(B, Z), ctx.empty(K, Z), ctx.empty(K, Z)
+        wsp, wsn = ctx.ws(L.query(form.workspace_bytes, Lmc, B, Z, K) if form.query_takes_L else L.query(form.workspace_bytes, B, Z, K))
+        L.call(form.fwd_bwd, _p(mu), _p(sd), _p(eps), _p(comp_mean), _p(comp_sd), Lmc, B, Z, K, _p(sum_out), _p(dmu), _p(dsd), _p(dcm), _p(dcs),
+               wsp, wsn, ctx.stream)
+        return dmu, dsd, dcm, dcs
+
+    def log_prob_rows(self, z, comp_mean, comp_sd):
+        """log p of the n points of the device tensor `z` [n, Z] -> device tensor [n] (one export for every width up to 256: nothing to select)."""
+        ctx, n = self.ctx, int(z.shape[0])
+        if self.rows_ws is None:                             # (the size does not depend on n)
+            self.rows_ws = sized_workspace("ladder_diag_mixture_logprob_rows_workspace_bytes", ctx.device, 1, self.Z, self.K)
+        out = ctx.empty(n)
+        L.call("ladder_diag_mixture_logprob_rows", _p(z), _p(comp_mean), _p(comp_sd), n, self.Z, self.K, _p(out), *self.rows_ws[1], ctx.stream)
         return out

@@ -6,6 +6,9 @@ follow them: "wide" in `ladder_vbgmm_wide_*` and `ladder_slp_wide_*` is the dens
 A row names its operation, its tiers, the shapes its family takes (lo <= R <= hi, R % step == 0, 1 <= K <= max_k; None: no bound drawn on this side),
 every entry point under a role name shared by the operation's rows, and what differs in how the families are called.  The table selects by tier;
 the operations in REFUSALS also hold the shape against the row, the others (the dense term at R = 10, say) are refused by the library, as ever.
+"diag_term", the VampPrior's diagonal mixture (mixture.py: DiagMixture), is the one operation that does not select by tier: its wide row serves exactly
+the widths that row takes, whatever K, and its narrow row every other width -- 70 too, which the tier rule would call wide -- so that such a model
+meets the narrow entry's refusal before any launch, as it always has.
 """
 import torch
 
@@ -34,6 +37,11 @@ FAMILIES = {
         Form("term", WIDE, 80, 256, 16, 1024, param_size="ladder_gmm_wide_param_bytes", prepare="ladder_gmm_wide_prepare", workspace_bytes="ladder_gmm_wide_workspace_bytes",
              fwd_bwd="ladder_gmm_wide_logprob_fwd_bwd", logprob_rows="ladder_gmm_wide_logprob_rows",
              prepare_workspace_bytes="ladder_gmm_wide_prepare_workspace_bytes", rows_workspace=True)),
+    # the VampPrior term (mixture.py: DiagMixture; csrc/diag_mixture.hip).  query_takes_L: the workspace query takes (L, B, Z, K), not (B, Z, K)
+    "diag_term": (
+        Form("diag_term", NARROW, 1, 64, workspace_bytes="ladder_diag_mixture_workspace_bytes", fwd_bwd="ladder_diag_mixture_fwd_bwd", query_takes_L=False),
+        Form("diag_term", WIDE, 80, 256, 16, 1024, workspace_bytes="ladder_diag_mixture_wide_workspace_bytes", fwd_bwd="ladder_diag_mixture_wide_fwd_bwd",
+             query_takes_L=True)),
     "sampler": (                                 # ancestral sampling (engine.py: prior_sampler)
         Form("sampler", NARROW, 1, 64, param_bytes="ladder_mixture_sample_param_bytes", prepare="ladder_mixture_sample_prepare",
              prepare_diag="ladder_mixture_sample_prepare_diag", sample="ladder_mixture_sample", prepare_workspace_bytes=None),
@@ -86,6 +94,9 @@ REFUSALS = {
 
 def family(op, K, R):
     """The row of `op` that serves K components on R dimensions; raises what the owner of `op` has always raised where there is none."""
+    if op == "diag_term":                                    # by the wide row's width rule alone (module docstring)
+        narrow, wide = FAMILIES[op]
+        return wide if wide.takes(R) else narrow
     tier = "packed" if R <= 8 else "dense" if R <= 64 else "wide"
     row = next((r for r in FAMILIES[op] if tier in r.tiers), None)
     if op in REFUSALS and (row is None or not row.takes(R, K)):

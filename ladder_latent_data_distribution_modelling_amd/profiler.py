@@ -36,7 +36,7 @@ class KernelProfiler:
                      "(+ 1x1 output projection) by four other waves; Z never written to HBM)",
              128134: "gemm_nt16_f32_kernel (backward-data GEMMs of the project-then-upsample pairs, dx = D . wcat^T with both operands K-contiguous: persistent "
                      "workgroups over 128x128 tiles, 128-bit fragments of both operands, fp32 MFMA 16x16x4)",
-             7700: "gmm_logprob_kernel<R> + gmm_sum_kernel (mixture log-prob / responsibilities, lane = component, wave-shuffle logsumexp)"}
+             7700: "gmm_logprob_kernel<R> + sum_doubles_kernel (mixture log-prob / responsibilities, lane = component, wave-shuffle logsumexp)"}
     LATENCY_BOUND = (7700,)          # not contraction kernels: reported beside the roofline, never as the dominant MFMA kernel
 
     def __init__(self):

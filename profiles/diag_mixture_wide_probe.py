@@ -1,4 +1,4 @@
-"""Time of the VampPrior term on a wide code ("The VampPrior term on a wide code"; csrc/diag_mixture_wide.hip).
+"""Time of the VampPrior term on a wide code ("The VampPrior term on a wide code"; csrc/diag_mixture.hip).
 
     python profiles/diag_mixture_wide_probe.py [--out profiles/diag_mixture_wide_probe.json] [--reps 30] [--kernel-db results.db]
     rocprofv3 --kernel-trace --stats -d DIR -- python profiles/diag_mixture_wide_probe.py --trace       (a run of its own: only leg (a), 30 calls)
@@ -52,7 +52,7 @@ def inputs(Z):
 
 
 def launch_model(Z):
-    """bytes and floating-point operations each launch of (a) needs, from the shapes (csrc/diag_mixture_wide.hip: DW_KC = 16, 256 slices)"""
+    """bytes and floating-point operations each launch of (a) needs, from the shapes (csrc/diag_mixture.hip: DW_KC = 16, 256 slices)"""
     S, Kp, nkc, slices = L_ * B, (K + 15) // 16 * 16, (K + 15) // 16, 256
     lsplit = slices // B
     return {
@@ -64,7 +64,7 @@ def launch_model(Z):
         "dw_reduce_kernel": dict(flop=2.0 * (slices * K * Z + nkc * lsplit * B * Z), bytes=4.0 * (2 * (slices + 1) * K * Z + 2 * (nkc * lsplit + 1) * B * Z),
                                  launches=2),
         "dw_prepare_kernel": dict(flop=3.0 * K * Z, bytes=16.0 * K * Z),
-        "dw_sum_kernel": dict(flop=S / 16.0, bytes=8.0 * S / 16),
+        "sum_doubles_kernel": dict(flop=S / 16.0, bytes=8.0 * S / 16),
     }
 
 
@@ -73,7 +73,7 @@ def kernel_times(db_path):
     db = sqlite3.connect(db_path)
     out = {}
     for name, calls, avg in db.execute("select name, count(*), avg(duration) from kernels group by name"):
-        for short in ("dw_resp_kernel", "dw_accum_kernel", "dw_reduce_kernel", "dw_prepare_kernel", "dw_sum_kernel"):
+        for short in ("dw_resp_kernel", "dw_accum_kernel", "dw_reduce_kernel", "dw_prepare_kernel", "sum_doubles_kernel"):
             if short in name:
                 out[short] = (calls, avg / 1e3)
     return out

@@ -20,6 +20,11 @@ if ROOT not in sys.path:
 
 PACKED = [(5, 1, 7, 3), (30, 2, 9, 5), (64, 8, 5, 4), (65, 3, 5, 4), (130, 8, 6, 2)]       # (K, R, L, B)
 N_ROWS = 7
+# the diagonal mixture (VampPrior).  Wide term (L, B, Z, K): S = 15 under one workgroup with lanes 20..63 off; two component chunks of 16, the second
+# padded; two chunks of 64 components (Kp = 80); an odd L.  Rows (n, Z, K): rows padded to 8; a second workgroup with one live row and two component
+# chunks; one row, one component, the widest code; ld = 252 and three chunks.
+DIAG_WIDE = [(3, 5, 80, 1), (5, 7, 80, 17), (2, 9, 256, 65), (7, 3, 96, 50)]
+DIAG_ROWS = [(7, 5, 3), (17, 40, 65), (1, 256, 1), (5, 250, 130)]
 
 
 def mixture(K, R, seed):
@@ -47,6 +52,7 @@ def main(out_path):
     from ladder_latent_data_distribution_modelling_amd.engine import Ctx, LadderEngine
     from ladder_latent_data_distribution_modelling_amd.codes.interpolation import SLPInterpolator
     from ladder_latent_data_distribution_modelling_amd.demo.demo_tools import MixturePrior
+    from ladder_latent_data_distribution_modelling_amd.mixture import DeviceMixture
     ctx = Ctx("cuda:0")
     st = ctx.stream
     dev = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.float32)).cuda()
@@ -123,6 +129,38 @@ def main(out_path):
     L.call("ladder_diag_mixture_fwd_bwd", *(p(v) for v in a), Lmc, B, Z, K, p(s), p(dmu), p(dsd), p(dcm), p(dcs), p(ws), ws.numel(), st)
     torch.cuda.synchronize()
     out.update(diag_sum=host(s), diag_dmu=host(dmu), diag_dsd=host(dsd), diag_dcm=host(dcm), diag_dcs=host(dcs))
+
+    # ---- the same term on a wide code, and the per-row log-density (csrc/diag_mixture.hip)
+    for Lmc, B, Z, K in DIAG_WIDE:
+        rng = np.random.default_rng(410 + K)
+        a = [dev(v) for v in (rng.standard_normal((B, Z)) * 1.2, 0.1 + rng.random((B, Z)), rng.standard_normal((Lmc, B, Z)), rng.standard_normal((K, Z)),
+                              0.3 + rng.random((K, Z)))]
+        s, dmu, dsd, dcm, dcs = (torch.empty(1, device="cuda"), torch.empty(B, Z, device="cuda"), torch.empty(B, Z, device="cuda"),
+                                 torch.empty(K, Z, device="cuda"), torch.empty(K, Z, device="cuda"))
+        ws = torch.empty(L.query("ladder_diag_mixture_wide_workspace_bytes", Lmc, B, Z, K), dtype=torch.uint8, device="cuda")
+        L.call("ladder_diag_mixture_wide_fwd_bwd", *(p(v) for v in a), Lmc, B, Z, K, p(s), p(dmu), p(dsd), p(dcm), p(dcs), p(ws), ws.numel(), st)
+        torch.cuda.synchronize()
+        tag = "diag_wide_L%d_B%d_Z%d_K%d" % (Lmc, B, Z, K)
+        out.update({tag + "_sum": host(s), tag + "_dmu": host(dmu), tag + "_dsd": host(dsd), tag + "_dcm": host(dcm), tag + "_dcs": host(dcs)})
+    for n, Z, K in DIAG_ROWS:
+        rng = np.random.default_rng(420 + K)
+        z, cm, cs = dev(rng.standard_normal((n, Z)) * 1.5), dev(rng.standard_normal((K, Z))), dev(0.3 + rng.random((K, Z)))
+        lp = torch.empty(n, device="cuda")
+        ws = torch.empty(L.query("ladder_diag_mixture_logprob_rows_workspace_bytes", n, Z, K), dtype=torch.uint8, device="cuda")
+        L.call("ladder_diag_mixture_logprob_rows", p(z), p(cm), p(cs), n, Z, K, p(lp), p(ws), ws.numel(), st)
+        torch.cuda.synchronize()
+        out["diag_rows_n%d_Z%d_K%d" % (n, Z, K)] = host(lp)
+
+    # ---- the wide form of the full-covariance term (its sum of the partials is the kernel every term shares)
+    K, R, Lmc, B = 3, 80, 3, 5
+    mix = DeviceMixture(ctx, K, R)
+    mix.set(*mixture(K, R, 113))
+    mu, sd, eps, t = inputs(K, R, Lmc, B, N_ROWS, 213)
+    s = torch.empty(1, device="cuda")
+    dmu, dsd = mix.fwd_bwd(mu, sd, eps, s)
+    lp = mix.log_prob_rows(t)
+    torch.cuda.synchronize()
+    out.update(wide_sum=host(s), wide_dmu=host(dmu), wide_dsd=host(dsd), wide_rows=host(lp))
 
     # ---- through Python
     d = np.load(os.path.join(ROOT, "tests", "golden", "oracle_mnist_digit.npz"))

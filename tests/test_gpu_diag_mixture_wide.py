@@ -1,4 +1,4 @@
-"""The VampPrior term on a wide code (csrc/diag_mixture_wide.hip; 80 <= Z <= 256, Z % 16 == 0) through the C ABI against float64 autograd of the formula
+"""The VampPrior term on a wide code (csrc/diag_mixture.hip; 80 <= Z <= 256, Z % 16 == 0) through the C ABI against float64 autograd of the formula
 in codes/base.py:244-254, 361-370, written as tests/test_gpu_kernels.py::test_diag_mixture_vamp writes it, at that test's bars:
 
     |sum - ref| < 3e-5 |ref| + 1e-3,   each of the four gradients within 1e-4 of the reference's largest magnitude.

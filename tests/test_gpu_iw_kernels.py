@@ -4,7 +4,7 @@ Row kernels (sample_rows' log q, laplace_rows, gauss_rows) form every difference
 of n_terms float64 terms in any order is within n_terms * 2^-52 * sum |terms| of the exact sum, plus 1e-12 relative on the terms a `log` produces (the
 device's float64 log is good to a few ulp; numpy's likewise).  `sample` is fp32 fmaf(sd, eps, mu): it must equal the z of ladder_latent_fwd bit for bit.
 It was meant to equal torch.addcmul's bits too; measured on an MI355X it does not (addcmul rounds the product before the sum), so that comparison is held
-at 1 ulp, as DESIGN.md says.  The diagonal-mixture rows run the fp32 arithmetic of the responsibilities pass of csrc/diag_mixture_wide.hip and
+at 1 ulp, as DESIGN.md says.  The diagonal-mixture rows run the fp32 arithmetic of the responsibilities pass of csrc/diag_mixture.hip and
 are held to the bar tests/test_gpu_diag_mixture_wide.py::check holds that kernel's sum of log-probs to, per row: |got - ref| < 3e-5 |ref| + 1e-3.
 accumulate + finish are compared with the one-shot float64 estimator at 1e-12 RELATIVE (log-weights near -7e4: one float64 ulp there is 1.5e-11, so an
 absolute 1e-12 could not be met by any float64 code; relative 1e-12 is 7e-8 absolute there, and four orders above the rounding of an 8-term sum)."""

@@ -4,7 +4,10 @@ project's own recorded result, kept as recorded; `python tests/test_gpu_mixture_
 
 One difference from the record is intended and spelt out in `without_selection_probes`: DeviceKMeans used to FIND its family by asking each
 family's state-size query in turn and then asked the chosen one again for the size; the table selects now, so of such a run of state-size queries
-only the last -- the sizing one, with its arguments -- is still issued.  Everything else, every other query included, is compared as recorded."""
+only the last -- the sizing one, with its arguments -- is still issued.  Everything else, every other query included, is compared as recorded.
+
+The "vamp" sections were recorded before the diagonal mixture (VampPrior) got its owner, mixture.py: DiagMixture: one engine forward with the narrow
+and with the wide term, one importance-weighted estimate; of those runs only the calls of that family are kept."""
 import ctypes
 import json
 import os
@@ -25,7 +28,9 @@ K, B, N = 3, 8, 256
 
 SECTIONS = (["term R=%d" % R for R in WIDTHS] + ["sampler %s R=%d" % (m, R) for R in WIDTHS for m in ("GMM", "standard_gaussian")]
             + ["em fit R=%d" % R for R in (16, 80)] + ["kmeans %s R=%d" % (s, R) for R in (16, 80) for s in ("seeded", "array")]
-            + ["vb fit persistent R=4", "vb fit sharded R=4", "vb fit R=16", "slp R=4", "slp R=16"])
+            + ["vb fit persistent R=4", "vb fit sharded R=4", "vb fit R=16", "slp R=4", "slp R=16"]
+            + ["vamp term Z=16", "vamp term Z=80", "vamp rows Z=16"])
+DIAG_PREFIX = "ladder_diag_mixture"  # the vamp sections run a whole forward / estimate: only the calls of this family are kept
 
 
 class Recorder:
@@ -40,8 +45,8 @@ class Recorder:
 
         def recorded(*args):
             assert len(args) == len(argtypes), name
-            self.calls.append([name] + [("PTR" if a else "NULL") if t is ctypes.c_void_p else (float(a) if t in (ctypes.c_float, ctypes.c_double) else int(a))
-                                        for t, a in zip(argtypes, args)])
+            self.calls.append([name] + [("PTR" if a else "NULL") if t is ctypes.c_void_p else "STRUCT" if issubclass(t, ctypes.Structure)
+                                        else (float(a) if t in (ctypes.c_float, ctypes.c_double) else int(a)) for t, a in zip(argtypes, args)])
             return fn(*args)
         return recorded
 
@@ -73,9 +78,9 @@ def drive(golden_dir):
     rec = Recorder(real, L.PROTOTYPES)
     out = {}
 
-    def section(name):
+    def section(name, prefix=""):
         torch.cuda.synchronize()
-        out[name], rec.calls = rec.calls, []
+        out[name], rec.calls = [c for c in rec.calls if c[0].startswith(prefix)], []
 
     L._lib = rec
     try:
@@ -122,6 +127,18 @@ def drive(golden_dir):
                 rec.calls = []                                                # (the mixture's own set(): section "term")
                 slp.optimise_batch(rng.normal(size=(2, R)), rng.normal(size=(2, R)), n_step=4, n_iter=5)
                 section("slp R=%d" % R)
+            x = np.load(os.path.join(golden_dir, "oracle_mnist_fashion.npz"))["x"]
+            x = np.concatenate([x] * -(-B // len(x)))[:B]                     # (the golden batch is smaller than B)
+            for Z in (16, 80):                                                # the narrow and the wide term of the diagonal mixture
+                eng = LadderEngine(dict(cfg, prior="vampPrior", code_size=Z, n_mixtures=K), "cuda:0", seed=2)
+                torch.cuda.synchronize()
+                rec.calls = []
+                eng.forward(x, use_sg=False, parts=("gmm",))
+                section("vamp term Z=%d" % Z, DIAG_PREFIX)
+                if Z == 16:
+                    from ladder_latent_data_distribution_modelling_amd.log_likelihood import ImportanceEstimator
+                    ImportanceEstimator(eng).estimate_batch(x, 2, rows=16)
+                    section("vamp rows Z=16", DIAG_PREFIX)
     finally:
         L._lib = real
     return out

@@ -1,5 +1,5 @@
 """VampPrior models whose code is wider than 64 (the reference's shipped codes/celeba_config.json has code_size 256): the engine's RUN#1 / RUN#3 /
-evaluate with the wide term (csrc/diag_mixture_wide.hip) against the float64 oracle, the captured runs against the eager ones, and the trainer,
+evaluate with the wide term (csrc/diag_mixture.hip) against the float64 oracle, the captured runs against the eager ones, and the trainer,
 generation, `model.psedeu_prior` and the demo's prior on an 80-dimensional code.  Before there was a wide term every test here met the library's
 shape error in the first run that evaluates the prior."""
 import json
@@ -44,7 +44,7 @@ def test_vamp_prior_wide_code_vs_oracle(golden_dir, exp, Z):
     st = O.OracleState(cfg, P, np.float64)
     st32 = O.OracleState(cfg, P, np.float32)
     eng = _engine(cfg, values=P)
-    assert eng.vamp and not eng.has_inner and eng._vamp_entries(Z)[2]
+    assert eng.vamp and not eng.has_inner and eng.vamp_mixture.form.query_takes_L
     for group, runner in (("ae", eng.run_ae), ("prior", eng.run_prior)):
         ref = O.run(st, x, noise, None, False, False, train=group, lr=0.0)
         ref32 = O.run(st32, x, noise, None, False, False, train=group, lr=0.0)

@@ -14,8 +14,11 @@ import iw_ref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 IW_EXPORTS = {"ladder_iw_randn_rows", "ladder_iw_sample_rows", "ladder_iw_laplace_rows_workspace_bytes", "ladder_iw_laplace_rows", "ladder_iw_gauss_rows",
-              "ladder_iw_add_term", "ladder_iw_accumulate", "ladder_iw_finish", "ladder_diag_mixture_logprob_rows_workspace_bytes",
-              "ladder_diag_mixture_logprob_rows"}
+              "ladder_iw_add_term", "ladder_iw_accumulate", "ladder_iw_finish"}
+# log p(z) of the VampPrior: declared and defined with the rest of the diagonal mixture (csrc/diag_mixture.hip)
+DIAG_ROWS_EXPORTS = {"ladder_diag_mixture_logprob_rows_workspace_bytes", "ladder_diag_mixture_logprob_rows"}
+DIAG_TERM_EXPORTS = {"ladder_diag_mixture_workspace_bytes", "ladder_diag_mixture_fwd_bwd", "ladder_diag_mixture_wide_workspace_bytes",
+                     "ladder_diag_mixture_wide_fwd_bwd"}
 
 
 # ------------------------------------------------------------------------------------------------ the reference itself
@@ -115,25 +118,33 @@ def test_header_prototypes_and_sources_agree():
     header = open(os.path.join(ROOT, "include", "ladder_hip.h")).read()
     section = header[header.index("N25: importance-weighted marginal log-likelihood"):]
     section = section[:section.index("/* ----", 10)]
-    declared = set(re.findall(r"^(?:int|size_t) (ladder_[a-z0-9_]+)\(", section, re.M))
-    assert declared == IW_EXPORTS
-    assert {n for n in _lib.PROTOTYPES if n.startswith("ladder_iw_") or n.startswith("ladder_diag_mixture_logprob_rows")} == IW_EXPORTS
-    for name in IW_EXPORTS:                                                  # one ctypes argument per declared parameter
-        decl = re.search(r"^(?:int|size_t) %s\(([^;]*)\);" % name, section, re.M | re.S).group(1)
+    diag = header[header.index("/* ---- diagonal mixture (csrc/diag_mixture.hip)"):]
+    diag = diag[:diag.index("/* ----", 10)]
+    names = lambda text: set(re.findall(r"^(?:int|size_t) (ladder_[a-z0-9_]+)\(", text, re.M))
+    assert names(section) == IW_EXPORTS
+    assert names(diag) == DIAG_ROWS_EXPORTS | DIAG_TERM_EXPORTS             # one section for the whole family
+    assert len(re.findall(r"ladder_diag_mixture[a-z_]*\(", header)) == 6     # ... and each declared there only
+    assert {n for n in _lib.PROTOTYPES if n.startswith("ladder_iw_")} == IW_EXPORTS
+    assert {n for n in _lib.PROTOTYPES if n.startswith("ladder_diag_mixture_")} == DIAG_ROWS_EXPORTS | DIAG_TERM_EXPORTS
+    for name, text in [(n, section) for n in IW_EXPORTS] + [(n, diag) for n in DIAG_ROWS_EXPORTS]:   # one ctypes argument per declared parameter
+        decl = re.search(r"^(?:int|size_t) %s\(([^;]*)\);" % name, text, re.M | re.S).group(1)
         assert len(decl.split(",")) == len(_lib.PROTOTYPES[name][1]), name
         assert _lib.PROTOTYPES[name][0] is (_lib._z if name.endswith("_bytes") else _lib._i)
         assert _lib.PROTOTYPES[name][1][-1] is _lib._p or name.endswith("_bytes")      # every launch takes the stream last
     for cite in ("codes/base.py:383-396", "codes/models.py:97-103", "codes/base.py:216-254", "codes/base.py:286-297"):
         assert cite in section, cite
+    assert "codes/base.py:216-254" in diag
     assert re.search(r"#define LADDER_ABI_VERSION (\d+)", header).group(1) == "2" == str(_lib.ABI_VERSION)
-    assert "iwll.hip" in build.SOURCES
-    source = open(os.path.join(ROOT, "ladder_latent_data_distribution_modelling_amd", "csrc", "iwll.hip")).read()
-    defined = set(re.findall(r"^(?:int|size_t) (ladder_[a-z0-9_]+)\(", source[source.index('extern "C"'):], re.M))
-    assert defined == IW_EXPORTS
+    assert "iwll.hip" in build.SOURCES and "diag_mixture.hip" in build.SOURCES
+    csrc = os.path.join(ROOT, "ladder_latent_data_distribution_modelling_amd", "csrc")
+    source, mixture = open(os.path.join(csrc, "iwll.hip")).read(), open(os.path.join(csrc, "diag_mixture.hip")).read()
+    assert names(source[source.index('extern "C"'):]) == IW_EXPORTS
+    assert names(mixture[mixture.index('extern "C"'):]) == DIAG_ROWS_EXPORTS | DIAG_TERM_EXPORTS
     assert "atomic" not in source.replace("no atomics", "")                  # every sum has one fixed order
-    wide = open(os.path.join(ROOT, "ladder_latent_data_distribution_modelling_amd", "csrc", "diag_mixture_wide.hip")).read()
-    for text in (source, wide):                                              # the component arithmetic lives in ONE header
-        assert '#include "diag_mixture_common.h"' in text and "dw_component_logp(dw_quad_partial(" in text and "logf(s)" not in text
+    assert "atomic" not in mixture.replace("No floating-point atomics", "")
+    # the component arithmetic of the rows and of the wide term is written ONCE: one scoring loop, called by both kernels, one log s in the prepare kernel
+    assert mixture.count("dm_score_chunk(t, m, is, c, ") == 2 and mixture.count("fmaf(-0.5f, wave_sum(") == 1 and mixture.count("logf(s)") == 1
+    assert "diag_mixture" not in source and "wave_sum(" not in source and "logf(s)" not in source
 
 
 def test_new_names_stay_out_of_the_frozen_families():
@@ -142,7 +153,7 @@ def test_new_names_stay_out_of_the_frozen_families():
     for name in IW_EXPORTS:
         assert not name.startswith(MIXTURE_PREFIXES) and not name.startswith("ladder_pairs_"), name
     table = open(mixture_forms.__file__).read()
-    assert not any(name in table for name in IW_EXPORTS)
+    assert not any(name in table for name in IW_EXPORTS | DIAG_ROWS_EXPORTS)  # (the rows export has one form: nothing to select)
 
 
 # ------------------------------------------------------------------------------------------------ refusals before the device

@@ -26,8 +26,12 @@ EXPECTED = {
                else "ladder_kmeans_wide_assign" if R in WIDE_WIDTHS else KMEANS_REFUSAL),
     "vb": ("estep", lambda K, R: "ladder_vbgmm_shard_estep" if R <= 8 else "ladder_vbgmm_wide_estep" if R <= 64 else VB_REFUSAL),
     "slp": ("optimise", lambda K, R: "ladder_slp_optimise" if R <= 8 else "ladder_slp_wide_optimise" if (R <= 64 and R % 4 == 0) else SLP_REFUSAL),
+    # the VampPrior term: the wide pair exactly where it takes the width, the narrow pair (whose entry refuses before any launch) everywhere else; K has no say
+    "diag_term": ("fwd_bwd", lambda K, R: "ladder_diag_mixture_wide_fwd_bwd" if R in WIDE_WIDTHS else "ladder_diag_mixture_fwd_bwd"),
 }
-MIXTURE_PREFIXES = ("ladder_gmm_", "ladder_mixture_sample", "ladder_emgmm_", "ladder_kmeans_", "ladder_vbgmm_", "ladder_slp_")
+MIXTURE_PREFIXES = ("ladder_gmm_", "ladder_mixture_sample", "ladder_emgmm_", "ladder_kmeans_", "ladder_vbgmm_", "ladder_slp_", "ladder_diag_mixture_")
+# the one mixture export that is deliberately NOT on the table: the per-row log-density of the diagonal mixture has one form, so nothing selects it
+OFF_THE_TABLE = ("ladder_diag_mixture_logprob_rows", "ladder_diag_mixture_logprob_rows_workspace_bytes")
 
 
 @pytest.fixture(scope="module")
@@ -69,7 +73,7 @@ def test_rows_of_an_operation_share_their_role_names_and_say_their_tiers(F):
                 "em": {"state_doubles", "stats_doubles", "shift_doubles", "workspace_bytes", "shift", "estep", "mstep", "prepare"},
                 "kmeans": {"state_doubles", "draws_doubles", "workspace_bytes", "seed", "set_centres", "assign", "update"},
                 "vb": {"state_doubles", "stats_doubles", "workspace_bytes", "moments_doubles", "moments", "estep", "mstep"},
-                "slp": {"state_bytes", "optimise"}}[op] == must, op
+                "slp": {"state_bytes", "optimise"}, "diag_term": {"workspace_bytes", "fwd_bwd"}}[op] == must, op
 
 
 def test_what_differs_in_calling_convention_is_on_the_row(F):
@@ -82,6 +86,8 @@ def test_what_differs_in_calling_convention_is_on_the_row(F):
     assert [r.state_doubles for r in F.FAMILIES["vb"]] == ["ladder_vbgmm_state_doubles", "ladder_vbgmm_wide_state_doubles"]
     assert [r.max_points for r in F.FAMILIES["slp"]] == [None, 2048]
     assert all(r.draws_doubles == "ladder_kmeans_draws_doubles" for r in F.FAMILIES["kmeans"])
+    assert [(r.workspace_bytes, r.query_takes_L) for r in F.FAMILIES["diag_term"]] == [("ladder_diag_mixture_workspace_bytes", False),
+                                                                                     ("ladder_diag_mixture_wide_workspace_bytes", True)]
 
 
 def test_size_queries_that_answer_zero_agree_with_the_rows(F, lib):
@@ -123,9 +129,11 @@ def test_table_and_prototypes_name_the_same_mixture_entries_each_once(F):
     from ladder_latent_data_distribution_modelling_amd import _lib
     in_table = [name for rows in F.FAMILIES.values() for row in rows for name in row.entries.values()]
     assert sorted(set(in_table)) == F.ENTRY_NAMES and all(name in _lib.PROTOTYPES for name in in_table)
-    mixture_exports = sorted(n for n in _lib.PROTOTYPES if n.startswith(MIXTURE_PREFIXES))
+    mixture_exports = sorted(n for n in _lib.PROTOTYPES if n.startswith(MIXTURE_PREFIXES) and n not in OFF_THE_TABLE)
     assert mixture_exports == F.ENTRY_NAMES
-    assert not any(n.startswith("ladder_diag_mixture_") for n in in_table)
+    assert all(n in _lib.PROTOTYPES for n in OFF_THE_TABLE) and not any(n in in_table for n in OFF_THE_TABLE)
+    assert sorted(n for n in in_table if n.startswith("ladder_diag_mixture_")) == sorted(
+        ["ladder_diag_mixture_workspace_bytes", "ladder_diag_mixture_fwd_bwd", "ladder_diag_mixture_wide_workspace_bytes", "ladder_diag_mixture_wide_fwd_bwd"])
     assert len(in_table) == len(set(in_table)) + 1 and in_table.count("ladder_kmeans_draws_doubles") == 2      # the one export two rows share
     with open(F.__file__) as f:
         src = f.read()
